@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the U-Net hot path on MI355X (BASELINE.json: echogram patches/sec, 4ch 256x256).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 without a torchrun environment: this process spawns N ranks itself (one per GPU, RCCL) BEFORE touching
 the GPU and prints rank 0's JSON line; under ``python -m torch.distributed.run --nproc-per-node N ... bench.py
@@ -10,7 +10,9 @@ the GPU and prints rank 0's JSON line; under ``python -m torch.distributed.run -
 A "step" is one pass of the hot path over one batch of synthetic echogram patches already resident in HBM: the
 full training step of the reference loop (forward + weighted CE + backward + SGD, pipeline.py:163-178), batch 32
 per GPU (BASELINE.json configs[1]); for N > 1 the mini-batches shard over ranks and gradients are exchanged
-over RCCL every step (configs[2], weak scaling).  The JSON line also carries
+over RCCL every step (configs[2], weak scaling).  A plain run sets up, warms up, times the K steps and prints the
+headline (``value`` patches/s, ``ms_per_step``); ``--dump-outputs DIR`` then writes what the last timed step computed
+(dump_outputs).  Every other measurement is taken with ``--full`` only; the JSON line then also carries
   * ``infer_patches_per_s``   eval forward + softmax (pipeline.py:205-219) on the same batch;
   * ``parity_mode``           the same two measurements in a precision that meets the north-star parity bar
                               (h3p: fp16 plane pairs, 3 MFMAs per product, ~2^-21: <= 1e-3 rel on logits and identical
@@ -90,6 +92,11 @@ def parse_args(argv=None):
                          "handed to rank 0 point-to-point, asserted complete and in ping order (off by default: the timed legs of "
                          "the scaling run use collectives only; tools/runs/r5_03.sh rehearses it)")
     ap.add_argument("--no-wide", action="store_true", help="skip the configs[4] (wide net, fp16, GPU augmentation) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every other leg: inference, per-kernel roofline passes, tiled survey, parity "
+                         "mode and golden parity, wide net, DataLoader loops, CPU baseline (the --no-* options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--spawn-selftest", action="store_true",
                     help="only start the ranks, all-reduce their ids and print the census (tests/test_bench_spawn.py)")
     return ap.parse_args(argv)
@@ -161,7 +168,10 @@ def cpu_baseline(parity_check=None):
 # ----------------------------------------------------------------------------------------------------------
 # one precision mode: train step + inference + serialized per-kernel pass
 # ----------------------------------------------------------------------------------------------------------
-def measure_mode(args, precision, steps, warmup, world, rank, dev, grad_sync, infer=True, log=print, serial_pass=True):
+def measure_mode(args, precision, steps, warmup, world, rank, dev, grad_sync, infer=True, log=print, serial_pass=True,
+                 per_kernel=True, dump_dir=None):
+    """Warm-up + timed region of the train step in ``precision``.  ``per_kernel``: the instrumented pass, the serialized
+    roofline pass and (N > 1) the exchange probe as well; ``dump_dir``: rank 0 writes the last timed step's outputs."""
     import torch
     import torch.distributed as dist
     import crimac_classifiers_unet_amd as pkg
@@ -214,13 +224,23 @@ def measure_mode(args, precision, steps, warmup, world, rank, dev, grad_sync, in
     # has created and destroyed tens of thousands of events in earlier legs (the parity leg of the default run read 19.6 ms
     # where the same binaries alone read 18.2).  The overlapped per-launch durations come from a short instrumented pass
     # right behind the timed region.
-    if world > 1:
+    if world > 1 and per_kernel:
         eng.exchange_probe = []      # (event after the backward pass, event after the last collective) per step
     t0 = time.perf_counter()
     for _ in range(steps):
         loss = step()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, loss, model, log)
+    res = {"precision": precision, "dtype": DTYPE_LABEL[precision],
+           "train_patches_per_s": world * B * steps / elapsed, "ms_per_step": 1e3 * elapsed / steps,
+           "train_tflops": world * B * steps / elapsed * TRAIN_GFLOP_PER_PATCH * (sf / 64.0) ** 2 / 1e3}
+    if not per_kernel:
+        gc.enable()
+        res.update(check_loss(eng, loss, steps, warmup))
+        log(f"{precision}: timed region done: {res['ms_per_step']:.2f} ms/step")
+        return res, model
     n_ovl = max(3, min(steps, 6))
     hip.PROFILE = []                 # HIP events around the conv / wgrad launches, side stream ON (overlapped durations)
     for _ in range(n_ovl):
@@ -239,13 +259,8 @@ def measure_mode(args, precision, steps, warmup, world, rank, dev, grad_sync, in
                             "pass did not hide); median over the timed steps, max over ranks",
                     "algo": getattr(grad_sync, "algo", None), "bucket_mb": grad_sync.bucket_elems * 4 / (1 << 20),
                     "per_range_optimiser_step": bool(eng.early_sgd and eng.early_sgd_multi)}
-    final_loss = float(loss)
-    assert final_loss == final_loss, "training diverged (NaN loss)"
-    skipped = eng.skipped_steps()
-    assert eng.loss_scale == 1.0 or skipped < steps + warmup, (
-        f"every loss-scaled step was skipped (scale {eng.loss_scale}): the number would be the throughput of steps "
-        "whose update never ran")
-    log(f"{precision}: timed region done: {1e3 * elapsed / steps:.2f} ms/step")
+    res.update(check_loss(eng, loss, steps, warmup))
+    log(f"{precision}: timed region done: {res['ms_per_step']:.2f} ms/step")
 
     # Per-kernel durations: in the timed region the weight gradients run on a side stream CONCURRENTLY with the
     # input-gradient convolutions, so their HIP-event intervals overlap.  The roofline figures come from a second,
@@ -326,10 +341,7 @@ def measure_mode(args, precision, steps, warmup, world, rank, dev, grad_sync, in
             r["mfma_calibration"] = calib
         return r
 
-    res = {"precision": precision, "dtype": DTYPE_LABEL[precision],
-           "train_patches_per_s": world * B * steps / elapsed, "ms_per_step": 1e3 * elapsed / steps,
-           "train_tflops": world * B * steps / elapsed * TRAIN_GFLOP_PER_PATCH * scale_f / 1e3,
-           "final_loss": final_loss, "loss_scale": eng.loss_scale, "skipped_steps": skipped, "exchange": exchange,
+    res.update({"exchange": exchange,
            "roofline": roofline("crimac_conv3x3", CONV_KERNELS if precision in ("bf16", "fp16") else
                                 ("crimac_conv3x3: conv3x3_wch_kernel (plane-pair forms: 3 MFMAs per fragment pair) + conv3x3_c16_kernel "
                                  "(first layer, pseudo-channels)" if precision == "h3p" else
@@ -339,7 +351,7 @@ def measure_mode(args, precision, steps, warmup, world, rank, dev, grad_sync, in
            "roofline_wgrad": roofline("crimac_wgrad", "wgrad_pp_kernel + wgrad_up_pp_kernel + wgrad_kernel (weight gradient, all shapes)"
                                       if precision == "h3p" else
                                       "wgrad_group_kernel (conv3x3 layers of a gradient range in one launch) + wgrad_kernel (first "
-                                      "layer, transposed convolutions)")}
+                                      "layer, transposed convolutions)")})
     if infer:
         model.eval()
         with torch.no_grad():
@@ -354,6 +366,43 @@ def measure_mode(args, precision, steps, warmup, world, rank, dev, grad_sync, in
         res["infer_patches_per_s"] = world * B * steps / ti
         res["infer_tflops"] = res["infer_patches_per_s"] * FWD_GFLOP_PER_PATCH * scale_f / 1e3
     return res, model
+
+
+def check_loss(eng, loss, steps, warmup):
+    """The last timed step's loss, and the guards that keep the figure honest."""
+    final_loss = float(loss)
+    assert final_loss == final_loss, "training diverged (NaN loss)"
+    skipped = eng.skipped_steps()
+    assert eng.loss_scale == 1.0 or skipped < steps + warmup, (
+        f"every loss-scaled step was skipped (scale {eng.loss_scale}): the number would be the throughput of steps "
+        "whose update never ran")
+    return {"final_loss": final_loss, "loss_scale": eng.loss_scale, "skipped_steps": skipped}
+
+
+DUMP_PARAM_SAMPLE = 1 << 22          # parameters written by dump_outputs: 16 MB of float32
+
+
+def dump_outputs(out_dir, loss, model, log):
+    """What a caller of the timed path holds after its last step, as float32 .npy files in ``out_dir``:
+      loss.npy             the step's loss (weighted cross entropy of the batch, before the update), shape [1];
+      params_sample.npy    the updated parameters: a fixed sample (numpy seed 0) of DUMP_PARAM_SAMPLE entries of the flat
+                           parameter vector in state_dict order (all of it when it is smaller);
+      bn_running.npy       every BatchNorm running_mean and running_var after the step, concatenated in state_dict order."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    sd = model.state_dict()
+    params = torch.cat([v.detach().reshape(-1).float() for k, v in model.named_parameters()]).cpu().numpy()
+    if params.size > DUMP_PARAM_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(params.size, DUMP_PARAM_SAMPLE, replace=False))
+        params = params[idx]
+    outs = {"loss": np.array([float(loss)], dtype=np.float32),
+            "params_sample": params.astype(np.float32),
+            "bn_running": torch.cat([v.detach().reshape(-1).float() for k, v in sd.items()
+                                     if k.endswith((".running_mean", ".running_var"))]).cpu().numpy()}
+    for name, a in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{k} {v.shape}" for k, v in outs.items()))
 
 
 _CALIB = {}
@@ -733,14 +782,16 @@ def run_rank(args):
                   "distinct_devices": len({int(d.item()) for d in devs})}
     grad_sync = parallel.GradSync()
     main, model = measure_mode(args, args.precision, args.steps, args.warmup, world, rank, dev, grad_sync,
-                               infer=not args.no_infer, log=log)
+                               infer=args.full and not args.no_infer, log=log, per_kernel=args.full,
+                               dump_dir=args.dump_outputs)
     tiled = None
-    if not args.no_tiled and args.start_filts == 64:
+    if args.full and not args.no_tiled and args.start_filts == 64:
         tiled = measure_tiled(model, args, log, world)
         log(f"tiled: {tiled['patches_per_s']:.0f} patches/s end to end")
     del model
     parity = None
-    if world == 1 and not args.no_parity_mode and args.precision != args.parity_precision and args.start_filts == 64:
+    if (args.full and world == 1 and not args.no_parity_mode and args.precision != args.parity_precision
+            and args.start_filts == 64):
         torch.cuda.empty_cache()
         parity, pm = measure_mode(args, args.parity_precision, max(3, args.steps), max(2, args.warmup), world, rank, dev,
                                   grad_sync, infer=not args.no_infer, log=log)
@@ -758,10 +809,11 @@ def run_rank(args):
             parity["h3p_plane_pair_backward"] = {"train_patches_per_s": hp["train_patches_per_s"], "ms_per_step": hp["ms_per_step"],
                                                  "what": "precision 'h3p': the same forward pass, backward pass on fp16 plane pairs "
                                                          "(the parity mode of round 3)"}
-    main["golden_parity"] = golden_parity(args.precision, dev, log) if (args.start_filts == 64 and rank == 0) else None
+    main["golden_parity"] = (golden_parity(args.precision, dev, log) if (args.full and args.start_filts == 64 and rank == 0)
+                             else None)
 
     wide = None
-    if world == 1 and not args.no_wide and args.start_filts == 64 and not args.gpu_augment:
+    if args.full and world == 1 and not args.no_wide and args.start_filts == 64 and not args.gpu_augment:
         # BASELINE configs[4] on one GPU, driver-timed: 2x channels, fp16 + MFMA with loss scaling, on-GPU add_noise / flip
         torch.cuda.empty_cache()
         wargs = argparse.Namespace(**vars(args))
@@ -780,7 +832,7 @@ def run_rank(args):
     # The loop the reference runs (DataLoader + train_model), LAST of the GPU legs: its DataLoader forks worker processes
     # from this process, and the legs measured after it in the first version of this bench ran 6 % slower
     # (h3p step 27.2 ms in the default run against 25.6 ms on its own, same box, same per-kernel durations)
-    if world == 1 and not args.no_train_loop and args.start_filts == 64 and not args.gpu_augment:
+    if args.full and world == 1 and not args.no_train_loop and args.start_filts == 64 and not args.gpu_augment:
         torch.cuda.empty_cache()
         main["train_loop"] = measure_train_loop(args, args.precision, dev, log, main["train_patches_per_s"])
         main["train_loop"]["inline_copy"] = measure_train_loop(args, args.precision, dev, log, main["train_patches_per_s"],
@@ -809,7 +861,7 @@ def run_rank(args):
         gc.collect()
     if rank == 0:
         sf = args.start_filts
-        rl = main["roofline"]
+        rl = main.get("roofline")
         def replay(roof, roof_w, prec):
             """HBM traffic (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes) and MFMA busy fraction (SQ_VALU_MFMA_BUSY_CYCLES /
             GRBM_GUI_ACTIVE pass) of the same command, from the committed profiles of this round -- labelled as replayed."""
@@ -831,7 +883,7 @@ def run_rank(args):
                     r_["util_source"] = "REPLAYED from the committed profile " + ut["_file"] + " (not observed in this run): " + str(ut.get("note"))
             # (no replayed clocks: the shader clock under a dense MFMA stream is OBSERVED in this run, before and after
             # the serialized pass -- roofline.mfma_calibration)
-        if sf == 64 and args.precision in ("bf16", "h3p", "h3f"):
+        if args.full and sf == 64 and args.precision in ("bf16", "h3p", "h3f"):
             replay(rl, main["roofline_wgrad"], args.precision)
         if parity is not None and args.parity_precision in ("bf16", "h3p", "h3f"):
             replay(parity["roofline"], parity["roofline_wgrad"], args.parity_precision)
@@ -859,7 +911,7 @@ def run_rank(args):
             "infer_tflops": main.get("infer_tflops"),
             "final_loss": main["final_loss"], "loss_scale": main["loss_scale"], "skipped_steps": main["skipped_steps"],
             "golden_parity": main["golden_parity"],
-            "roofline": rl, "roofline_wgrad": main["roofline_wgrad"],
+            "roofline": rl, "roofline_wgrad": main.get("roofline_wgrad"),
         }
         if main.get("train_loop") is not None:
             out["train_loop"] = main["train_loop"]
@@ -873,7 +925,7 @@ def run_rank(args):
             out["tiled"] = tiled
         if wide is not None:
             out["wide_fp16"] = wide
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             def parity32(x32, ref_logits):
                 """The parity precision on the 32 crops the oracle has just been timed on: logits rel, argmax flips and the
                 oracle's own top-2 margin at every flipped pixel (a flip below ~2e-6 is the oracle's fp32 round-off)."""

@@ -76,3 +76,25 @@ def test_failed_rank_stops_the_job_at_eight_ranks():
     code = "import os,sys,time\nif os.environ['RANK']=='5': sys.exit(9)\ntime.sleep(60)\n"
     rc, _ = launch.spawn_ranks([sys.executable, "-c", code], 8, timeout=30)
     assert rc == 9
+
+
+def test_dump_outputs_writes_the_step_outputs_as_float32_within_64_mb(tmp_path):
+    """--dump-outputs: float32 .npy files, 64 MB at most in all, and the same parameter sample in every run."""
+    import numpy as np
+    import torch
+    import bench
+    import crimac_classifiers_unet_amd as pkg
+    from crimac_classifiers_unet_amd import synth
+    m = pkg.UNet_Baseline(3, 4)
+    m.load_state_dict(synth.synth_state_dict(seed=0))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(1.25), m, lambda msg: None)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["bn_running.npy", "loss.npy", "params_sample.npy"]
+    arrays = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["loss.npy"].tolist() == [1.25]
+    assert arrays["params_sample.npy"].size == bench.DUMP_PARAM_SAMPLE
+    for n in names:
+        assert np.array_equal(arrays[n], np.load(tmp_path / "b" / n))

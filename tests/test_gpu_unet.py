@@ -1396,8 +1396,11 @@ def test_row_major_fallback_of_the_weight_planes_is_bit_identical(precision):
         out[tag] = (float(loss), float(loss2), eng.flat_p.clone(), logits)
     assert torch.equal(out["frag"][3], out["row"][3])     # eval forward (no atomics anywhere): bit for bit
     # the first step's forward has the same weights and the same planes' VALUES; its BatchNorm statistics are added up by
-    # atomics in arrival order, so two runs of ONE layout already differ in the last bit now and then
-    assert abs(out["frag"][0] - out["row"][0]) <= 2e-6 * abs(out["frag"][0])
+    # atomics in arrival order, so two runs of ONE layout already differ in the last bit now and then.  In bf16 that bit
+    # moves 16-bit roundings downstream: fresh models of one layout give step-1 losses 3.06e-6 apart (six per layout, both
+    # layouts: the same two values), so the bar is a few of those steps; h3f's fp32-class arithmetic stays within 1e-7
+    tol = 1e-5 if precision == "bf16" else 2e-6
+    assert abs(out["frag"][0] - out["row"][0]) <= tol * abs(out["frag"][0])
     # (weight gradients are summed by atomics in arrival order: what follows an update agrees to round-off only)
     assert abs(out["frag"][1] - out["row"][1]) <= 2e-3 * abs(out["frag"][1])
     rel = float((out["frag"][2] - out["row"][2]).abs().max() / out["frag"][2].abs().max())
@@ -1410,7 +1413,7 @@ def test_row_major_fallback_of_the_weight_planes_is_bit_identical(precision):
     eng.bind()
     eng._wfrag_geometry(4096, 256, 256)
     l3 = float(eng.train_step(x, lab, cw, lr=0.005, momentum=0.95))
-    assert any(pk.get("fwd_frag") for pk in eng.pk_main.values()) and abs(l3 - out["frag"][0]) <= 2e-6 * abs(l3)
+    assert any(pk.get("fwd_frag") for pk in eng.pk_main.values()) and abs(l3 - out["frag"][0]) <= tol * abs(l3)
 
 
 @pytest.mark.parametrize("workers,dtype", [(2, np.float32), (0, np.float64)])

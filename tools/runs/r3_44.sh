@@ -2,11 +2,12 @@
 # rocprofv3 kernel stats of the DEFAULT bench command (all legs), for profiles/
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
+BENCH=$PWD/bench.py      # (absolute: the profiled runs start from another directory)
 R=$GRAFT_REPO_ROOT/gpurun_out/r3_44
 mkdir -p $R
 export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/p -- python3 $GRAFT_REPO_ROOT/bench.py > $R/bench.json 2> $R/bench.err || { echo failed; tail -20 $R/bench.err; exit 1; }
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/p -- python3 "$BENCH" --full > $R/bench.json 2> $R/bench.err || { echo failed; tail -20 $R/bench.err; exit 1; }
 f=$(find $R/p -name "*kernel_stats.csv" | head -1); cp $f $R/default_bench_kernel_stats.csv
 rm -rf $R/p
 head -12 $R/default_bench_kernel_stats.csv | cut -c1-160

@@ -2,7 +2,7 @@
 # A/B inside one call: bf16 step with the normal library vs the -DCRIMAC_EXP_NOATOMIC build of wgrad.hip (the
 # weight-gradient flush skipped: results are wrong, timing is an UPPER BOUND of what hiding the flush can give).
 cd "$(dirname "$0")/../.." || exit 1
-B="python bench.py --no-cpu-baseline --no-parity-mode --no-tiled --no-wide --no-train-loop --no-infer --steps 40 --warmup 10 --roofline-steps 12 --roofline-warmup 4"
+B="python bench.py --full --no-cpu-baseline --no-parity-mode --no-tiled --no-wide --no-train-loop --no-infer --steps 40 --warmup 10 --roofline-steps 12 --roofline-warmup 4"
 for i in 1 2 3; do
   $B > gpurun_out/r4_01_base_$i.json 2> gpurun_out/r4_01_base_$i.err || exit 1
   CRIMAC_LIB=$PWD/gpurun_exp_noatomic.so $B > gpurun_out/r4_01_noatomic_$i.json 2> gpurun_out/r4_01_noatomic_$i.err || exit 1

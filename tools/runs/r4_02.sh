@@ -2,7 +2,7 @@
 # A/B inside one call: bf16 (and fp16) step with the conv3x3 weight gradients grouped per gradient range
 # (crimac_wgrad_group) against one launch per layer, and the plan's items per layer / layers per launch.
 cd "$(dirname "$0")/../.." || exit 1
-B="python bench.py --no-cpu-baseline --no-parity-mode --no-tiled --no-wide --no-train-loop --no-infer --steps 40 --warmup 10 --roofline-steps 12 --roofline-warmup 4"
+B="python bench.py --full --no-cpu-baseline --no-parity-mode --no-tiled --no-wide --no-train-loop --no-infer --steps 40 --warmup 10 --roofline-steps 12 --roofline-warmup 4"
 run() {   # tag, env...
   tag=$1; shift
   env "$@" $B > gpurun_out/r4_02_$tag.json 2> gpurun_out/r4_02_$tag.err || { echo "$tag failed"; tail -5 gpurun_out/r4_02_$tag.err; exit 1; }

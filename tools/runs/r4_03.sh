@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B inside one call, plane-pair precision (h3p): conv3x3 weight gradients grouped per gradient range vs one launch per layer.
 cd "$(dirname "$0")/../.." || exit 1
-B="python bench.py --precision h3p --no-cpu-baseline --no-parity-mode --no-tiled --no-wide --no-train-loop --no-infer --steps 20 --warmup 5 --roofline-steps 8 --roofline-warmup 3"
+B="python bench.py --full --precision h3p --no-cpu-baseline --no-parity-mode --no-tiled --no-wide --no-train-loop --no-infer --steps 20 --warmup 5 --roofline-steps 8 --roofline-warmup 3"
 run() { tag=$1; shift; env "$@" $B > gpurun_out/r4_03_$tag.json 2> gpurun_out/r4_03_$tag.err || { echo "$tag failed"; tail -5 gpurun_out/r4_03_$tag.err; exit 1; }; }
 for i in 1 2; do
   run off_$i CRIMAC_WGRAD_GROUP=0

@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/../.." || exit 1
 run() {   # tag, precision, env...
   tag=$1; prec=$2; shift 2
-  env "$@" python bench.py --precision $prec --no-cpu-baseline --no-parity-mode --no-tiled --no-wide --no-train-loop \
+  env "$@" python bench.py --full --precision $prec --no-cpu-baseline --no-parity-mode --no-tiled --no-wide --no-train-loop \
       --steps 30 --warmup 8 --roofline-steps 10 --roofline-warmup 3 > gpurun_out/r4_04_$tag.json 2> gpurun_out/r4_04_$tag.err \
       || { echo "$tag failed"; tail -5 gpurun_out/r4_04_$tag.err; exit 1; }
 }

@@ -6,7 +6,7 @@ A="--no-cpu-baseline --no-tiled --no-parity-mode --no-infer --no-wide --no-train
 for i in 1 2; do
   for P in bf16 h3f; do
     for F in 0 1; do
-      CRIMAC_FUSE_UNPOOL_APPLY=$F timeout -k 10 200 python bench.py --precision $P $A > $R/${P}_f${F}_$i.json 2> $R/${P}_f${F}_$i.err || exit 1
+      CRIMAC_FUSE_UNPOOL_APPLY=$F timeout -k 10 200 python bench.py --full --precision $P $A > $R/${P}_f${F}_$i.json 2> $R/${P}_f${F}_$i.err || exit 1
       python -c "import json,sys; d=json.load(open('$R/${P}_f${F}_$i.json')); print('$P fuse=$F run $i: %.3f ms/step' % d['ms_per_step'])"
     done
   done

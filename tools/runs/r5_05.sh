@@ -13,7 +13,7 @@ done
 paste <(grep -n crimac_conv3x3 $R/launches_short0.txt | awk '{print $1, $3, $6}') <(grep crimac_conv3x3 $R/launches_short2.txt | awk '{print $6}') <(grep crimac_conv3x3 $R/launches_short1.txt | awk '{print $6}')
 BARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-tiled --no-parity-mode --no-wide --no-train-loop"
 for S in 0 2 0 2; do
-  CRIMAC_CONV_SHORT=$S timeout -k 10 200 python bench.py $BARGS > $R/bench_short$S.json 2> $R/bench_short$S.err || { tail $R/bench_short$S.err; exit 1; }
+  CRIMAC_CONV_SHORT=$S timeout -k 10 200 python bench.py --full $BARGS > $R/bench_short$S.json 2> $R/bench_short$S.err || { tail $R/bench_short$S.err; exit 1; }
   python -c "
 import json; d=json.load(open('$R/bench_short$S.json')); print('short=$S', round(d['ms_per_step'],3), 'ms', round(d['roofline']['frac'],4), 'conv frac', round(d['infer_patches_per_s']), 'infer')"
 done

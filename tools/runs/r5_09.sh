@@ -14,7 +14,7 @@ done
 paste <(grep crimac_conv3x3 $R/launches_wfrag0.txt | awk '{print $1, $3, $6}') <(grep crimac_conv3x3 $R/launches_wfrag1.txt | awk '{print $6}')
 BARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-tiled --no-parity-mode --no-wide --no-train-loop"
 for S in 0 1 0 1; do
-  CRIMAC_WFRAG=$S timeout -k 10 200 python bench.py $BARGS > $R/bench_wfrag$S.json 2> $R/bench_wfrag$S.err || { tail $R/bench_wfrag$S.err; exit 1; }
+  CRIMAC_WFRAG=$S timeout -k 10 200 python bench.py --full $BARGS > $R/bench_wfrag$S.json 2> $R/bench_wfrag$S.err || { tail $R/bench_wfrag$S.err; exit 1; }
   python -c "
 import json; d=json.load(open('$R/bench_wfrag$S.json')); print('wfrag=$S', round(d['ms_per_step'],3), 'ms', round(d['roofline']['frac'],4), 'conv frac', round(d['infer_patches_per_s']), 'infer', d['golden_parity']['eval_argmax_flips'], 'flips')"
 done

@@ -8,7 +8,7 @@ tail -2 $R/pytest.log
 BARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-tiled --no-parity-mode --no-wide --no-train-loop"
 for P in h3f bf16; do
 for S in 0 1 0 1; do
-  CRIMAC_WFRAG=$S timeout -k 10 300 python bench.py --precision $P $BARGS > $R/bench_${P}_wfrag$S.json 2> $R/bench_${P}_wfrag$S.err || { tail $R/bench_${P}_wfrag$S.err; exit 1; }
+  CRIMAC_WFRAG=$S timeout -k 10 300 python bench.py --full --precision $P $BARGS > $R/bench_${P}_wfrag$S.json 2> $R/bench_${P}_wfrag$S.err || { tail $R/bench_${P}_wfrag$S.err; exit 1; }
   python -c "
 import json; d=json.load(open('$R/bench_${P}_wfrag$S.json')); print('$P wfrag=$S', round(d['ms_per_step'],3), 'ms', round(d['roofline']['frac'],4), 'conv frac', round(d['infer_patches_per_s']), 'infer', d['golden_parity']['eval_argmax_flips'], 'flips', d['golden_parity']['eval_logits_rel'])"
 done

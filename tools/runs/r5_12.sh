@@ -11,7 +11,7 @@ echo "--- new"; cat $R/unpool_new.txt; echo "--- old"; cat $R/unpool_old.txt
 BARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-tiled --no-parity-mode --no-wide --no-train-loop --no-infer"
 for L in old new old new; do
   if [ "$L" = old ]; then export CRIMAC_LIB=$GRAFT_REPO_ROOT/gpurun_exp_prev.so; else unset CRIMAC_LIB; fi
-  timeout -k 10 200 python bench.py $BARGS > $R/bench_$L.json 2> $R/bench_$L.err || { tail $R/bench_$L.err; exit 1; }
+  timeout -k 10 200 python bench.py --full $BARGS > $R/bench_$L.json 2> $R/bench_$L.err || { tail $R/bench_$L.err; exit 1; }
   python -c "
 import json; d=json.load(open('$R/bench_$L.json')); print('$L', round(d['ms_per_step'],3), 'ms')"
 done

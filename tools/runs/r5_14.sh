@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT/gpurun_out/r5_14; mkdir -p $R
 BARGS="--steps 30 --warmup 5 --no-cpu-baseline --no-tiled --no-parity-mode --no-wide --no-train-loop --no-infer"
 for V in none single all none single all; do
   if [ "$V" = none ]; then unset CRIMAC_EXP_SKIP_WGRAD; else export CRIMAC_EXP_SKIP_WGRAD=$V; fi
-  timeout -k 10 200 python bench.py $BARGS > $R/bench_$V.json 2> $R/bench_$V.err || { tail $R/bench_$V.err; exit 1; }
+  timeout -k 10 200 python bench.py --full $BARGS > $R/bench_$V.json 2> $R/bench_$V.err || { tail $R/bench_$V.err; exit 1; }
   python -c "
 import json; d=json.load(open('$R/bench_$V.json')); print('skip=$V', round(d['ms_per_step'],3), 'ms')"
 done

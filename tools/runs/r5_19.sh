@@ -11,7 +11,7 @@ timeout -k 10 200 python tools/step_launches.py bf16 30 > $R/bf16_serial_per_lau
 grep -c crimac_conv3x3 $R/bf16_serial_per_launch.txt; echo "conv: $(grep crimac_conv3x3 $R/bf16_serial_per_launch.txt | awk '{s+=$6} END {print s}') us"; sed -n 20,30p $R/bf16_serial_per_launch.txt
 BARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-tiled --no-parity-mode --no-wide --no-train-loop"
 for S in 1 2; do
-  timeout -k 10 200 python bench.py $BARGS > $R/bench_$S.json 2> $R/bench_$S.err || { tail $R/bench_$S.err; exit 1; }
+  timeout -k 10 200 python bench.py --full $BARGS > $R/bench_$S.json 2> $R/bench_$S.err || { tail $R/bench_$S.err; exit 1; }
   python -c "
 import json; d=json.load(open('$R/bench_$S.json')); print(round(d['ms_per_step'],3), 'ms', round(d['roofline']['frac'],4), 'conv frac', d['roofline']['launches_per_step'], 'launches', round(d['roofline_wgrad']['frac'],4))"
 done

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT/gpurun_out/r5_21; mkdir -p $R
 BARGS="--steps 30 --warmup 5 --no-cpu-baseline --no-tiled --no-parity-mode --no-wide --no-train-loop --no-infer"
 for V in off 1 12 012 2 off 1 12 012 2; do
   if [ "$V" = off ]; then unset CRIMAC_WGRAD_MERGE; else export CRIMAC_WGRAD_MERGE=$V; fi
-  timeout -k 10 200 python bench.py $BARGS > $R/bench_$V.json 2> $R/bench_$V.err || { tail $R/bench_$V.err; exit 1; }
+  timeout -k 10 200 python bench.py --full $BARGS > $R/bench_$V.json 2> $R/bench_$V.err || { tail $R/bench_$V.err; exit 1; }
   python -c "
 import json; d=json.load(open('$R/bench_$V.json')); print('merge=$V', round(d['ms_per_step'],3), 'ms', 'wgrad frac', d.get('roofline_wgrad',{}).get('frac'))"
 done

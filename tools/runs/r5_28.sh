@@ -7,6 +7,6 @@ timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $R/pytest_gpu.log 2>&1 
 tail -3 $R/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $R/smoke.log 2>&1 || { tail -20 $R/smoke.log; exit 1; }
 tail -2 $R/smoke.log
-timeout -k 10 600 python bench.py > $R/bench_c.json 2> $R/bench_c.err || { tail -30 $R/bench_c.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $R/bench_c.json 2> $R/bench_c.err || { tail -30 $R/bench_c.err; exit 1; }
 grep "timed region\|train_loop\|tiled\|wide" $R/bench_c.err
 echo r5_28 done

@@ -15,7 +15,7 @@ paste <(grep crimac_conv3x3 $R/launches_old.txt | awk '{print $1, $3, $6}') <(gr
 BARGS="--steps 30 --warmup 5 --no-cpu-baseline --no-tiled --no-parity-mode --no-wide --no-train-loop"
 for V in old new old new; do
   if [ "$V" = new ]; then unset CRIMAC_LIB; else export CRIMAC_LIB=$GRAFT_REPO_ROOT/gpurun_exp_p64old.so; fi
-  timeout -k 10 200 python bench.py $BARGS > $R/bench_$V.json 2> $R/bench_$V.err || { tail $R/bench_$V.err; exit 1; }
+  timeout -k 10 200 python bench.py --full $BARGS > $R/bench_$V.json 2> $R/bench_$V.err || { tail $R/bench_$V.err; exit 1; }
   python -c "
 import json; d=json.load(open('$R/bench_$V.json')); print('$V', round(d['ms_per_step'],3), 'ms', round(d['infer_patches_per_s']), 'infer', round(d['roofline']['frac'],4))"
 done

@@ -2,18 +2,19 @@
 # round-5 profile refresh for both benched precisions: kernel stats (two streams + serialized), PMC traffic, MFMA busy
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
+BENCH=$PWD/bench.py      # (absolute: the profiled runs start from another directory)
 R=$GRAFT_REPO_ROOT/gpurun_out/r5_profiles
 mkdir -p $R
 export TMPDIR=/tmp
 for P in ${PRECS:-bf16 h3f}; do
   BARGS="--precision $P --steps 4 --warmup 2 --no-cpu-baseline --no-tiled --no-parity-mode --no-infer --no-wide --no-train-loop --roofline-steps 3 --roofline-warmup 1"
   cd /tmp
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/${P}_prof -- python3 $GRAFT_REPO_ROOT/bench.py $BARGS > $R/${P}_prof.log 2>&1 || { echo prof failed; tail -20 $R/${P}_prof.log; exit 1; }
-  CRIMAC_WGRAD_STREAM=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/${P}_prof_serial -- python3 $GRAFT_REPO_ROOT/bench.py $BARGS > $R/${P}_prof_serial.log 2>&1 || { echo prof serial failed; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/${P}_prof -- python3 "$BENCH" --full $BARGS > $R/${P}_prof.log 2>&1 || { echo prof failed; tail -20 $R/${P}_prof.log; exit 1; }
+  CRIMAC_WGRAD_STREAM=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/${P}_prof_serial -- python3 "$BENCH" --full $BARGS > $R/${P}_prof_serial.log 2>&1 || { echo prof serial failed; exit 1; }
   echo "$P kernel traces ok"
-  CRIMAC_WGRAD_STREAM=0 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/${P}_pmc_fetch -- python3 $GRAFT_REPO_ROOT/bench.py $BARGS > $R/${P}_pmc_fetch.log 2>&1 || { echo pmc fetch failed; exit 1; }
-  CRIMAC_WGRAD_STREAM=0 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $R/${P}_pmc_write -- python3 $GRAFT_REPO_ROOT/bench.py $BARGS > $R/${P}_pmc_write.log 2>&1 || { echo pmc write failed; exit 1; }
-  CRIMAC_WGRAD_STREAM=0 timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $R/${P}_pmc_mfma -- python3 $GRAFT_REPO_ROOT/bench.py $BARGS > $R/${P}_pmc_mfma.log 2>&1 || { echo pmc mfma failed; exit 1; }
+  CRIMAC_WGRAD_STREAM=0 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/${P}_pmc_fetch -- python3 "$BENCH" --full $BARGS > $R/${P}_pmc_fetch.log 2>&1 || { echo pmc fetch failed; exit 1; }
+  CRIMAC_WGRAD_STREAM=0 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $R/${P}_pmc_write -- python3 "$BENCH" --full $BARGS > $R/${P}_pmc_write.log 2>&1 || { echo pmc write failed; exit 1; }
+  CRIMAC_WGRAD_STREAM=0 timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $R/${P}_pmc_mfma -- python3 "$BENCH" --full $BARGS > $R/${P}_pmc_mfma.log 2>&1 || { echo pmc mfma failed; exit 1; }
   echo "$P pmc ok"
   cd $GRAFT_REPO_ROOT
   for d in prof prof_serial; do
