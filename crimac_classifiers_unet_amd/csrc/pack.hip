@@ -22,7 +22,7 @@ struct LayerDesc {             // mirrors crimac_layer_desc (include/crimac_unet
   unsigned short* fwd_lo;
   unsigned short* dg_hi;
   unsigned short* dg_lo;
-  int kind, Co, Ci, Ci_pad;  // (kind: bit 0 only here; the fragment-major flags travel in `frag`)
+  int kind, Co, Ci, Ci_pad;  // (kind: 0, 1 or 2 here; the fragment-major flags travel in `frag`)
   int dw_splits;             // partial slabs of dw to add up (crimac_wgrad_partials); <= 1: dw is the gradient
   long dw_stride;            // floats between slabs
   int frag;                  // bit 0: fwd_hi fragment-major, bit 1: dg_hi fragment-major (common.h wfrag_index)
@@ -37,12 +37,15 @@ struct Table {
 // Geometry of a layer seen as [outer][inner][taps] in the torch layout:
 //   kind 0 (conv3x3,  w[Co][Ci][3][3]): outer = co, inner = ci, taps = 9
 //   kind 1 (upconv2x2, w[Ci][Co][2][2]): outer = ci, inner = co, taps = 4
+//   kind 2 (conv1x1,  w[Co][Ci][1][1]): outer = co, inner = ci, taps = 1 (laid out like kind 0 with one tap)
 struct Geo {
   int outer, inner, inner_pad, taps, tiles_inner;
 };
+__device__ __host__ inline int taps_of(int kind) { return kind == 0 ? 9 : (kind == 1 ? 4 : 1); }
 __device__ __host__ inline Geo geo_of(int kind, int Co, int Ci, int Ci_pad) {
   Geo g;
   if (kind == 0) { g.outer = Co; g.inner = Ci; g.inner_pad = Ci_pad; g.taps = 9; }
+  else if (kind == 2) { g.outer = Co; g.inner = Ci; g.inner_pad = Ci; g.taps = 1; }
   else { g.outer = Ci; g.inner = Co; g.inner_pad = Co; g.taps = 4; }
   g.tiles_inner = (g.inner_pad + TILE - 1) / TILE;
   return g;
@@ -125,11 +128,15 @@ __global__ __launch_bounds__(256) void pack_layers_kernel(Table tb, int planes_a
   }
   __syncthreads();
   const long n = (long)T * g.outer * g.inner_pad;
-  // pass A, inner index fastest: conv3x3 forward panel [t][co][ci_pad] / upconv dgrad panel [ab][ci][co]
-  unsigned short* a_hi = d.kind == 0 ? d.fwd_hi : d.dg_hi;
-  unsigned short* a_lo = d.kind == 0 ? d.fwd_lo : d.dg_lo;
-  const int a_fp16 = d.kind == 0 ? pf.fwd_fp16 : pf.dg_fp16, b_fp16 = d.kind == 0 ? pf.dg_fp16 : pf.fwd_fp16;
-  const float a_sc = d.kind == 0 ? pf.fwd_scale : pf.dg_scale, b_sc = d.kind == 0 ? pf.dg_scale : pf.fwd_scale;
+  // pass A, inner index fastest: conv3x3 forward panel [t][co][ci_pad] / upconv dgrad panel [ab][ci][co] / conv1x1 forward
+  // panel [co][ci]
+  const bool co_outer = d.kind != 1;
+  unsigned short* a_hi = co_outer ? d.fwd_hi : d.dg_hi;
+  unsigned short* a_lo = co_outer ? d.fwd_lo : d.dg_lo;
+  const int a_fp16 = co_outer ? pf.fwd_fp16 : pf.dg_fp16, b_fp16 = co_outer ? pf.dg_fp16 : pf.fwd_fp16;
+  const float a_sc = co_outer ? pf.fwd_scale : pf.dg_scale, b_sc = co_outer ? pf.dg_scale : pf.fwd_scale;
+  // (conv1x1 planes are never interleaved: the plane-pair mode runs them on the F32H3 split, two separate planes)
+  const bool ilv = pf.interleaved && d.kind != 2;
   if (a_hi && g.inner_pad % 8 == 0) {
     for (int idx = threadIdx.x; idx < T * TILE * (TILE / 8); idx += 256) {
       const int il = (idx % (TILE / 8)) * 8, ol = (idx / (TILE / 8)) % TILE, t = idx / (TILE * TILE / 8);
@@ -137,8 +144,8 @@ __global__ __launch_bounds__(256) void pack_layers_kernel(Table tb, int planes_a
       float v[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = tile[ol][(il + q) * T + t] * a_sc;
-      if (pf.interleaved && (d.frag & 1)) put_planes8_il_frag(v, a_hi, t, o0 + ol, g.outer, i0 + il, g.inner_pad, a_fp16);
-      else if (pf.interleaved) put_planes8_il(v, a_hi, (long)t * g.outer + o0 + ol, i0 + il, g.inner_pad, a_fp16);
+      if (ilv && (d.frag & 1)) put_planes8_il_frag(v, a_hi, t, o0 + ol, g.outer, i0 + il, g.inner_pad, a_fp16);
+      else if (ilv) put_planes8_il(v, a_hi, (long)t * g.outer + o0 + ol, i0 + il, g.inner_pad, a_fp16);
       else if (d.frag & 1) put_planes8(v, npl, a_hi, a_lo, wfrag_index(t, o0 + ol, i0 + il, g.outer, g.inner_pad), n, a_fp16);
       else put_planes8(v, npl, a_hi, a_lo, ((long)t * g.outer + o0 + ol) * g.inner_pad + i0 + il, n, a_fp16);
     }
@@ -150,19 +157,20 @@ __global__ __launch_bounds__(256) void pack_layers_kernel(Table tb, int planes_a
                   ((long)t * g.outer + o0 + ol) * g.inner_pad + i0 + il, n, a_fp16);
     }
   }
-  // pass B, outer index fastest: conv3x3 dgrad panel [8-t][ci][co] / upconv forward panel [ab][co][ci]
-  unsigned short* b_hi = d.kind == 0 ? d.dg_hi : d.fwd_hi;
-  unsigned short* b_lo = d.kind == 0 ? d.dg_lo : d.fwd_lo;
+  // pass B, outer index fastest: conv3x3 dgrad panel [8-t][ci][co] / upconv forward panel [ab][co][ci] / conv1x1 dgrad
+  // panel [ci][co]
+  unsigned short* b_hi = co_outer ? d.dg_hi : d.fwd_hi;
+  unsigned short* b_lo = co_outer ? d.dg_lo : d.fwd_lo;
   if (b_hi) {              // (outer is a multiple of 32: the 16-byte stores are aligned)
     for (int idx = threadIdx.x; idx < T * TILE * (TILE / 8); idx += 256) {
       const int ol = (idx % (TILE / 8)) * 8, il = (idx / (TILE / 8)) % TILE, t = idx / (TILE * TILE / 8);
       if (i0 + il >= g.inner) continue;
-      const int tt = d.kind == 0 ? T - 1 - t : t;
+      const int tt = co_outer ? T - 1 - t : t;
       float v[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = tile[ol + q][il * T + t] * b_sc;
-      if (pf.interleaved && (d.frag & 2)) put_planes8_il_frag(v, b_hi, tt, i0 + il, g.inner, o0 + ol, g.outer, b_fp16);
-      else if (pf.interleaved) put_planes8_il(v, b_hi, (long)tt * g.inner + i0 + il, o0 + ol, g.outer, b_fp16);
+      if (ilv && (d.frag & 2)) put_planes8_il_frag(v, b_hi, tt, i0 + il, g.inner, o0 + ol, g.outer, b_fp16);
+      else if (ilv) put_planes8_il(v, b_hi, (long)tt * g.inner + i0 + il, o0 + ol, g.outer, b_fp16);
       else if (d.frag & 2) put_planes8(v, npl, b_hi, b_lo, wfrag_index(tt, i0 + il, o0 + ol, g.inner, g.outer), n, b_fp16);
       else put_planes8(v, npl, b_hi, b_lo, ((long)tt * g.inner + i0 + il) * g.outer + o0 + ol, n, b_fp16);
     }
@@ -261,9 +269,9 @@ int run_layers(const HostDesc* descs, int n, int mode, int planes_arg, hipStream
     for (int i = 0; i < tb.n; ++i) {
       HostDesc h = descs[base + i];
       const int frag = ((h.kind & CRIMAC_LAYER_FWD_FRAG) ? 1 : 0) | ((h.kind & CRIMAC_LAYER_DG_FRAG) ? 2 : 0);
-      CRIMAC_REQUIRE((h.kind & ~(1 | CRIMAC_LAYER_FWD_FRAG | CRIMAC_LAYER_DG_FRAG)) == 0 && h.Co > 0 && h.Ci > 0,
-                     "layer %d: bad kind/shape", base + i);
-      h.kind &= 1;
+      CRIMAC_REQUIRE((h.kind & ~(3 | CRIMAC_LAYER_FWD_FRAG | CRIMAC_LAYER_DG_FRAG)) == 0 && (h.kind & 3) != 3 && h.Co > 0 &&
+                     h.Ci > 0, "layer %d: bad kind/shape", base + i);
+      h.kind &= 3;
       if (frag && mode == 0) {
         const bool ilv = (planes_arg & CRIMAC_PLANES_INTERLEAVED) != 0;
         const int kq = ilv ? 32 : 64;        // (a 64-deep chunk of the row of halves is 32 channels of a plane pair)
@@ -282,6 +290,8 @@ int run_layers(const HostDesc* descs, int n, int mode, int planes_arg, hipStream
         CRIMAC_REQUIRE(h.w && h.fwd_hi && (planes == 1 || il || h.fwd_lo) && (planes == 1 || il || !h.dg_hi || h.dg_lo),
                        "layer %d: missing weight / plane pointers", base + i);
         CRIMAC_REQUIRE(!il || h.kind == 1 || h.Ci_pad % 8 == 0, "layer %d: interleaved planes need Ci_pad %% 8 == 0", base + i);
+        CRIMAC_REQUIRE(h.kind != 2 || planes == 1 || (h.fwd_lo && (!h.dg_hi || h.dg_lo)),
+                       "layer %d: a 1x1 layer's low planes are separate buffers in every multi-plane mode", base + i);
         CRIMAC_REQUIRE(h.kind == 1 || !h.dg_hi || h.Ci_pad == h.Ci, "layer %d: dgrad planes need Ci_pad == Ci",
                        base + i);
       } else {
@@ -295,7 +305,7 @@ int run_layers(const HostDesc* descs, int n, int mode, int planes_arg, hipStream
       d.dw_splits = h.dw_splits; d.dw_stride = h.dw_stride;
       d.frag = mode == 0 ? frag : 0;
       if (mode == 1)
-        CRIMAC_REQUIRE(h.dw_splits <= 1 || h.dw_stride >= (long)(h.kind == 0 ? 9L * h.Co * h.Ci_pad : 4L * h.Co * h.Ci),
+        CRIMAC_REQUIRE(h.dw_splits <= 1 || h.dw_stride >= (long)taps_of(h.kind) * h.Co * (h.kind == 0 ? h.Ci_pad : h.Ci),
                        "layer %d: dw_stride smaller than one packed gradient", base + i);
       const Geo g = geo_of(d.kind, d.Co, d.Ci, d.Ci_pad);
       tb.first[i] = total;
@@ -310,7 +320,7 @@ int run_layers(const HostDesc* descs, int n, int mode, int planes_arg, hipStream
       for (int i = 0; i < tb.n; ++i) {
         const LayerDesc& d = tb.d[i];
         if (d.dw_splits <= kFold) continue;
-        const long nfl = (long)(d.kind == 0 ? 9 : 4) * d.Co * d.Ci_pad;
+        const long nfl = (long)taps_of(d.kind) * d.Co * d.Ci_pad;
         CRIMAC_REQUIRE(nfl % 4 == 0 && d.dw_stride % 4 == 0 && ((uintptr_t)d.dw % 16 == 0),
                        "layer %d: partial slabs must be 16-byte aligned", base + i);
         ft.dw[ft.n] = const_cast<float*>(d.dw); ft.stride[ft.n] = d.dw_stride; ft.splits[ft.n] = d.dw_splits;

@@ -64,8 +64,12 @@ class _ConvBlock:
 
 
 class _UpConv:
-    def __init__(self, key, cin, cout):
-        self.key, self.cin, self.cout = key, cin, cout
+    """The up-sampling layer of a decoder stage: ConvTranspose2d(k2, s2) (up_mode 'transpose', key ``upconv``) or
+    Upsample(bilinear, x2) + conv1x1 (up_mode 'upsample', key ``upconv.1``; csrc/upsample.hip)."""
+
+    def __init__(self, key, cin, cout, mode="transpose"):
+        self.key, self.cin, self.cout, self.mode = key, cin, cout, mode
+        self.up1x1 = mode == "upsample"
 
 
 class UNetEngine:
@@ -126,6 +130,10 @@ class UNetEngine:
         if not 2 <= self.n_classes <= 4:
             raise ValueError("n_classes must be in 2..4")
         D, sf = self.depth, self.sf
+        self.up_mode = getattr(module, "up_mode", "transpose")
+        if self.up_mode == "upsample" and self.bwd16:
+            raise NotImplementedError("precision 'h3f' with up_mode='upsample' (its fp16 backward pass exists for the "
+                                      "transposed convolutions only); precision 'h3p' covers it")
         self.enc, self.dec, self.ups = [], [], []
         for i in range(D):
             c = sf * 2 ** i
@@ -137,7 +145,7 @@ class UNetEngine:
             cprev = sf * 2 ** (D - 1 - j)
             c = cprev // 2
             p = f"up_convs.{j}."
-            self.ups.append(_UpConv(p + "upconv", cprev, c))
+            self.ups.append(_UpConv(p + ("upconv.1" if self.up_mode == "upsample" else "upconv"), cprev, c, self.up_mode))
             self.dec.append((_ConvBlock(p + "conv1", p + "bn1", 2 * c, c),
                              _ConvBlock(p + "conv2", p + "bn2", c, c)))
         # UNet_LateMetInject (unet.py:346-391): per-pixel perceptron on the metadata planes, its output concatenated
@@ -274,6 +282,15 @@ class UNetEngine:
                 "fwd_frag": self.pk[b.conv_key]["fwd_frag"], "fwd_rows": fr,
             }
         for u in self.ups:
+            if u.up1x1:
+                # conv1x1 planes (crimac_pack_layers kind 2): the low planes are separate buffers in every mode (h3p: the
+                # F32H3 split, csrc/upsample.hip)
+                n, n_lo = u.cin * u.cout, max(self.planes - 1, 1)
+                self.pk[u.key] = {"fwd_hi": torch.empty(n, dtype=i16, device=dev),
+                                  "fwd_lo": torch.empty(n_lo * n, dtype=i16, device=dev),
+                                  "dg_hi": torch.empty(n, dtype=i16, device=dev),
+                                  "dg_lo": torch.empty(n_lo * n, dtype=i16, device=dev)}
+                continue
             n = 4 * u.cin * u.cout
             n_lo = max(self.planes - 1, 1)
             self.pk[u.key] = {"fwd_hi": torch.empty(m_hi * n, dtype=i16, device=dev),
@@ -369,6 +386,9 @@ class UNetEngine:
         def add(key, mode, cf, cs, n, h, w):
             nonlocal tot
             sp = 1
+            if self.use_wgrad_partials and mode is None:
+                raise NotImplementedError("CRIMAC_WGRAD_PARTIALS (reproducible weight-gradient slabs): the conv1x1 layers of "
+                                          "up_mode='upsample' have no slab form (crimac_conv1x1_wgrad accumulates atomically)")
             if self.use_wgrad_partials:
                 sp = lib.crimac_wgrad_splits(self.prec_bwd, mode, cf, cs, B, h, w, self.wgrad_target_blocks)
                 if sp < 1:
@@ -388,7 +408,10 @@ class UNetEngine:
                 add(b.conv_key, 0, b.cout, b.cin_pad, 9 * b.cout * b.cin_pad, h, w)
             u = self.ups[j]
             hp, wp, _ = geo[L + 1]
-            add(u.key, 1, u.cin, u.cout, 4 * u.cin * u.cout, hp, wp)
+            if u.up1x1:
+                add(u.key, None, u.cout, u.cin, u.cout * u.cin, hp, wp)
+            else:
+                add(u.key, 1, u.cin, u.cout, 4 * u.cin * u.cout, hp, wp)
         self.dw_off = off
         self.dw_packed = torch.zeros(tot, dtype=torch.float32, device=self.device)
         self.dw_plan = (B, H, W, self.use_wgrad_partials)
@@ -444,7 +467,8 @@ class UNetEngine:
             d.fwd_hi, d.fwd_lo = pk["fwd_hi"].data_ptr(), pk["fwd_lo"].data_ptr()
             d.dg_hi = pk["dg_hi"].data_ptr() if pk["dg_hi"] is not None else None
             d.dg_lo = pk["dg_lo"].data_ptr() if pk["dg_lo"] is not None else None
-            d.kind, d.Co, d.Ci, d.Ci_pad = (1 if up else 0), l.cout, l.cin, cin_pad
+            kind = (hip.LAYER_CONV1X1 if l.up1x1 else hip.LAYER_UPCONV2X2) if up else hip.LAYER_CONV3X3
+            d.kind, d.Co, d.Ci, d.Ci_pad = kind, l.cout, l.cin, cin_pad
             if not up:
                 d.kind |= (hip.LAYER_FWD_FRAG if pk.get("fwd_frag") else 0) | (hip.LAYER_DG_FRAG if pk.get("dg_frag") else 0)
         bounds, pos = [], 0
@@ -674,6 +698,11 @@ class UNetEngine:
             on_ready(*rng)
 
     def _pack_ups(self):
+        if self.up_mode == "upsample":                # (the conv1x1 layers' entries of the layer table, one launch)
+            arr, _ = self._layer_table()
+            sub = (hip.LayerDesc * len(self.ups))(*[d for d in arr if (d.kind & 3) == hip.LAYER_CONV1X1])
+            call("crimac_pack_layers", C.byref(sub), len(sub), self._fwd_planes_arg())
+            return
         for u in self.ups:
             pk = self.pk[u.key]
             call("crimac_pack_upconv2x2", ptr(self.P[u.key + ".weight"]), u.cin, u.cout, self.planes_arg,
@@ -827,8 +856,19 @@ class UNetEngine:
         return (y.p, y.ld, ptr(self._bnf(blk, 0)), self.cmax, ptr(self._stat(blk, 0)), ptr(self._stat(blk, 1)),
                 self._nrep(blk.cout))
 
+    def _up1x1_work(self, u, M):
+        """Coarse-grid scratch of a conv1x1 up-sampling layer: z in the forward pass, dz in the backward pass (fp32
+        elements; h3p's forward also keeps the fp32 copy of its plane-pair input there)."""
+        return self._buf(f"up1.{u.key}", (M * (u.cout + (u.cin if self.is_hp else 0)),), torch.float32)
+
     def _upconv_fwd(self, x: Act, u, out: Act, B, H, W):
         pk = self.pk[u.key]
+        if u.up1x1:
+            # bilinear 2x + conv1x1 = 2x of the conv1x1 on the coarse grid (csrc/upsample.hip)
+            call("crimac_conv1x1_up2x", self.prec, x.p, x.ld, B, H, W, u.cin, u.cout, ptr(pk["fwd_hi"]),
+                 ptr(pk["fwd_lo"]), ptr(self.P[u.key + ".bias"]), ptr(self._up1x1_work(u, B * H * W)), out.p, out.ld,
+                 flops=2.0 * u.cin * u.cout * B * H * W, mfmas=hip.MFMAS_PER_PRODUCT[self.prec])
+            return
         call("crimac_igemm_conv", self.prec, x.p, x.ld, B, H, W, H, W, u.cin, 4 * u.cout, 1, 1, 0, 1,
              ptr(pk["fwd_hi"]), ptr(pk["fwd_lo"]), ptr(self.P[u.key + ".bias"]), u.cout, out.p, out.ld,
              hip.EPI_OUT_PLANES if self.is_hp else 0, 1, u.cout, flops=2.0 * 4 * u.cin * u.cout * B * H * W,
@@ -838,7 +878,14 @@ class UNetEngine:
         """dy on the fine grid [B,2H,2W,cout] -> dx on the coarse grid [B,H,W,cin].
 
         next_bn=(block, y): dx is the ``da`` of that BatchNorm block -> take its backward sums in the epilogue
-        (bf16 kernel shapes only).  Returns whether they were taken."""
+        (bf16 kernel shapes only).  Returns whether they were taken.
+        (up_mode 'upsample': dy is dz on the COARSE grid, _up1x1_adjoint; the BatchNorm sums are left to the block)"""
+        if u.up1x1:
+            pk = self.pk[u.key]
+            call("crimac_conv1x1_dgrad", self.prec_bwd, dy.p, dy.ld, B, H, W, u.cout, u.cin, ptr(pk["dg_hi"]),
+                 ptr(pk["dg_lo"]), out.p, out.ld, flops=2.0 * u.cin * u.cout * B * H * W,
+                 mfmas=hip.MFMAS_PER_PRODUCT[hip.PREC_F32H3 if self.is_hp else self.prec_bwd])
+            return False
         pk = self._pk_bwd(u.key)
         hp_in = self.is_hp and not self.bwd16          # (dy is a plane-pair tensor: 8 bytes per element of halves)
         prec = self.prec_bwd if self.bwd16 else self.prec
@@ -855,6 +902,22 @@ class UNetEngine:
                                       f"(Cout={u.cout} % 64, Cin={u.cin} % 128); precision 'h3p' covers it")
         self._upconv_dgrad_plain(dy, u, out, B, H, W)
         return False
+
+    def _up1x1_adjoint(self, dy: Act, u, B, H, W):
+        """dz [B*H*W, cout] (coarse grid) = adjoint of the bilinear 2x applied to dy (fine grid; the up half of
+        d(concat)), in the engine's activation type (h3p: fp32, loss-scaled) -- held in the layer's forward scratch."""
+        M = B * H * W
+        dz = Act(self._up1x1_work(u, M).view(self.act_dtype)[:M * u.cout].view(M, u.cout), u.cout)
+        call("crimac_up2x_adjoint", self.prec_bwd, dy.p, dy.ld, B, H, W, u.cout, dz.p, dz.ld, flops=0.0)
+        return dz
+
+    def _wgrad1x1(self, dz: Act, x: Act, u, M):
+        """dW[cout][cin] += dz^T x on the coarse grid (crimac_conv1x1_wgrad), on the weight-gradient side stream."""
+        if self._skip_wgrad in ("all", "single"):
+            return
+        dwt, _, _ = self._dw(u.key)
+        args = (self.prec_bwd, dz.p, dz.ld, u.cout, x.p, x.ld, u.cin, M, ptr(dwt))
+        self._on_side(lambda: call("crimac_conv1x1_wgrad", *args, flops=2.0 * u.cin * u.cout * M, mfmas=1))
 
     def _upconv_dgrad_plain(self, dy: Act, u, out: Act, B, H, W):
         pk = self.pk[u.key]
@@ -1416,8 +1479,13 @@ class UNetEngine:
             dup = self._dup16.get(j) or dcat.slice(0, c)
             skip_grad[L] = dcat.slice(c, c)
             hp, wp, Mp = geo[L + 1]
-            self._wgrad(self.prec_bwd, 1, x_prev.p, x_prev.ld, u.cin, dup.p, dup.ld, u.cout, B, hp, wp, u.key,
-                        flops=2.0 * 4 * u.cin * u.cout * B * hp * wp)
+            if u.up1x1:
+                # up_mode 'upsample': dz = up2x^T(d(up half)) on the coarse grid feeds both contractions of the conv1x1
+                dup = self._up1x1_adjoint(dup, u, B, hp, wp)
+                self._wgrad1x1(dup, x_prev, u, Mp)
+            else:
+                self._wgrad(self.prec_bwd, 1, x_prev.p, x_prev.ld, u.cin, dup.p, dup.ld, u.cout, B, hp, wp, u.key,
+                            flops=2.0 * 4 * u.cin * u.cout * B * hp * wp)
             d_prev = Act(self._buf(f"g.d{j}.xprev", (Mp, u.cin)), u.cin)
             # d_prev is the `da` of the next coarser block (decoder j-1, or the bottleneck encoder block)
             nxt = (self.dec[j - 1][1], s[f"d{j - 1}"][4]) if j > 0 else (self.enc[D - 1][1], s[f"e{D - 1}"][3])

@@ -21,10 +21,11 @@ import torch
 LABEL_IGNORE_VAL = -100  # crimac_unet/constants.py:25
 
 
-def unet_state_shapes(n_classes=3, in_channels=4, depth=5, start_filts=64, meta_in_channels=0):
+def unet_state_shapes(n_classes=3, in_channels=4, depth=5, start_filts=64, meta_in_channels=0, up_mode="transpose"):
     """Key -> shape of ``UNet_Baseline.state_dict()`` (crimac_unet/models/unet.py:200-289).
 
     Key order follows module registration order in the reference: down_convs, up_convs, conv_final.
+    ``up_mode="upsample"``: the decoder's ``upconv`` is Upsample + conv1x1 (unet.py:50-56), keys ``upconv.1.*``.
     """
     shapes = OrderedDict()
 
@@ -50,8 +51,12 @@ def unet_state_shapes(n_classes=3, in_channels=4, depth=5, start_filts=64, meta_
         ins = outs
         outs = ins // 2
         p = f"up_convs.{i}."
-        shapes[p + "upconv.weight"] = (ins, outs, 2, 2)
-        shapes[p + "upconv.bias"] = (outs,)
+        if up_mode == "transpose":
+            shapes[p + "upconv.weight"] = (ins, outs, 2, 2)
+            shapes[p + "upconv.bias"] = (outs,)
+        else:
+            shapes[p + "upconv.1.weight"] = (outs, ins, 1, 1)
+            shapes[p + "upconv.1.bias"] = (outs,)
         shapes[p + "conv1.weight"] = (outs, 2 * outs, 3, 3)
         shapes[p + "conv1.bias"] = (outs,)
         shapes[p + "conv2.weight"] = (outs, outs, 3, 3)
@@ -106,7 +111,7 @@ def synth_tensor(key: str, shape, seed: int = 0) -> np.ndarray:
     if leaf == "weight":
         if len(shape) == 2:  # nn.Linear [out, in] (metadata perceptron)
             fan_in = shape[1]
-        elif "upconv" in key:  # ConvTranspose2d weight [Cin, Cout, 2, 2]: torch fan_in = Cout*k*k
+        elif "upconv" in key:  # ConvTranspose2d weight [Cin, Cout, 2, 2]: torch fan_in = Cout*k*k (conv1x1: Cin)
             fan_in = shape[1] * shape[2] * shape[3]
         else:
             fan_in = shape[1] * shape[2] * shape[3]
@@ -119,11 +124,12 @@ def synth_tensor(key: str, shape, seed: int = 0) -> np.ndarray:
     raise KeyError(key)
 
 
-def synth_state_dict(n_classes=3, in_channels=4, depth=5, start_filts=64, seed=0, meta_in_channels=0):
+def synth_state_dict(n_classes=3, in_channels=4, depth=5, start_filts=64, seed=0, meta_in_channels=0,
+                     up_mode="transpose"):
     """Full deterministic ``state_dict`` (torch CPU tensors) for ``UNet_Baseline`` (``meta_in_channels`` > 0:
-    for ``UNet_LateMetInject``)."""
+    for ``UNet_LateMetInject``; ``up_mode="upsample"``: its up-sampling decoder)."""
     sd = OrderedDict()
-    for k, shp in unet_state_shapes(n_classes, in_channels, depth, start_filts, meta_in_channels).items():
+    for k, shp in unet_state_shapes(n_classes, in_channels, depth, start_filts, meta_in_channels, up_mode).items():
         sd[k] = torch.from_numpy(np.ascontiguousarray(synth_tensor(k, shp, seed)))
     return sd
 

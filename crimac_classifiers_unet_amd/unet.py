@@ -33,11 +33,17 @@ class _EncoderStage(nn.Module):
 
 
 class _DecoderStage(nn.Module):
-    """Parameter container with the reference's key names upconv/conv1/conv2/bn1/bn2 (unet.py:112-122)."""
+    """Parameter container with the reference's key names upconv/conv1/conv2/bn1/bn2 (unet.py:112-122).
 
-    def __init__(self, cin, cout):
+    up_mode 'upsample' (unet.py:50-56): ``upconv`` is Sequential(Upsample(bilinear, x2), Conv2d(cin, cout, 1)) -- keys
+    ``upconv.1.weight`` / ``upconv.1.bias``, registered in the reference's order (same seeded initialisation)."""
+
+    def __init__(self, cin, cout, up_mode="transpose"):
         super().__init__()
-        self.upconv = nn.ConvTranspose2d(cin, cout, kernel_size=2, stride=2)
+        if up_mode == "transpose":
+            self.upconv = nn.ConvTranspose2d(cin, cout, kernel_size=2, stride=2)
+        else:
+            self.upconv = nn.Sequential(nn.Upsample(mode="bilinear", scale_factor=2), nn.Conv2d(cin, cout, kernel_size=1))
         self.conv1 = nn.Conv2d(2 * cout, cout, 3, padding=1)
         self.conv2 = nn.Conv2d(cout, cout, 3, padding=1)
         self.bn1 = nn.BatchNorm2d(cout)
@@ -150,10 +156,10 @@ class UNet_Baseline(nn.Module):
         if merge_mode not in ("concat", "add"):
             raise ValueError('"{}" is not a valid mode for merging up and down paths. Only "concat" '
                              'and "add" are allowed.'.format(merge_mode))
-        if up_mode != "transpose" or merge_mode != "concat":
-            # the reference pipeline always passes transpose/concat (pipeline.py:396-397)
-            raise NotImplementedError("the MI355X hot path implements up_mode='transpose', "
-                                      "merge_mode='concat' (the only combination the pipeline uses)")
+        if merge_mode != "concat":
+            # the reference pipeline always passes concat (pipeline.py:396-397)
+            raise NotImplementedError("the MI355X hot path implements merge_mode='concat' (with up_mode 'transpose' -- "
+                                      "what the pipeline uses -- or 'upsample')")
         if late_meta_inject and type(self) is UNet_Baseline:
             raise ValueError("late_meta_inject=True is the UNet_LateMetInject model (pipeline.py:400-410)")
         self.late_meta_inject = bool(late_meta_inject)
@@ -169,7 +175,7 @@ class UNet_Baseline(nn.Module):
         dec = []
         for _ in range(depth - 1):
             ins, outs = outs, outs // 2
-            dec.append(_DecoderStage(ins, outs))
+            dec.append(_DecoderStage(ins, outs, up_mode))
         self.down_convs = nn.Sequential(*enc)
         self.up_convs = nn.Sequential(*dec)
         if not self.late_meta_inject:

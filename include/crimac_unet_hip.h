@@ -132,7 +132,7 @@ extern "C" {
  * binding must refuse a library whose version differs from the header it was written against (an older build that
  * happens to export every symbol would walk a descriptor array with the wrong stride).  crimac_layer_desc_size() is
  * sizeof(crimac_layer_desc) as the library was compiled. */
-#define CRIMAC_ABI_VERSION 6
+#define CRIMAC_ABI_VERSION 7
 int crimac_version(void);
 int crimac_layer_desc_size(void);
 const char* crimac_last_error(void);
@@ -258,6 +258,30 @@ int crimac_wgrad_splits(int prec, int mode, int CF, int CS, int B, int Hf, int W
 int crimac_wgrad_partials(int prec, int mode, const void* f, long f_ld, int CF, const void* s, long s_ld, int CS,
                           int B, int Hf, int Wf, float* partials, long slab_stride, int target_blocks, void* stream);
 
+/* ---- up_mode="upsample" decoder stage: nn.Upsample(bilinear, x2, align_corners=False) + conv1x1 (unet.py:47-56) ----
+ * Bilinear 2x and a 1x1 convolution with bias commute (every fine pixel is a convex combination of coarse pixels), so the
+ * contractions run on the COARSE grid [B][H][W] and only the Cout-channel result is interpolated (csrc/upsample.hip).
+ * Weight planes: crimac_pack_layers kind 2.  Cin % 64 == 0, Cout % 64 == 0, strides multiples of 8.  Storage per `prec`:
+ * the 16-bit modes read and write their 16-bit type, the fp32 modes fp32; CRIMAC_PREC_H3P reads plane-pair activations
+ * (x) and output gradients (dy), writes plane pairs (out) and keeps z / dz in fp32.
+ *   crimac_conv1x1_up2x: out[B][2H][2W] (out_ld; e.g. the up half of a concat buffer) = up2x(W x + bias); x [B][H][W]
+ *     (x_ld).  `work`: scratch of B*H*W*Cout floats (H3P: B*H*W*(Cout + Cin) floats), free again when the call's work
+ *     has run.  Train and eval mode alike (no BatchNorm behind this layer). */
+int crimac_conv1x1_up2x(int prec, const void* x, long x_ld, int B, int H, int W, int Cin, int Cout, const void* w_hi,
+                        const void* w_lo, const float* bias, void* work, void* out, long out_ld, void* stream);
+/*   crimac_up2x_adjoint: dz [B][H][W] (dz_ld) = up2x^T(dy), dy [B][2H][2W] (dy_ld), fp32 accumulation.  dz is stored in
+ *     the mode's 16-bit type (16-bit modes) or fp32 (every other mode, H3P included: loss-scaled fp32). */
+int crimac_up2x_adjoint(int prec, const void* dy, long dy_ld, int B, int H, int W, int C, void* dz, long dz_ld,
+                        void* stream);
+/*   crimac_conv1x1_dgrad: dx [B][H][W][Cin] (dx_ld) = W^T dz with the input-gradient planes (crimac_igemm_conv, 1 tap;
+ *     H3P: the F32H3 split of the fp32 dz, fp32 dx).  Backward precisions: not F32H3 (its backward pass is F32X3). */
+int crimac_conv1x1_dgrad(int prec, const void* dz, long dz_ld, int B, int H, int W, int Cout, int Cin, const void* w_dg_hi,
+                         const void* w_dg_lo, void* dx, long dx_ld, void* stream);
+/*   crimac_conv1x1_wgrad: dw[Cout][Cin] += sum over the M pixels of dz[p][co] * x[p][ci] (fp32 products and accumulation,
+ *     fp32 atomics: the caller zeroes dw; no slab form -- crimac_wgrad_partials has no counterpart here). */
+int crimac_conv1x1_wgrad(int prec, const void* dz, long dz_ld, int Cout, const void* x, long x_ld, int Cin, long M,
+                         float* dw, void* stream);
+
 
 /* ---- weight layout (fp32 master weights <-> bf16 MFMA operand planes) ------------------------ */
 
@@ -278,14 +302,18 @@ int crimac_unpack_wgrad_upconv2x2(const float* dw, int Ci, int Co, float* grad, 
  * step, optim.SGD.step pipeline.py:178, so the planes are rebuilt every step).  `descs` is a HOST array;
  * it is read during the call only.  Co % 32 == 0; kind 1 also needs Ci % 32 == 0. */
 typedef struct crimac_layer_desc {
-  const float* w;      /* fp32 weights: kind 0 [Co][Ci][3][3], kind 1 [Ci][Co][2][2] (device) */
+  const float* w;      /* fp32 weights: kind 0 [Co][Ci][3][3], kind 1 [Ci][Co][2][2], kind 2 [Co][Ci][1][1] (device) */
   float* grad;         /* crimac_unpack_wgrad_layers: gradient, laid out as w (device) */
   const float* dw;     /* crimac_unpack_wgrad_layers: packed gradient written by crimac_wgrad (device) */
   void* fwd_hi;        /* crimac_pack_layers: planes as in crimac_pack_conv3x3 / crimac_pack_upconv2x2 */
   void* fwd_lo;
   void* dg_hi;         /* may be NULL (no input gradient needed: first layer) */
   void* dg_lo;
-  int kind;            /* bit 0 -- 0: Conv2d 3x3, 1: ConvTranspose2d 2x2 stride 2; kind 0, 16-bit single-plane or interleaved-pair packs:
+  int kind;            /* bits 0-1 -- 0: Conv2d 3x3, 1: ConvTranspose2d 2x2 stride 2, 2: Conv2d 1x1 (the conv of an up_mode="upsample"
+                        * decoder stage: forward planes [Co][Ci], input-gradient planes [Ci][Co], packed gradient [Co][Ci]; with
+                        * an interleaved `planes` argument (CRIMAC_PLANES_H3P) the two planes go to *_hi / *_lo separately, as
+                        * for F32H3 -- the plane-pair mode runs these contractions on that split, crimac_conv1x1_up2x);
+                        * kind 0, 16-bit single-plane or interleaved-pair packs:
                         * | CRIMAC_LAYER_FWD_FRAG: fwd_hi is written FRAGMENT-MAJOR (CRIMAC_EPI_WFRAG; Co % 32 == 0, Ci_pad % 64 == 0),
                         * | CRIMAC_LAYER_DG_FRAG: dg_hi likewise (rows = Ci, columns = Co: Ci % 32 == 0, Co % 64 == 0) */
   int Co, Ci, Ci_pad;  /* Ci_pad: kind 0 only */
