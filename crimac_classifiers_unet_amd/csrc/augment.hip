@@ -36,7 +36,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void augment_db_kernel(
     const float* __restrict__ data, const void* __restrict__ labels_in, int label_bytes,
     T* __restrict__ out, short* __restrict__ labels_out, unsigned char* __restrict__ aux, int thr_channel,
-    float thr_lo, float thr_hi, int B, int C, int H, int W, int ld,
+    float thr_lo, float thr_hi, int B, int C, int n_data, int H, int W, int ld,
     unsigned seed_lo, unsigned seed_hi, int do_noise, int do_flip, int db_scaled, float p_apply, float p_change) {
   const long HW = (long)H * W, npix = (long)B * HW;
   for (long pix = blockIdx.x * (long)blockDim.x + threadIdx.x; pix < npix;
@@ -53,6 +53,9 @@ __global__ __launch_bounds__(256) void augment_db_kernel(
     bool nonfinite0 = false, thr_hit = false;
     for (int c = 0; c < C; ++c) {
       float d = data[((long)b * C + c) * HW + hw];
+      // channels >= n_data: metadata planes (early injection, add_noise_metadata / flip_x_axis_metadata,
+      // add_noise.py:42-63): no noise, no NaN rule, no dB -- flipped and stored as they are
+      if (c >= n_data) { v[c] = d; continue; }
       if (noisy) {
         const u4 r = philox4x32_10(u4{(unsigned)(c * HW + hw), (unsigned)((c * HW + hw) >> 32), 1u, 0u},
                                    seed_lo ^ (unsigned)b, seed_hi);
@@ -120,17 +123,18 @@ extern "C" int crimac_augment_flip_planes(const float* in, float* out, int B, in
   return CRIMAC_OK;
 }
 
-extern "C" int crimac_augment_db_nhwc(int prec, const float* data, const void* labels_in, int label_bytes,
-                                      void* out, short* labels_out, unsigned char* aux_mask, int thr_channel,
-                                      float thr_lo, float thr_hi, int B, int C, int H, int W, long ld,
-                                      unsigned long long seed, int do_noise, int do_flip, int db_scaled, void* stream) {
+static int augment_run(int prec, const float* data, const void* labels_in, int label_bytes, void* out,
+                       short* labels_out, unsigned char* aux_mask, int thr_channel, float thr_lo, float thr_hi, int B,
+                       int C, int n_data, int H, int W, long ld, unsigned long long seed, int do_noise, int do_flip,
+                       int db_scaled, void* stream) {
   CRIMAC_REQUIRE(prec >= CRIMAC_PREC_BF16 && prec <= CRIMAC_PREC_MAX, "augment_db_nhwc: bad precision %d", prec);
   CRIMAC_REQUIRE(data && out && B > 0 && C > 0 && C <= 16 && H > 0 && W > 0 && ld >= C && ld <= 16 && ld % 8 == 0,
                  "augment_db_nhwc: bad arguments (C=%d ld=%ld)", C, ld);
+  CRIMAC_REQUIRE(n_data >= 1 && n_data <= C, "augment_db_nhwc: n_data=%d must be in 1..C=%d", n_data, C);
   CRIMAC_REQUIRE(!labels_in || label_bytes == 2 || label_bytes == 4 || label_bytes == 8,
                  "augment_db_nhwc: label_bytes=%d", label_bytes);
-  CRIMAC_REQUIRE(!aux_mask || (thr_channel >= 0 && thr_channel < C), "augment_db_nhwc: bad threshold channel %d",
-                 thr_channel);
+  CRIMAC_REQUIRE(!aux_mask || (thr_channel >= 0 && thr_channel < n_data),
+                 "augment_db_nhwc: bad threshold channel %d (data channels: %d)", thr_channel, n_data);
   if (!aux_mask) thr_channel = -1;
   const long npix = (long)B * H * W;
   long blocks = (npix + 255) / 256;
@@ -139,8 +143,25 @@ extern "C" int crimac_augment_db_nhwc(int prec, const float* data, const void* l
   hipStream_t st = (hipStream_t)stream;
   CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(augment_db_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, data,
                                                  labels_in, label_bytes, (T*)out, labels_out, aux_mask, thr_channel,
-                                                 thr_lo, thr_hi, B, C, H, W, (int)ld, lo, hi, do_noise, do_flip, db_scaled, 0.5f,
-                                                 0.05f));
+                                                 thr_lo, thr_hi, B, C, n_data, H, W, (int)ld, lo, hi, do_noise, do_flip,
+                                                 db_scaled, 0.5f, 0.05f));
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
+}
+
+extern "C" int crimac_augment_db_nhwc(int prec, const float* data, const void* labels_in, int label_bytes,
+                                      void* out, short* labels_out, unsigned char* aux_mask, int thr_channel,
+                                      float thr_lo, float thr_hi, int B, int C, int H, int W, long ld,
+                                      unsigned long long seed, int do_noise, int do_flip, int db_scaled, void* stream) {
+  return augment_run(prec, data, labels_in, label_bytes, out, labels_out, aux_mask, thr_channel, thr_lo, thr_hi, B, C, C,
+                     H, W, ld, seed, do_noise, do_flip, db_scaled, stream);
+}
+
+extern "C" int crimac_augment_db_meta_nhwc(int prec, const float* data, const void* labels_in, int label_bytes,
+                                           void* out, short* labels_out, unsigned char* aux_mask, int thr_channel,
+                                           float thr_lo, float thr_hi, int B, int C, int H, int W, long ld,
+                                           unsigned long long seed, int do_noise, int do_flip, int db_scaled,
+                                           int n_data, void* stream) {
+  return augment_run(prec, data, labels_in, label_bytes, out, labels_out, aux_mask, thr_channel, thr_lo, thr_hi, B, C,
+                     n_data, H, W, ld, seed, do_noise, do_flip, db_scaled, stream);
 }

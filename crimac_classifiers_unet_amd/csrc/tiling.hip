@@ -16,6 +16,7 @@
 // (along ping, 16 channels per pixel) are coalesced, and the dB transform, channel padding and
 // bf16/fp32 conversion are fused into it -- the patch lands directly in the first conv's input layout.
 #include "common.h"
+#include "meta_planes.h"
 
 namespace {
 
@@ -26,11 +27,17 @@ constexpr int TS = 32;   // tile side
 // same extent as `data`; a pixel outside that extent, or whose raw label the test-time label transform maps to
 // "ignore" (convert_label_indexing: negative ids), gets 0.0 AFTER the dB transform in every channel
 // (set_data_border_value, batch/data_transforms/set_data_border_value.py:20-23, last step of define_data_transform_test).
+// meta.flags != 0 (early metadata injection, crimac_gather_patches_memm_meta): channels C .. C+Cm-1 of every pixel get
+// the crop's metadata planes (meta_plane_values, crop centred on meta_centres[p] = (range idx, GLOBAL ping idx)), which
+// neither the dB transform nor the border rule touches (batch/dataset.py:109: np.concatenate((data, meta)) after the
+// data transform); db_scaled: db_with_limits_scaled (1 + dB / 75, define_data_transform_test(use_metadata=True)).
 template <typename T>
 __global__ __launch_bounds__(256) void gather_patches_kernel(const float* __restrict__ data, int C, int Wd,
                                                              int H, const int* __restrict__ centres,
                                                              int ph, int pw, T* __restrict__ out,
-                                                             int ld, const short* __restrict__ border_labels) {
+                                                             int ld, const short* __restrict__ border_labels,
+                                                             int db_scaled, MetaPlaneSrc meta,
+                                                             const int* __restrict__ meta_centres) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float* tile = reinterpret_cast<float*>(smem_raw);      // [C][TS (x)][TS + 1 (y)]
   const int p = blockIdx.z;
@@ -60,6 +67,7 @@ __global__ __launch_bounds__(256) void gather_patches_kernel(const float* __rest
       if (!isfinite(v)) v = 0.f;                 // remove_nan_inf
       v = 10.f * log10f(v + 1e-10f);             // db_with_limits
       v = fminf(fmaxf(v, -75.f), 0.f);
+      if (db_scaled) v = 1.f + v / 75.f;         // db_with_limits_scaled (db_with_limits.py:27-33)
       if (border[k]) v = 0.f;                    // set_data_border_value
       tile[(c * TS + xi) * (TS + 1) + tx] = v;
     }
@@ -72,10 +80,19 @@ __global__ __launch_bounds__(256) void gather_patches_kernel(const float* __rest
     const int py = ty0 + yi, px = tx0 + tx;
     if (py >= ph || px >= pw) continue;
     T* dst = out + (((long)p * ph + py) * pw + px) * ld;
+    float mv[CRIMAC_MAX_META_PLANES];
+    int Cm = 0;
+    if (meta.flags) {
+      meta_plane_values(meta, meta_centres[2 * p], meta_centres[2 * p + 1], ph, pw, py, px, mv);
+      Cm = meta_plane_count(meta.flags);
+    }
     for (int c0 = 0; c0 < ld; c0 += 8) {
       float v[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (c0 + j) < C ? tile[((c0 + j) * TS + tx) * (TS + 1) + yi] : 0.f;
+      for (int j = 0; j < 8; ++j) {
+        const int ch = c0 + j;
+        v[j] = ch < C ? tile[(ch * TS + tx) * (TS + 1) + yi] : ch < C + Cm ? mv[ch - C] : 0.f;
+      }
       store8(dst + c0, v);
     }
   }
@@ -189,31 +206,51 @@ extern "C" int crimac_pr_histogram(const float* logits, int ncls, const void* la
 }
 
 static int gather_run(int prec, const float* data, int C, int Wd, int H, const int* centres, int P, int ph, int pw,
-                      void* out, long ld, const short* border_labels, void* stream) {
+                      void* out, long ld, const short* border_labels, int db_scaled, const MetaPlaneSrc& meta,
+                      const int* meta_centres, void* stream) {
   CRIMAC_REQUIRE(prec >= CRIMAC_PREC_BF16 && prec <= CRIMAC_PREC_MAX, "gather_patches: bad precision %d", prec);
   CRIMAC_REQUIRE(data && centres && out && C > 0 && C <= 16 && Wd > 0 && H > 0 && P > 0 && ph > 0 && pw > 0,
                  "gather_patches: bad arguments (C=%d must be <= 16)", C);
   CRIMAC_REQUIRE(ld >= C && ld % 8 == 0 && ld <= 16, "gather_patches: ld=%ld must be 8 or 16 and >= C", ld);
   CRIMAC_REQUIRE(P <= 65535, "gather_patches: at most 65535 patches per call");
+  CRIMAC_REQUIRE(!meta.flags || C + meta_plane_count(meta.flags) <= ld,
+                 "gather_patches: %d data + %d metadata channels do not fit ld=%ld", C, meta_plane_count(meta.flags), ld);
   dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
   const size_t lds = (size_t)C * TS * (TS + 1) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
   CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(gather_patches_kernel<T>, grid, dim3(256), lds, st, data, C, Wd, H,
-                                                 centres, ph, pw, (T*)out, (int)ld, border_labels));
+                                                 centres, ph, pw, (T*)out, (int)ld, border_labels, db_scaled, meta,
+                                                 meta_centres));
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
 }
 
 extern "C" int crimac_gather_patches(int prec, const float* data, int C, int Wd, int H, const int* centres,
                                      int P, int ph, int pw, void* out, long ld, void* stream) {
-  return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, nullptr, stream);
+  return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, nullptr, 0, MetaPlaneSrc{}, nullptr, stream);
 }
 
 extern "C" int crimac_gather_patches_memm(int prec, const float* data, int C, int Wd, int H, const int* centres,
                                           int P, int ph, int pw, void* out, long ld, const short* border_labels,
                                           void* stream) {
   CRIMAC_REQUIRE(border_labels, "gather_patches_memm: needs the label array (border rule)");
-  return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, border_labels, stream);
+  return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, border_labels, 0, MetaPlaneSrc{}, nullptr,
+                    stream);
+}
+
+extern "C" int crimac_gather_patches_memm_meta(int prec, const float* data, int C, int Wd, int H, const int* centres,
+                                               int P, int ph, int pw, void* out, long ld, const short* border_labels,
+                                               int db_scaled, int flags, double portion_year, const double* portion_day,
+                                               int n_day, const double* time_diff, int n_td, const long long* seabed,
+                                               int n_sb, const int* meta_centres, void* stream) {
+  CRIMAC_REQUIRE(border_labels, "gather_patches_memm_meta: needs the label array (border rule)");
+  CRIMAC_REQUIRE(meta_centres && flags > 0 && flags < 64, "gather_patches_memm_meta: bad metadata arguments");
+  CRIMAC_REQUIRE(!(flags & 2) || (portion_day && n_day > 0), "gather_patches_memm_meta: portion_day needs its vector");
+  CRIMAC_REQUIRE(!(flags & 4) || (time_diff && n_td > 0), "gather_patches_memm_meta: time_diff needs its vector");
+  CRIMAC_REQUIRE(!(flags & 56) || (seabed && n_sb > 0), "gather_patches_memm_meta: the depth planes need the seabed vector");
+  const MetaPlaneSrc meta{flags, portion_year, portion_day, n_day, time_diff, n_td, seabed, n_sb};
+  return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, border_labels, db_scaled ? 1 : 0, meta,
+                    meta_centres, stream);
 }
 
 extern "C" int crimac_scatter_patches_ex(const float* probs, int ncls, const int* centres, int P, int ph, int pw,

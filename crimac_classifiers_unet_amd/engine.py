@@ -1836,10 +1836,14 @@ class UNetEngine:
     # on-GPU augmentation (BASELINE configs[4]; reference: batch/data_augmentation/*)
     # ------------------------------------------------------------------------------------------
     @_on_device
-    def augment_batch(self, data_linear, labels, seed, do_noise=True, do_flip=True, refine_labels=None, db_scaled=False):
+    def augment_batch(self, data_linear, labels, seed, do_noise=True, do_flip=True, refine_labels=None, db_scaled=False,
+                      n_data=None):
         """add_noise + flip_x_axis + remove_nan_inf + db_with_limits + NCHW->NHWC in one kernel.
         ``db_scaled``: db_with_limits_scaled instead (1 + dB / 75), the data transform of the metadata configurations
         (batch/transforms.py:50-51).
+        ``n_data``: channels ``n_data..C-1`` of ``data_linear`` are metadata planes (early injection, the Dataset's
+        ``np.concatenate((data, meta))``): they take the flip of their sample and nothing else (add_noise_metadata /
+        flip_x_axis_metadata); noise, the NaN rule, the dB transform and the label facts use channels ``< n_data`` only.
 
         data_linear [B,C,H,W] fp32 LINEAR sv on the GPU, labels [B,H,W] int16/32/64 (or None).
         refine_labels=(thr_channel, thr_lo, thr_hi): ``labels`` are RAW annotation ids and the reference's
@@ -1853,6 +1857,8 @@ class UNetEngine:
         B, C, H, W = data_linear.shape
         if C != self.in_channels:
             raise ValueError(f"expected {self.in_channels} channels, got {C}")
+        if n_data is not None and not 1 <= int(n_data) <= C:
+            raise ValueError(f"n_data={n_data}: the batch has {C} channels")
         x = self._buf("x_nhwc", (B * H * W, CIN_PAD))
         lab_out = self._buf("aug.labels", (B, H, W), torch.int16)
         lab_in = None if labels is None else self._labels(labels)
@@ -1861,15 +1867,20 @@ class UNetEngine:
             if lab_in is None:
                 raise ValueError("refine_labels needs labels")
             thr_c, lo, hi = refine_labels
+            if n_data is not None and not 0 <= int(thr_c) < int(n_data):
+                raise ValueError(f"refine_labels: threshold channel {thr_c} is not one of the {n_data} data channels")
             aux = self._buf("aug.aux", (B, H, W), torch.uint8)
-        call("crimac_augment_db_nhwc", self.prec, ptr(data_linear), ptr(lab_in),
-             lab_in.element_size() if lab_in is not None else 0, ptr(x), ptr(lab_out), ptr(aux), int(thr_c),
-             float(lo), float(hi), B, C, H, W, CIN_PAD, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if do_noise else 0,
-             1 if do_flip else 0, 1 if db_scaled else 0)
+        args = (self.prec, ptr(data_linear), ptr(lab_in), lab_in.element_size() if lab_in is not None else 0, ptr(x),
+                ptr(lab_out), ptr(aux), int(thr_c), float(lo), float(hi), B, C, H, W, CIN_PAD,
+                int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if do_noise else 0, 1 if do_flip else 0, 1 if db_scaled else 0)
+        if n_data is None:
+            call("crimac_augment_db_nhwc", *args)
+        else:
+            call("crimac_augment_db_meta_nhwc", *args, int(n_data))
         if aux is not None:
             refined = self._buf("aug.labels_refined", (B, H, W), torch.int16)
             call("crimac_refine_labels", ptr(lab_out), 2, ptr(aux), None, int(thr_c), float(lo), float(hi), 1,
-                 ptr(refined), B, C, H, W)
+                 ptr(refined), B, C if n_data is None else int(n_data), H, W)
             lab_out = refined
         return x, lab_out
 
@@ -1886,12 +1897,28 @@ class UNetEngine:
 
     @_on_device
     def train_step_augmented(self, data_linear, labels, class_w, lr, momentum, seed, grad_sync=None,
-                             do_noise=True, do_flip=True, ignore_index=-100, refine_labels=None, meta=None):
+                             do_noise=True, do_flip=True, ignore_index=-100, refine_labels=None, meta=None,
+                             n_data=None):
         """Training step on RAW linear-sv crops: augmentation and dB transform (and, with ``refine_labels``,
         the label transform on raw annotation ids) run on the GPU.  ``meta`` [B,Cm,H,W] (UNet_LateMetInject): the
         reference's *_metadata augmentations (batch/transforms.py:41-42) -- noise on the data planes only, the flip on
-        data, metadata and labels alike -- and the scaled dB transform of the metadata configurations (:50-51)."""
-        B, _, H, W = data_linear.shape
+        data, metadata and labels alike -- and the scaled dB transform of the metadata configurations (:50-51).
+        ``n_data`` (early injection: a UNet_Baseline whose input channels are ``n_data`` frequencies + the metadata
+        planes): ``data_linear`` is the whole ``[B, n_data + Cm, H, W]`` batch as the Dataset concatenates it; the same
+        metadata augmentations and scaled dB transform, in one kernel over the whole batch."""
+        B, C, H, W = data_linear.shape
+        if n_data is not None:
+            if self.lmi:
+                raise ValueError("n_data belongs to early metadata injection: a UNet_LateMetInject model takes `meta`")
+            if meta is not None:
+                raise ValueError("early metadata injection takes the metadata planes inside the batch, not as `meta`")
+            if C != self.in_channels or not 1 <= int(n_data) <= C:
+                raise ValueError(f"early metadata injection: the model takes {self.in_channels} input channels, the batch "
+                                 f"has {C} channels of which {n_data} are data planes")
+            x, lab = self.augment_batch(data_linear, labels, seed, do_noise, do_flip, refine_labels, db_scaled=True,
+                                        n_data=int(n_data))
+            logits = self.forward_nhwc(x, B, H, W, training=True)
+            return self._loss_backward_update(logits, lab, class_w, lr, momentum, grad_sync, ignore_index)
         if self.lmi:
             meta = self.flip_planes(self._meta(meta, data_linear), seed, do_flip)
         elif meta is not None:

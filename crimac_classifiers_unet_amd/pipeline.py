@@ -52,7 +52,7 @@ class SegPipe:
                  save_model_params, meta_channels, late_meta_inject, eval_mode, experiment_name,
                  precision="bf16", infer_precision="h3p", loss_flush=50, gpu_augment=False, random_seed=0,
                  gpu_metrics=False, gpu_label_transform=False, sync_bn=False, pin_batches=True,
-                 release_batch_pages=True, collate_float32=True, **kwargs):
+                 release_batch_pages=True, collate_float32=True, gpu_meta_input=False, **kwargs):
         assert not (save_model_params and (checkpoint_dir is None))
         self.model = None
         self.model_is_loaded = False
@@ -114,10 +114,20 @@ class SegPipe:
         self.gpu_label_transform = bool(gpu_label_transform)
         if self.gpu_label_transform and not self.gpu_augment:
             raise ValueError("gpu_label_transform needs gpu_augment (the transform runs on the augmented crop)")
-        if self.gpu_augment and self.use_metadata and not self.late_meta_inject:
+        # gpu_meta_input (with gpu_augment): opt-in for metadata planes as extra INPUT channels (late_meta_inject=False,
+        # the reference's default): the train Dataset's raw batch [data | metadata planes] goes to the GPU whole, and the
+        # augmentation + scaled dB transform treat channels >= len(frequencies) as metadata (noise, NaN rule and dB on the
+        # frequency planes only, the flip on everything: add_noise_metadata / flip_x_axis_metadata, transforms.py:41-42)
+        self.gpu_meta_input = bool(gpu_meta_input)
+        if self.gpu_meta_input and not self.gpu_augment:
+            raise ValueError("gpu_meta_input needs gpu_augment (it tells the on-GPU augmentation which channels are "
+                             "metadata planes)")
+        self.early_meta = self.use_metadata and not self.late_meta_inject
+        if self.gpu_augment and self.early_meta and not self.gpu_meta_input:
             raise NotImplementedError("gpu_augment with metadata planes as extra INPUT channels (late_meta_inject=False): the "
-                                      "on-GPU data transform would take them for sv; use late_meta_inject=True or the host "
-                                      "transforms")
+                                      "on-GPU data transform would take them for sv; set gpu_meta_input: True (the batch "
+                                      "is raw frequency planes followed by metadata planes), use late_meta_inject=True or "
+                                      "the host transforms")
         self.random_seed = int(random_seed)
         # gpu_metrics: in-training validation builds the PR curve / F1 from GPU histograms instead of
         # shipping every pixel's probability to sklearn (same numbers; the logger gets no pr_curve)
@@ -223,8 +233,9 @@ class SegPipe:
                 nf = len(self.frequencies)
                 inputs_train, meta_train = inputs_train[:, :nf], inputs_train[:, nf:]
             if self.gpu_augment:
-                if i == 0 and bool((inputs_train < 0).any()):
-                    # (one device -> host sync, first batch only) linear sv is non-negative; dB data is not
+                if i == 0 and bool((inputs_train[:, :len(self.frequencies)] < 0).any()):
+                    # (one device -> host sync, first batch only) linear sv is non-negative; dB data is not (the
+                    # frequency planes only: metadata planes may be negative)
                     raise ValueError("gpu_augment=True, but the training Dataset yields negative values: it still applies "
                                      "its own data transform (db_with_limits).  Build it with augmentation_function=None, "
                                      "data_transform_function=None (and label_transform_function=None with "
@@ -232,11 +243,12 @@ class SegPipe:
                 rank = parallel.env_world()[1]
                 # (late metadata injection: add_noise_metadata / flip_x_axis_metadata, batch/transforms.py:41-42 -- the
                 # metadata planes take the flip, and the data transform is db_with_limits_scaled, :50-51)
+                # (early injection, gpu_meta_input: the whole batch, channels >= len(frequencies) are metadata planes)
                 loss = engine.train_step_augmented(
                     inputs_train, labels_train, criterion.weight, optimizer.param_groups[0]["lr"],
                     self.momentum, seed=(self.random_seed << 40) ^ (rank << 32) ^ i, grad_sync=grad_sync,
                     refine_labels=(len(self.frequencies) - 1, 1e-7, 1e-4) if self.gpu_label_transform else None,
-                    meta=meta_train)
+                    meta=meta_train, n_data=len(self.frequencies) if self.early_meta else None)
             else:
                 loss = engine.train_step(inputs_train, labels_train, criterion.weight,
                                          optimizer.param_groups[0]["lr"], self.momentum,
@@ -304,9 +316,6 @@ class SegPipe:
         if getattr(reader, "data_format", "zarr") != "zarr":
             raise NotImplementedError("use_gpu_test_transform: zarr readers only (the memmap flow's set_data_border_value "
                                       "lives in the tiled path, tiled_inference.predict_echogram_memm)")
-        if self.use_metadata and not self.late_meta_inject:
-            raise NotImplementedError("use_gpu_test_transform with metadata planes as extra input channels "
-                                      "(late_meta_inject=False)")
         n_pings, n_range = (int(v) for v in reader.shape)
         boxes = None
         if self.eval_mode in ("region", "trace"):
@@ -374,9 +383,13 @@ class SegPipe:
         if data.dtype != torch.float32:
             data = data.float()
         meta = None
+        nf = len(self.frequencies)
+        batch_in = None
         if self.late_meta_inject:                # pipeline.py:210-216: data planes | metadata planes
-            nf = len(self.frequencies)
             data, meta = data[:, :nf], data[:, nf:].contiguous()
+        elif self.early_meta:                    # metadata planes as extra input channels: the data transform takes the
+            batch_in = data.contiguous()         # whole batch, the label transform the frequency planes
+            data = data[:, :nf]
         data = data.contiguous()
         labels = batch["labels"].to(dev)
         if labels.dtype not in (torch.int16, torch.int32, torch.int64):
@@ -397,7 +410,10 @@ class SegPipe:
                 call("crimac_labels_extend_mask", ptr(out), ptr(data), C, ptr(cen), ptr(src["boxes"]),
                      int(src["boxes"].shape[0]), -1, B, H, W)
             # remove_nan_inf + db_with_limits (db_with_limits_scaled with metadata channels)
-            x, _ = eng.augment_batch(data, None, 0, do_noise=False, do_flip=False, db_scaled=self.use_metadata)
+            if batch_in is not None:
+                x, _ = eng.augment_batch(batch_in, None, 0, do_noise=False, do_flip=False, db_scaled=True, n_data=nf)
+            else:
+                x, _ = eng.augment_batch(data, None, 0, do_noise=False, do_flip=False, db_scaled=self.use_metadata)
             logits = eng.forward_nhwc(x, B, H, W, training=False, meta=meta)
         return logits, out
 

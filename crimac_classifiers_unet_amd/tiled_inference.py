@@ -111,7 +111,9 @@ class ChunkPredictor:
         self.out_f16 = bool(out_f16)
         self.flavour = "zarr"
         self.seabed = self.mask = None
-        self.meta_source = None          # MetaSource: needed by a UNet_LateMetInject model (metadata planes per crop)
+        # MetaSource: needed by a UNet_LateMetInject model (metadata planes per crop) and by an early-injection model
+        # (UNet_Baseline whose input channels are the data planes + the metadata planes, gathered into the same crop)
+        self.meta_source = None
 
     def _device(self):
         return self.engine.device or next(self.model.parameters()).device
@@ -169,6 +171,19 @@ class ChunkPredictor:
             world, rank = torch.distributed.get_world_size(), torch.distributed.get_rank()
         mine = parallel.shard_indices(len(grid), rank, world)
         memm = self.flavour == "memm"
+        early = not eng.lmi and eng.in_channels > C       # metadata planes as extra input channels
+        ms = self.meta_source
+        if early:
+            if ms is None:
+                raise ValueError(f"the model takes {eng.in_channels} input channels and the chunk has {C} data planes: "
+                                 "an early-injection model needs the metadata planes, set ChunkPredictor.meta_source "
+                                 "(MetaSource.from_echogram(...))")
+            if ms.n_planes != eng.in_channels - C:
+                raise ValueError(f"the model takes {eng.in_channels - C} metadata input channels, meta_source builds "
+                                 f"{ms.n_planes}")
+            if not memm:
+                raise NotImplementedError("metadata input channels: memm flavour only (the reference's preload path "
+                                          "builds no metadata, batch/dataset.py:210-216)")
         step = max(self.batch_size, INTERNAL_BATCH) if predict_fn is None else self.batch_size
         for b0 in range(0, len(mine), step):
             idx = mine[b0:b0 + step]
@@ -182,7 +197,12 @@ class ChunkPredictor:
                 both = torch.from_numpy(np.ascontiguousarray(np.stack([cen, local]))).to(self.data.device)
                 cen_d, loc_d = both[0], both[1]
             x = eng._buf("tiled.x", (P * ph * pw, 16))
-            if memm:
+            if early:       # + the metadata planes in channels C.., and db_with_limits_scaled (transforms.py:57-64)
+                call("crimac_gather_patches_memm_meta", eng.prec, ptr(self.data), C, self.data.shape[1], self.n_range,
+                     ptr(loc_d), P, ph, pw, ptr(x), 16, ptr(self.labels), 1, ms.flags, ms.portion_year,
+                     ptr(ms.portion_day), ms.portion_day.numel(), ptr(ms.time_diff), ms.time_diff.numel(),
+                     ptr(ms.seabed), ms.seabed.numel(), ptr(cen_d.contiguous()))
+            elif memm:
                 call("crimac_gather_patches_memm", eng.prec, ptr(self.data), C, self.data.shape[1], self.n_range,
                      ptr(loc_d), P, ph, pw, ptr(x), 16, ptr(self.labels))
             else:
@@ -363,6 +383,10 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
     if not chunks:
         return
     n_freq = len(segpipe.frequencies)
+    if not cp.engine.lmi and cp.engine.in_channels > n_freq:
+        raise NotImplementedError(f"predict_survey: the model takes {cp.engine.in_channels} input channels for "
+                                  f"{n_freq} frequencies (metadata planes as input channels); the zarr preload path has "
+                                  "no metadata (batch/dataset.py:210-216) -- use predict_echogram_memm(meta_channels=...)")
     widest = max(e - s for s, e in chunks)
     halo = patch_size[1]
     n_data = n_freq * (widest + 2 * halo) * n_range
@@ -531,10 +555,17 @@ def predict_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_si
     ``echogram``: the reference's ``Echogram`` API -- ``shape = (n_range, n_pings)``, ``data_memmaps(freqs)`` ->
     list of [n_range, n_pings] arrays, ``label_memmap()``, ``get_seabed(idx_ping, n_pings)``.  The whole echogram is
     one grid (ping_start 0); the arrays are transposed to the ping-major layout of the gather kernel on the GPU.
+    ``meta_channels`` (the yaml's dict): the metadata planes of a UNet_LateMetInject model, or -- required for a model
+    whose input channels outnumber the frequencies (early injection) -- its extra input channels, gathered into the
+    crop with the data planes (which then take db_with_limits_scaled, transforms.py:57-64).
     """
     n_range, n_pings = echogram.shape
     model = segpipe.model.to(segpipe.device).eval()
     dev = segpipe.device
+    eng = model.infer_engine
+    if not eng.lmi and eng.in_channels > len(segpipe.frequencies) and not meta_channels:
+        raise ValueError(f"the model takes {eng.in_channels} input channels for {len(segpipe.frequencies)} frequencies "
+                         "(metadata planes as input channels): pass meta_channels")
     seabed = np.asarray(echogram.get_seabed(0, n_pings)).astype(np.int32)
     grid = plan_grid(n_range, int(seabed.max()), 0, n_pings, patch_size, patch_overlap)
     if n_range <= patch_size[1]:
@@ -545,7 +576,7 @@ def predict_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_si
     data = data.permute(0, 2, 1).contiguous()                                     # [C, pings, range]
     labels = torch.as_tensor(np.ascontiguousarray(echogram.label_memmap()).astype(np.int16)).to(dev).t().contiguous()
     cp = ChunkPredictor(model, n_range, patch_size, patch_overlap, batch_size, out_f16=True)
-    if meta_channels:                    # late metadata injection: the planes are built on the GPU, per batch of crops
+    if meta_channels:                    # metadata planes (late or early injection): built on the GPU, per batch of crops
         cp.meta_source = MetaSource.from_echogram(echogram, meta_channels, dev)
     cp.load_chunk(data, 0, labels, None, 0, n_pings, seabed=seabed, flavour="memm")
     out = cp.predict(grid, predict_fn=predict_fn)

@@ -132,7 +132,7 @@ extern "C" {
  * binding must refuse a library whose version differs from the header it was written against (an older build that
  * happens to export every symbol would walk a descriptor array with the wrong stride).  crimac_layer_desc_size() is
  * sizeof(crimac_layer_desc) as the library was compiled. */
-#define CRIMAC_ABI_VERSION 8
+#define CRIMAC_ABI_VERSION 9
 int crimac_version(void);
 int crimac_layer_desc_size(void);
 const char* crimac_last_error(void);
@@ -466,6 +466,19 @@ int crimac_gather_patches(int prec, const float* data, int C, int Wd, int H, con
  * maps to "ignore" (negative ids), are set to 0.0 after the dB transform (set_data_border_value). */
 int crimac_gather_patches_memm(int prec, const float* data, int C, int Wd, int H, const int* centres, int P, int ph,
                                int pw, void* out, long ld, const short* border_labels, void* stream);
+/* crimac_gather_patches_memm for a model that takes the metadata planes as extra INPUT channels (early injection,
+ * UNet_Baseline(in_channels = C + Cm), pipeline.py:388-397; the Dataset's np.concatenate((data, meta)),
+ * batch/dataset.py:109): channels 0..C-1 as crimac_gather_patches_memm, with db_with_limits_scaled (1 + dB / 75,
+ * define_data_transform_test(use_metadata=True), transforms.py:57-64) when db_scaled != 0; channels C..C+Cm-1 receive
+ * the crop's metadata planes exactly as crimac_meta_planes computes them (same flags / scalar / vectors, same per-pixel
+ * formula, float64 with one rounding) for the crop centred on meta_centres[p] = (range idx, GLOBAL ping idx) -- the
+ * metadata grid keeps its one-pixel offset to the data grid -- and are not touched by the dB transform or the border
+ * rule.  C + Cm <= ld. */
+int crimac_gather_patches_memm_meta(int prec, const float* data, int C, int Wd, int H, const int* centres, int P,
+                                    int ph, int pw, void* out, long ld, const short* border_labels, int db_scaled,
+                                    int flags, double portion_year, const double* portion_day, int n_day,
+                                    const double* time_diff, int n_td, const long long* seabed, int n_sb,
+                                    const int* meta_centres, void* stream);
 
 /* fill_out_array (save_predict.py:41-65) for P patches: probs [P][ncls][ph][pw] fp32 softmax;
  * centres[p] = (range idx, GLOBAL ping idx); writes channels SANDEEL(1), OTHER(2) of every valid
@@ -556,6 +569,16 @@ int crimac_augment_db_nhwc(int prec, const float* data, const void* labels_in, i
                            short* labels_out, unsigned char* aux_mask, int thr_channel, float thr_lo,
                            float thr_hi, int B, int C, int H, int W, long ld, unsigned long long seed,
                            int do_noise, int do_flip, int db_scaled, void* stream);
+/* The same for a batch whose channels n_data..C-1 are metadata planes (early injection: the reference Dataset's
+ * np.concatenate((data, meta)), batch/dataset.py:109; add_noise_metadata / flip_x_axis_metadata, add_noise.py:42-63,
+ * flip_x_axis.py:27-32): data [B][C][H][W] fp32, channels < n_data are linear sv and are treated exactly as
+ * crimac_augment_db_nhwc treats data[:, :n_data] (same noise draws, same label / aux_mask facts, thr_channel < n_data);
+ * channels >= n_data take the flip of their sample and nothing else (NaN stays NaN, no dB) and are rounded once to the
+ * storage type.  n_data == C is crimac_augment_db_nhwc. */
+int crimac_augment_db_meta_nhwc(int prec, const float* data, const void* labels_in, int label_bytes, void* out,
+                                short* labels_out, unsigned char* aux_mask, int thr_channel, float thr_lo,
+                                float thr_hi, int B, int C, int H, int W, long ld, unsigned long long seed,
+                                int do_noise, int do_flip, int db_scaled, int n_data, void* stream);
 
 /* flip_x_axis_metadata (flip_x_axis.py:27-32) for planes that do not pass through crimac_augment_db_nhwc -- the
  * metadata planes of UNet_LateMetInject (add_noise_metadata, add_noise.py:42-63, leaves them untouched): in [B][C][H][W]
