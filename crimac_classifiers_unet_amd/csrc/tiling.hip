@@ -188,7 +188,104 @@ __global__ __launch_bounds__(256) void pr_histogram_kernel(const float* __restri
   }
 }
 
+// RAW evaluation crops (the per-patch crop of the reference's gridded test Dataset, before any transform): for patch p
+//   data_out [P][C][ph][pw] fp32 linear sv, labels_out [P][ph][pw] int16 raw annotation ids
+// from the resident chunk data [C][Wd][H] / labels [Wd][H].  flavour 0 = get_crop_zarr (dataset.py:358-407): the patch
+// is placed by patch_coord_to_data_coord (centre - size / 2 + 1), data 0 / label -100 outside, nan_to_num on the data
+// (NaN -> 0, +-inf -> the largest finite value, here of fp32); flavour 1 = get_crop_memmap (dataset.py:254-287): placed
+// by getGrid (centre - (size + 1) / 2 + 1), DATA_BOUNDARY_VAL 0 / LABEL_BOUNDARY_VAL -100 outside, every non-finite sample
+// 0, and a water column not deeper than the patch puts the centre row at H / 2.
+// A pure streaming transpose: one 32 x 32 tile per block and plane, lanes along range (contiguous in the chunk) when
+// reading, along ping (contiguous in the crop) when writing; `vec`: 16-byte stores (pw % 8 == 0, 16-byte aligned bases).
+__global__ __launch_bounds__(256) void gather_eval_crops_kernel(const float* __restrict__ data, int C, int Wd, int H,
+                                                                const short* __restrict__ labels,
+                                                                const int* __restrict__ centres, int ph, int pw,
+                                                                int flavour, int vec, float* __restrict__ data_out,
+                                                                short* __restrict__ labels_out) {
+  __shared__ float tile[TS][TS + 1];          // [x (ping)][y (range)]
+  __shared__ short ltile[TS][TS + 2];
+  const int p = blockIdx.z;
+  const int ty0 = blockIdx.y * TS, tx0 = blockIdx.x * TS;
+  int cy = centres[2 * p];
+  const int cx = centres[2 * p + 1];
+  if (flavour == 1 && H <= ph) cy = H / 2;                  // dataset.py:259-261
+  const int y_base = cy - (flavour == 1 ? (ph + 1) / 2 : ph / 2) + 1 + ty0;
+  const int x_base = cx - (flavour == 1 ? (pw + 1) / 2 : pw / 2) + 1 + tx0;
+  const int tx = threadIdx.x & 31, tr = threadIdx.x >> 5;   // read phase: tx along range, tr + 8k along ping
+  const int y = y_base + tx;
+  // labels
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int xi = tr + 8 * k, x = x_base + xi;
+    short l = -100;
+    if (x >= 0 && x < Wd && y >= 0 && y < H) l = labels[(long)x * H + y];
+    ltile[xi][tx] = l;
+  }
+  __syncthreads();
+  if (threadIdx.x < 128) {                                  // 32 rows x 4 groups of 8 pings
+    const int yi = threadIdx.x >> 2, q = threadIdx.x & 3;
+    const int py = ty0 + yi, px = tx0 + 8 * q;
+    if (py < ph && px < pw) {
+      short* dst = labels_out + ((long)p * ph + py) * pw + px;
+      if (vec) {                                            // (pw % 8 == 0: the whole group lies inside the row)
+        u16x8 r;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = (unsigned short)ltile[8 * q + j][yi];
+        *reinterpret_cast<u16x8*>(dst) = r;
+      } else {
+        for (int j = 0; j < 8 && px + j < pw; ++j) dst[j] = ltile[8 * q + j][yi];
+      }
+    }
+  }
+  // data planes
+  const int yi = threadIdx.x >> 3, q = threadIdx.x & 7;     // write phase: 32 rows x 8 groups of 4 pings
+  const int py = ty0 + yi, px = tx0 + 4 * q;
+  for (int c = 0; c < C; ++c) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int xi = tr + 8 * k, x = x_base + xi;
+      float v = 0.f;
+      if (x >= 0 && x < Wd && y >= 0 && y < H) v = data[((long)c * Wd + x) * H + y];
+      if (flavour == 1) {
+        if (!isfinite(v)) v = 0.f;
+      } else {
+        if (v != v) v = 0.f;                                // np.nan_to_num
+        v = fminf(fmaxf(v, -3.402823466e+38f), 3.402823466e+38f);
+      }
+      tile[xi][tx] = v;
+    }
+    __syncthreads();
+    if (py < ph && px < pw) {
+      float* dst = data_out + (((long)p * C + c) * ph + py) * pw + px;
+      if (vec) {
+        f32x4 r;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = tile[4 * q + j][yi];
+        *reinterpret_cast<f32x4*>(dst) = r;
+      } else {
+        for (int j = 0; j < 4 && px + j < pw; ++j) dst[j] = tile[4 * q + j][yi];
+      }
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace
+
+extern "C" int crimac_gather_eval_crops(const float* data, int C, int Wd, int H, const short* labels, const int* centres,
+                                        int P, int ph, int pw, int flavour, float* data_out, short* labels_out,
+                                        void* stream) {
+  CRIMAC_REQUIRE(data && labels && centres && data_out && labels_out && C > 0 && Wd > 0 && H > 0 && P > 0 && ph > 0 &&
+                     pw > 0, "gather_eval_crops: bad arguments");
+  CRIMAC_REQUIRE(flavour == 0 || flavour == 1, "gather_eval_crops: flavour=%d (0 zarr, 1 memm)", flavour);
+  CRIMAC_REQUIRE(P <= 65535, "gather_eval_crops: at most 65535 patches per call");
+  const int vec = pw % 8 == 0 && ((uintptr_t)data_out & 15) == 0 && ((uintptr_t)labels_out & 15) == 0;
+  dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
+  hipLaunchKernelGGL(gather_eval_crops_kernel, grid, dim3(256), 0, (hipStream_t)stream, data, C, Wd, H, labels, centres,
+                     ph, pw, flavour, vec, data_out, labels_out);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}
 
 extern "C" int crimac_pr_histogram(const float* logits, int ncls, const void* labels, int label_bytes,
                                    int B, int H, int W, unsigned int* hist_pos, unsigned int* hist_neg,

@@ -10,6 +10,10 @@ reference's names, keyword arguments and file naming.  This package never reache
 Dataset class and the transform factories are INJECTED (``dataset_cls`` / ``data_transform_factory`` /
 ``label_transform_factory``), and the command line (``python -m crimac_classifiers_unet_amd.evaluate``, the reference's
 ``evaluate.py`` ``__main__``, :120-167) takes the location of the host data stack as an explicit ``--data-stack`` path.
+
+``tiled=True`` (``--tiled``) runs the same evaluation without that host chain: ``tiled_inference.evaluate_survey`` /
+``evaluate_echogram_memm`` keep the survey chunk, the crops, the label and data transforms and the PR histograms on the
+GPU and need the readers only -- no Dataset class, no transform factory, no DataLoader workers.
 """
 from __future__ import annotations
 
@@ -55,8 +59,18 @@ def _is_use_metadata(meta_channels):
 def validate_model_survey_zarr(readers, segpipe, meta_channels, patch_size, patch_overlap, eval_mode, batch_size,
                                num_workers, save_path_metrics, save_path_plot, preload_n_pings=0, survey="survey",
                                dataset_cls=None, data_transform_factory=None, label_transform_factory=None,
-                               worker_init_fn=None, **kwargs):
-    """evaluate.py:39-81: one zarr file = one survey; gridded patches of the whole survey -> PR curve / F1."""
+                               worker_init_fn=None, tiled=False, **kwargs):
+    """evaluate.py:39-81: one zarr file = one survey; gridded patches of the whole survey -> PR curve / F1.
+    ``tiled=True``: on the tiled GPU path (``tiled_inference.evaluate_survey``); ``preload_n_pings`` > 0 is then the
+    chunk size (0: the default of ``predict_survey``), and no factory is needed."""
+    if tiled:
+        from .tiled_inference import evaluate_survey
+        if not segpipe.model_is_loaded:
+            segpipe.load_model_params()
+        assert len(readers) == 1, "Current evaluation code assumes one zarr file contains an entire survey"
+        hp, hn = evaluate_survey(readers[0], segpipe, patch_size, patch_overlap, batch_size, preload_n_pings,
+                                 eval_mode=eval_mode)
+        return _tiled_metrics(segpipe, hp, hn, save_path_metrics, save_path_plot, survey)
     dataset_cls, dtf, ltf = _reference_factories(dataset_cls, data_transform_factory, label_transform_factory, False)
     assert len(readers) == 1, "Current evaluation code assumes one zarr file contains an entire survey"
     assert preload_n_pings == 0, "Current evaluation code for zarr only works when 'preloading_n_pings' = 0"
@@ -80,8 +94,24 @@ def validate_model_survey_zarr(readers, segpipe, meta_channels, patch_size, patc
 def validate_model_survey_memm(readers, segpipe, meta_channels, patch_size, patch_overlap, eval_mode, batch_size,
                                num_workers, save_path_metrics, save_path_plot, survey="survey", dataset_cls=None,
                                data_transform_factory=None, label_transform_factory=None, worker_init_fn=None,
-                               **kwargs):
-    """evaluate.py:84-117: one gridded Dataset per echogram, concatenated -> PR curve / F1 of the survey."""
+                               tiled=False, **kwargs):
+    """evaluate.py:84-117: one gridded Dataset per echogram, concatenated -> PR curve / F1 of the survey.
+    ``tiled=True``: every echogram on the tiled GPU path (``tiled_inference.evaluate_echogram_memm``; with several ranks
+    the echograms are dealt to the ranks and the histograms all-reduced once); no factory is needed."""
+    if tiled:
+        import torch
+
+        from . import parallel
+        from .tiled_inference import PR_BINS, _dist_rank_world, evaluate_echogram_memm, finish_histograms
+        if not segpipe.model_is_loaded:
+            segpipe.load_model_params()
+        hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=segpipe.device)
+        rank, world = _dist_rank_world()
+        for i in parallel.shard_indices(len(readers), rank, world):
+            evaluate_echogram_memm(readers[i], segpipe, patch_size, patch_overlap, batch_size, eval_mode=eval_mode,
+                                   meta_channels=meta_channels or None, hist=hist)
+        hp, hn = finish_histograms(hist)
+        return _tiled_metrics(segpipe, hp, hn, save_path_metrics, save_path_plot, survey)
     dataset_cls, dtf, ltf = _reference_factories(dataset_cls, data_transform_factory, label_transform_factory, True)
     frequencies = segpipe.frequencies
     data_transform = dtf(_is_use_metadata(meta_channels))
@@ -95,6 +125,13 @@ def validate_model_survey_memm(readers, segpipe, meta_channels, patch_size, patc
     return segpipe.validate_model_testing(
         dataloader, save_path_metrics=os.path.join(save_path_metrics, f"{survey}_test.csv"),
         save_path_plot=os.path.join(save_path_plot, f"{survey}_pr.png"))
+
+
+def _tiled_metrics(segpipe, hist_pos, hist_neg, save_path_metrics, save_path_plot, survey):
+    return segpipe.validate_model_testing_from_histograms(
+        hist_pos, hist_neg,
+        save_path_metrics=None if save_path_metrics is None else os.path.join(save_path_metrics, f"{survey}_test.csv"),
+        save_path_plot=None if save_path_plot is None else os.path.join(save_path_plot, f"{survey}_pr.png"))
 
 
 def main(argv=None, data_partition_factory=None, factories=None):
@@ -122,7 +159,10 @@ def main(argv=None, data_partition_factory=None, factories=None):
     ap.add_argument("--data_mode", choices=["memm", "zarr"])
     ap.add_argument("--data-stack", dest="data_stack", default=None,
                     help="checkout of the host data stack (the reference's crimac_unet directory): readers, partition, "
-                         "Dataset, transforms")
+                         "Dataset, transforms (with --tiled: readers and partition only)")
+    ap.add_argument("--tiled", action="store_true", default=None,
+                    help="evaluate on the tiled GPU path: chunk, crops, transforms and PR histograms stay on the GPU; "
+                         "no Dataset / transform factories, no DataLoader workers")
     args = ap.parse_args(argv)
     config = yaml.safe_load(open(args.yaml_path))
     for k, v in vars(args).items():                     # command line takes precedence (utils/general.py:128-136)
@@ -133,6 +173,9 @@ def main(argv=None, data_partition_factory=None, factories=None):
     memm = config["data_mode"] == "memm"
     if config["data_mode"] not in ("zarr", "memm"):
         raise ValueError('data_mode not in ["zarr", "memm"]')
+    tiled = bool(config.pop("tiled", False))
+    if tiled:
+        factories = factories or (None, None, None)
     if factories is None:
         if data_stack is None:
             raise SystemExit("evaluate: name the host data stack with --data-stack PATH (or call main() with injected "
@@ -171,7 +214,7 @@ def main(argv=None, data_partition_factory=None, factories=None):
         print("Running evaluation for", survey)
         fn = validate_model_survey_memm if memm else validate_model_survey_zarr
         kw = dict(config)
-        kw.update(survey=survey, dataset_cls=ds, data_transform_factory=dtf, label_transform_factory=ltf)
+        kw.update(survey=survey, dataset_cls=ds, data_transform_factory=dtf, label_transform_factory=ltf, tiled=tiled)
         results[survey] = fn(readers, segpipe, **kw)
     return results
 

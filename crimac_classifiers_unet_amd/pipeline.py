@@ -317,27 +317,10 @@ class SegPipe:
             raise NotImplementedError("use_gpu_test_transform: zarr readers only (the memmap flow's set_data_border_value "
                                       "lives in the tiled path, tiled_inference.predict_echogram_memm)")
         n_pings, n_range = (int(v) for v in reader.shape)
-        boxes = None
-        if self.eval_mode in ("region", "trace"):
-            # get_extended_label_mask_for_crop (extend_label_masks.py:57-80); the reference asks the reader for
-            # get_object_bounding_boxes(), which only its memmap Echogram defines (data_reader.py:404) -- a zarr reader
-            # without it fails there with an AttributeError
-            if not hasattr(reader, "get_object_bounding_boxes"):
-                raise NotImplementedError(
-                    f"eval_mode={self.eval_mode!r}: the reader has no get_object_bounding_boxes() (the reference's "
-                    "get_extended_label_mask_for_crop needs it, extend_label_masks.py:67); use eval_mode='all'")
-            bb = np.array(reader.get_object_bounding_boxes(), dtype=np.int64).reshape(-1, 4)
-            if self.eval_mode == "region":
-                bb[:, 0] -= int(extend_size)
-                bb[:, 1] += int(extend_size)
-            else:
-                bb[:, 0] = 0
-                bb[:, 1] = int(reader.shape[0])          # (the reference's `echogram.shape[0]`, :78)
-            bb[:, 2] -= int(extend_size)
-            bb[:, 3] += int(extend_size)
-            boxes = torch.from_numpy(np.ascontiguousarray(bb.astype(np.int32))).to(self.device)
-        elif self.eval_mode != "all":
-            raise ValueError(f"eval_mode={self.eval_mode!r}: 'all', 'region' or 'trace' (batch/transforms.py:87)")
+        from .tiled_inference import eval_boxes
+        boxes = eval_boxes(reader, self.eval_mode, extend_size)     # get_extended_label_mask_for_crop's boxes, or None
+        if boxes is not None:
+            boxes = torch.from_numpy(boxes).to(self.device)
         sb = np.ascontiguousarray(np.asarray(reader.get_seabed(0, n_pings, return_numpy=True)).astype(np.int32))
         self._test_source = {"reader": reader, "seabed_host": sb, "seabed_dev": None, "blocks": {},
                              "boxes": boxes, "n_pings": n_pings, "n_range": n_range,
@@ -376,7 +359,8 @@ class SegPipe:
 
     def _predict_raw_batch(self, batch):
         """(logits, transformed int16 labels on the device) of one batch of RAW crops (``use_gpu_test_transform``)."""
-        from .hip import MASK_PER_PATCH, call, ptr
+        from .hip import MASK_PER_PATCH
+        from .tiled_inference import raw_crops_to_logits
         src, dev = self._test_source, self.device
         self.model.eval()
         data = batch["data"].to(dev)
@@ -399,23 +383,12 @@ class SegPipe:
         cen = cen_host.to(dev).contiguous()
         B, C, H, W = data.shape
         seabed, mask = self._test_seabed(cen_host.numpy(), B, W)
-        out = torch.empty((B, H, W), dtype=torch.int16, device=dev)
-        eng = self.model.infer_engine
-        with torch.no_grad(), torch.cuda.device(dev):
-            call("crimac_labels_test_transform", ptr(labels), labels.element_size(), ptr(data), len(self.frequencies) - 1,
-                 1e-7, 1e-4, ptr(cen), ptr(seabed), 0, src["n_pings"] if seabed is not None else 0,
-                 ptr(mask), MASK_PER_PATCH if mask is not None else 0, B * W if mask is not None else 0, src["n_range"],
-                 src["pad"], 0, src["overlap"], ptr(out), B, C, H, W)
-            if src["boxes"] is not None:         # eval_mode 'region' / 'trace'
-                call("crimac_labels_extend_mask", ptr(out), ptr(data), C, ptr(cen), ptr(src["boxes"]),
-                     int(src["boxes"].shape[0]), -1, B, H, W)
-            # remove_nan_inf + db_with_limits (db_with_limits_scaled with metadata channels)
-            if batch_in is not None:
-                x, _ = eng.augment_batch(batch_in, None, 0, do_noise=False, do_flip=False, db_scaled=True, n_data=nf)
-            else:
-                x, _ = eng.augment_batch(data, None, 0, do_noise=False, do_flip=False, db_scaled=self.use_metadata)
-            logits = eng.forward_nhwc(x, B, H, W, training=False, meta=meta)
-        return logits, out
+        return raw_crops_to_logits(
+            self.model.infer_engine, data, labels, cen, thr_channel=len(self.frequencies) - 1, seabed=seabed, seabed_ping0=0,
+            seabed_pings=src["n_pings"] if seabed is not None else 0, mask=mask,
+            mask_ping0=MASK_PER_PATCH if mask is not None else 0, mask_pings=B * W if mask is not None else 0,
+            n_range=src["n_range"], pad=src["pad"], seabed_rule=0, overlap=src["overlap"], boxes=src["boxes"],
+            db_scaled=self.use_metadata, meta=meta, batch_in=batch_in, n_data=nf)
 
     def set_label_ignore_val(self, labels):
         """Reference pipeline.py:222-239 (in place, like the reference)."""
@@ -584,6 +557,15 @@ class SegPipe:
             preds[labels == LABEL_SEABED_MASK_VAL] = 0
             labels, preds = self.select_valid_predictions(labels=labels, preds=preds)
             metrics = self.compute_evaluation_metrics(labels=labels, preds=preds)
+        return self._finish_testing(metrics, save_path_metrics, save_path_plot)
+
+    def validate_model_testing_from_histograms(self, hist_pos, hist_neg, save_path_metrics, save_path_plot):
+        """The tail of ``validate_model_testing`` for a caller that already holds the PR histograms of the test set
+        (``tiled_inference.evaluate_survey`` / ``evaluate_echogram_memm``): metrics, csv, plot, the printed F1."""
+        metrics = self.compute_evaluation_metrics_from_histograms(np.asarray(hist_pos), np.asarray(hist_neg))
+        return self._finish_testing(metrics, save_path_metrics, save_path_plot)
+
+    def _finish_testing(self, metrics, save_path_metrics, save_path_plot):
         metrics["thresholds"] = np.append(np.asarray(metrics["thresholds"], dtype=np.float64), np.nan)
         if parallel.env_world()[1] == 0:
             if save_path_metrics is not None:

@@ -119,12 +119,14 @@ class ChunkPredictor:
         return self.engine.device or next(self.model.parameters()).device
 
     def load_chunk(self, data, data_ping0, labels, seabed_mask, start_ping, end_ping, seabed=None, seabed_ping0=None,
-                   flavour="zarr", stream=None):
+                   flavour="zarr", stream=None, wide=False):
         """data [C, pings, range] fp32 (global ping of column 0 = data_ping0; numpy or a pinned CPU tensor);
         labels [end-start, range] (or None); for pings [start_ping, end_ping) either ``seabed_mask``
         [end-start, range] uint8/bool (1 below the seabed, as the reader's get_seabed_mask(..., seabed_pad=0)) or
         -- cheaper, nothing to build on the host -- ``seabed`` [n] int seabed index per ping starting at global ping
-        ``seabed_ping0`` (default start_ping).  ``stream``: copy stream for the uploads (the caller orders it)."""
+        ``seabed_ping0`` (default start_ping).  ``stream``: copy stream for the uploads (the caller orders it).
+        ``wide`` (the chunk of ``evaluate``): ``labels`` and ``seabed_mask`` cover the pings of ``data`` -- every ping a
+        patch can touch -- not only [start_ping, end_ping), and no prediction array is allocated."""
         dev = self._device()
         nb = stream is not None
 
@@ -148,6 +150,10 @@ class ChunkPredictor:
         self.seabed_ping0 = int(start_ping if seabed_ping0 is None else seabed_ping0)
         self.start_ping, self.end_ping = int(start_ping), int(end_ping)
         self.flavour = flavour
+        self.wide = bool(wide)
+        if self.wide:
+            self.out = None
+            return
         self.out = torch.zeros((2, self.n_range, self.end_ping - self.start_ping),
                                dtype=torch.float16 if self.out_f16 else torch.float32, device=dev)
 
@@ -162,6 +168,8 @@ class ChunkPredictor:
         ``centres_dev``: int32 [2, P, 2] on the GPU = (global centres, centres relative to the data slice), uploaded
         by the caller (a pageable host-to-device copy here would block the host until the stream has drained and
         serialise the enqueue of a chunk with the execution of the previous one)."""
+        if self.wide:
+            raise ValueError("ChunkPredictor.predict: the chunk was loaded for evaluate() (wide=True)")
         eng = self.engine
         eng.bind()
         ph, pw = self.patch_size[1], self.patch_size[0]
@@ -227,6 +235,176 @@ class ChunkPredictor:
         if world > 1:
             torch.distributed.all_reduce(self.out)      # interiors are disjoint: sum == union (exact in fp16 too)
         return self.out
+
+    def _check_meta(self, C):
+        """Early-injection models (metadata planes as extra input channels): the conditions of ``predict``."""
+        eng, ms = self.engine, self.meta_source
+        early = not eng.lmi and eng.in_channels > C
+        if early:
+            if ms is None:
+                raise ValueError(f"the model takes {eng.in_channels} input channels and the chunk has {C} data planes: "
+                                 "an early-injection model needs the metadata planes, set ChunkPredictor.meta_source "
+                                 "(MetaSource.from_echogram(...))")
+            if ms.n_planes != eng.in_channels - C:
+                raise ValueError(f"the model takes {eng.in_channels - C} metadata input channels, meta_source builds "
+                                 f"{ms.n_planes}")
+            if self.flavour != "memm":
+                raise NotImplementedError("metadata input channels: memm flavour only (the reference's preload path "
+                                          "builds no metadata, batch/dataset.py:210-216)")
+        return early
+
+    def evaluate(self, grid, hist, eval_mode="all", boxes=None, predict_fn=None, on_batch=None):
+        """Test-set evaluation of the patches of ``grid`` ([P, 2] global centres) on a ``wide`` chunk: what the reference's
+        gridded test Dataset + ``get_predictions_dataloader`` + the masking of ``validate_model_testing`` do per patch
+        (batch/dataset.py:207-242; pipeline.py:242-282, :347-353), accumulated into ``hist`` (int32 [2, 16384] on the GPU:
+        the float16 sandeel probability of the valid pixels, by label == SANDEEL / the rest).
+
+        Per internal batch: ``crimac_gather_eval_crops`` (RAW linear-sv crops and raw annotation ids) ->
+        ``crimac_labels_test_transform`` (+ ``crimac_labels_extend_mask`` with ``boxes`` for ``eval_mode`` 'region' /
+        'trace'; ``boxes`` int32 [n, 4] on the GPU, already extended: ``eval_boxes``) -> network input -> eval forward
+        (logits) -> ``crimac_pr_histogram``.  The network input follows the reference's per-patch chain: zarr -- the raw
+        crop through remove_nan_inf + db_with_limits (``augment_batch``; the crop's nan_to_num came first, so an inf
+        sample reaches the network as 0 dB, not as -75 dB as on the preload path); memm -- ``crimac_gather_patches_memm``
+        (``_meta``) straight from the chunk, which ends with set_data_border_value (define_data_transform_test) exactly
+        as ``predict`` feeds it.
+        ``predict_fn(x_nhwc, P, H, W) -> logits [P, 3, H, W]`` replaces the network; ``on_batch(centres [P, 2] numpy,
+        labels int16 [P, H, W], logits [P, 3, H, W])`` sees the transformed labels and the logits of every batch, on the
+        GPU (tests)."""
+        if not self.wide:
+            raise ValueError("ChunkPredictor.evaluate needs a chunk loaded with wide=True (labels and seabed for every "
+                             "ping a patch can touch)")
+        if eval_mode not in ("all", "region", "trace"):
+            raise ValueError(f"eval_mode={eval_mode!r}: 'all', 'region' or 'trace' (batch/transforms.py:87)")
+        if (boxes is not None) != (eval_mode != "all"):
+            raise ValueError(f"eval_mode={eval_mode!r} goes with boxes {'given' if eval_mode != 'all' else 'None'}")
+        if self.labels is None:
+            raise ValueError("ChunkPredictor.evaluate needs the annotation ids of the chunk")
+        eng = self.engine
+        eng.bind()
+        ph, pw = self.patch_size[1], self.patch_size[0]
+        C, Wd = self.data.shape[0], self.data.shape[1]
+        if tuple(self.labels.shape) != (Wd, self.n_range):
+            raise ValueError(f"labels {tuple(self.labels.shape)} do not cover the data extent {(Wd, self.n_range)}")
+        memm = self.flavour == "memm"
+        early = self._check_meta(C)
+        ms = self.meta_source
+        if eng.lmi and ms is None:
+            raise ValueError("a UNet_LateMetInject model needs the metadata planes: set ChunkPredictor.meta_source "
+                             "(MetaSource.from_echogram(...))")
+        if (eng.lmi or early) and not memm:
+            raise NotImplementedError("metadata planes: memm flavour only (the zarr path builds none)")
+        grid = np.asarray(grid)
+        step = max(self.batch_size, INTERNAL_BATCH) if predict_fn is None else self.batch_size
+        dev = self.data.device
+        for b0 in range(0, len(grid), step):
+            cen = grid[b0:b0 + step].astype(np.int32)
+            P = len(cen)
+            local = cen.copy()
+            local[:, 1] -= self.data_ping0
+            both = torch.from_numpy(np.ascontiguousarray(np.stack([cen, local]))).to(dev)
+            cen_d, loc_d = both[0].contiguous(), both[1].contiguous()
+            raw = eng._buf("eval.raw", (P, C, ph, pw), torch.float32)
+            lab = eng._buf("eval.lab", (P, ph, pw), torch.int16)
+            call("crimac_gather_eval_crops", ptr(self.data), C, Wd, self.n_range, ptr(self.labels), ptr(loc_d), P, ph,
+                 pw, 1 if memm else 0, ptr(raw), ptr(lab))
+            x = meta = None
+            if memm and boxes is not None:
+                # 'region' / 'trace': the extended mask turns -100 pixels outside the boxes into -1 BEFORE
+                # set_data_border_value looks for -100 (batch/dataset.py:229-235), so the border rule follows the
+                # transformed labels and cannot be read off the raw ids as crimac_gather_patches_memm does
+                if eng.lmi or early:
+                    raise NotImplementedError(f"eval_mode={eval_mode!r} with metadata planes on the tiled path; use "
+                                              "eval_mode='all' or the DataLoader path")
+            elif memm:
+                x = eng._buf("tiled.x", (P * ph * pw, 16))
+                if early:
+                    call("crimac_gather_patches_memm_meta", eng.prec, ptr(self.data), C, Wd, self.n_range, ptr(loc_d), P,
+                         ph, pw, ptr(x), 16, ptr(self.labels), 1, ms.flags, ms.portion_year, ptr(ms.portion_day),
+                         ms.portion_day.numel(), ptr(ms.time_diff), ms.time_diff.numel(), ptr(ms.seabed),
+                         ms.seabed.numel(), ptr(cen_d))
+                else:
+                    call("crimac_gather_patches_memm", eng.prec, ptr(self.data), C, Wd, self.n_range, ptr(loc_d), P, ph,
+                         pw, ptr(x), 16, ptr(self.labels))
+                if eng.lmi:
+                    meta = ms.planes(cen_d, self.patch_size)
+            logits, labels_t = raw_crops_to_logits(
+                eng, raw, lab, cen_d.long().contiguous(), thr_channel=C - 1, seabed=self.seabed,
+                seabed_ping0=self.seabed_ping0, seabed_pings=0 if self.seabed is None else self.seabed.numel(),
+                mask=self.mask, mask_ping0=self.data_ping0, mask_pings=0 if self.mask is None else self.mask.shape[0],
+                n_range=self.n_range, pad=SEABED_PAD, seabed_rule=1 if memm else 0, overlap=self.patch_overlap,
+                boxes=boxes, meta=meta, x=x, predict_fn=predict_fn, split=True,
+                border_to_0db=memm and boxes is not None)
+            if on_batch is not None:
+                on_batch(cen, labels_t, logits)
+            B, nc, H, W = logits.shape
+            call("crimac_pr_histogram", ptr(logits), nc, ptr(labels_t), labels_t.element_size(), B, H, W, ptr(hist[0]),
+                 ptr(hist[1]))
+        return hist
+
+
+def raw_crops_to_logits(eng, data, labels, centres, *, thr_channel, seabed, seabed_ping0, seabed_pings, mask, mask_ping0,
+                        mask_pings, n_range, pad, seabed_rule, overlap, boxes, db_scaled=False, meta=None, batch_in=None,
+                        n_data=None, x=None, predict_fn=None, split=False, border_to_0db=False):
+    """The body the two evaluation flows share -- DataLoader batches of RAW crops (``SegPipe._predict_raw_batch``) and
+    crops gathered from a resident chunk (``ChunkPredictor.evaluate``): data [B, C, H, W] fp32 linear sv, labels [B, H, W]
+    raw annotation ids, centres int64 [B, 2] (range idx, global ping idx), all on the GPU ->
+    (logits [B, ncls, H, W], transformed int16 labels [B, H, W]).
+
+    ``crimac_labels_test_transform`` (seabed vector OR mask, as ``crimac_scatter_patches_ex`` takes them) ->
+    ``crimac_labels_extend_mask`` when ``boxes`` is given -> network input ``x`` (given, or remove_nan_inf + db_with_limits
+    of ``data`` -- of ``batch_in`` = data | metadata planes with ``n_data`` data channels for an early-injection model)
+    -> eval forward (``split``: the two-stream form of the tiled path) or ``predict_fn(x, B, H, W)``.
+    ``border_to_0db``: set_data_border_value by the TRANSFORMED labels (the memm flavour's define_data_transform_test,
+    transforms.py:57-64): a pixel whose label came out as -100 enters the dB transform as 1.0 and leaves it as 0.0 dB."""
+    dev = data.device
+    B, C, H, W = data.shape
+    out = torch.empty((B, H, W), dtype=torch.int16, device=dev)
+    with torch.no_grad(), torch.cuda.device(dev):
+        call("crimac_labels_test_transform", ptr(labels), labels.element_size(), ptr(data), thr_channel, 1e-7, 1e-4,
+             ptr(centres), ptr(seabed), seabed_ping0, seabed_pings, ptr(mask), mask_ping0, mask_pings, n_range, pad,
+             seabed_rule, overlap, ptr(out), B, C, H, W)
+        if boxes is not None:                    # eval_mode 'region' / 'trace'
+            call("crimac_labels_extend_mask", ptr(out), ptr(data), C, ptr(centres), ptr(boxes), int(boxes.shape[0]), -1,
+                 B, H, W)
+        if x is None:                            # remove_nan_inf + db_with_limits (db_with_limits_scaled with metadata)
+            if border_to_0db:
+                data = data.masked_fill((out == -100).unsqueeze(1), 1.0)
+            if batch_in is not None:
+                x, _ = eng.augment_batch(batch_in, None, 0, do_noise=False, do_flip=False, db_scaled=True, n_data=n_data)
+            else:
+                x, _ = eng.augment_batch(data, None, 0, do_noise=False, do_flip=False, db_scaled=db_scaled)
+        if predict_fn is not None:
+            logits = predict_fn(x, B, H, W)
+        elif split and meta is None:
+            logits = eng.forward_nhwc_eval_split(x, B, H, W, softmax=False)
+        else:
+            logits = eng.forward_nhwc(x, B, H, W, training=False, meta=meta)
+    return logits, out
+
+
+def eval_boxes(reader, eval_mode, extend_size=20):
+    """School bounding boxes (y0, y1, x0, x1) as ``crimac_labels_extend_mask`` takes them for ``eval_mode`` 'region' /
+    'trace' (get_extended_label_mask_for_crop, extend_label_masks.py:57-80), int32 [n, 4] numpy; None for 'all'.  The
+    reference asks the reader for get_object_bounding_boxes(), which only its memmap Echogram defines
+    (data_reader.py:404) -- a zarr reader without it fails there with an AttributeError."""
+    if eval_mode == "all":
+        return None
+    if eval_mode not in ("region", "trace"):
+        raise ValueError(f"eval_mode={eval_mode!r}: 'all', 'region' or 'trace' (batch/transforms.py:87)")
+    if not hasattr(reader, "get_object_bounding_boxes"):
+        raise NotImplementedError(
+            f"eval_mode={eval_mode!r}: the reader has no get_object_bounding_boxes() (the reference's "
+            "get_extended_label_mask_for_crop needs it, extend_label_masks.py:67); use eval_mode='all'")
+    bb = np.array(reader.get_object_bounding_boxes(), dtype=np.int64).reshape(-1, 4)
+    if eval_mode == "region":
+        bb[:, 0] -= int(extend_size)
+        bb[:, 1] += int(extend_size)
+    else:
+        bb[:, 0] = 0
+        bb[:, 1] = int(reader.shape[0])          # (the reference's `echogram.shape[0]`, :78)
+    bb[:, 2] -= int(extend_size)
+    bb[:, 3] += int(extend_size)
+    return np.ascontiguousarray(bb.astype(np.int32))
 
 
 def seabed_vector_or_mask(reader, s, e, n_range, sb, sb_ping0):
@@ -581,3 +759,206 @@ def predict_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_si
     cp.load_chunk(data, 0, labels, None, 0, n_pings, seabed=seabed, flavour="memm")
     out = cp.predict(grid, predict_fn=predict_fn)
     return out.cpu().numpy().astype(np.float64)
+
+
+# ---- whole-survey evaluation (evaluate.py:39-117 of the reference) on the tiled path -------------------------------------
+PR_BINS = 16384            # CRIMAC_PR_BINS: float16 bit patterns of [0, 1] are 0 .. 0x3C00
+
+
+def plan_eval_grid(n_range, seabed, n_pings, patch_size, patch_overlap, memm=False):
+    """The patch grid of the reference's evaluation: ``DatasetGriddedReader(grid_start=None, grid_end=None,
+    grid_mode='all')`` (evaluate.py:39-117; batch/dataset.py:148-160) -- ONE grid over the whole survey / echogram, range
+    extent capped at the survey's deepest seabed + 50.  ``memm``: get_crop_memmap's centre adjustment for a water column
+    not deeper than the patch (dataset.py:259-261; it writes into the Dataset's own grid, so ``center_coordinates`` and
+    the label transform see the adjusted row too)."""
+    grid = plan_grid(n_range, int(np.max(seabed)), 0, n_pings, patch_size, patch_overlap)
+    if memm and n_range <= patch_size[1]:
+        grid = grid.copy()
+        grid[:, 0] = n_range // 2
+    return grid
+
+
+def plan_eval_chunks(grid, n_pings, patch_size, preload_n_pings):
+    """Cut the survey's grid into chunks by CENTRE ping: ``[(patch indices, lo, hi)]`` for every chunk of ``plan_chunks``
+    that owns a patch, with [lo, hi) the pings its patches touch (clipped to the survey).  Every patch belongs to exactly
+    one chunk whatever the chunk size, so the chunk size cannot change the result."""
+    chunks = plan_chunks(0, n_pings, preload_n_pings)
+    starts = np.array([s for s, _ in chunks])
+    owner = np.searchsorted(starts, np.clip(grid[:, 1], 0, n_pings - 1), side="right") - 1
+    pw = int(patch_size[0])
+    out = []
+    for k in range(len(chunks)):
+        idx = np.nonzero(owner == k)[0]
+        if len(idx):
+            x0 = grid[idx, 1] - pw // 2 + 1            # first ping of a patch (patch_coord_to_data_coord)
+            out.append((idx, max(0, int(x0.min())), min(n_pings, int(x0.max()) + pw)))
+    return out
+
+
+def finish_histograms(hist, all_reduce=True):
+    """int32 [2, 16384] on the GPU -> (hist_pos, hist_neg) int64 numpy; with several ranks the ONE collective of the flow
+    (the histograms are the metric's sufficient statistic, as in ``SegPipe.get_pr_histograms_dataloader``)."""
+    dist = torch.distributed
+    if all_reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(hist)
+    h = hist.cpu().numpy().astype(np.int64)
+    if h[:, PR_BINS - 1].any():           # CRIMAC_PR_NAN_BIN: sklearn raises on NaN scores as well
+        raise ValueError("Input contains NaN (sandeel probabilities of the validation set)")
+    return h[0], h[1]
+
+
+def _dist_rank_world():
+    dist = torch.distributed
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
+def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, eval_mode="all",
+                    extend_size=20, predict_fn=None, on_batch=None, stats=None, **kwargs):
+    """Test-set evaluation of one zarr survey (``validate_model_survey_zarr``, evaluate.py:39-81) on the tiled path:
+    returns ``(hist_pos, hist_neg)`` int64 numpy [16384] -- what ``SegPipe.get_pr_histograms_dataloader`` returns for the
+    reference's gridded test DataLoader over the same survey; ``SegPipe.validate_model_testing_from_histograms`` turns
+    them into the PR curve / F1.
+
+    The grid is the whole survey's (``plan_eval_grid``); it is cut into chunks of at most ``preload_n_pings`` centre
+    pings (``plan_eval_chunks``), every chunk is read ONCE over the pings its patches touch -- data, annotation ids and
+    seabed (``seabed_vector_or_mask``, checked on exactly those pings) -- into pinned staging, uploaded on a copy stream
+    while the previous chunk computes, and evaluated by ``ChunkPredictor.evaluate``; nothing but the two histograms comes
+    back.  With torch.distributed initialised the chunks are dealt to the ranks (``parallel.shard_indices``) and the
+    histograms all-reduced once at the end; every rank returns the survey's histograms.
+    ``reader``: the reference's zarr reader API (shape, get_data_slice, get_label_slice, get_seabed, get_seabed_mask;
+    get_object_bounding_boxes for ``eval_mode`` 'region' / 'trace')."""
+    from concurrent.futures import ThreadPoolExecutor
+    import time as _time
+    n_pings, n_range = (int(v) for v in reader.shape)
+    dev = segpipe.device
+    model = segpipe.model.to(dev).eval()
+    cp = ChunkPredictor(model, n_range, patch_size, patch_overlap, batch_size)
+    n_freq = len(segpipe.frequencies)
+    if cp.engine.lmi or cp.engine.in_channels > n_freq:
+        raise NotImplementedError("evaluate_survey: metadata planes (late or early injection) exist on the memm flavour "
+                                  "only (batch/dataset.py:210-216) -- use evaluate_echogram_memm(meta_channels=...)")
+    boxes = eval_boxes(reader, eval_mode, extend_size)
+    if boxes is not None:
+        boxes = torch.from_numpy(boxes).to(dev)
+    sb_all = np.asarray(reader.get_seabed(0, n_pings, return_numpy=True)).astype(np.int32)
+    grid = plan_eval_grid(n_range, sb_all, n_pings, patch_size, patch_overlap)
+    chunks = plan_eval_chunks(grid, n_pings, patch_size, preload_n_pings)
+    rank, world = _dist_rank_world()
+    mine = [chunks[i] for i in parallel.shard_indices(len(chunks), rank, world)]
+    hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=dev)
+    if stats is not None:
+        stats["patches"] = int(sum(len(c[0]) for c in mine))
+        stats["chunks"] = len(mine)
+    if not mine:
+        return finish_histograms(hist)
+    widest = max(hi - lo for _, lo, hi in mine)
+    NS = 2
+    key = ("eval", str(dev), n_freq, widest, n_range)
+    bufs = _STAGING.get(key)
+    if bufs is None or bufs["busy"]:
+        fresh = {
+            "stage_data": [torch.empty(n_freq * widest * n_range, dtype=torch.float32).pin_memory() for _ in range(NS)],
+            "stage_lab": [torch.empty(widest * n_range, dtype=torch.int16).pin_memory() for _ in range(NS)],
+            "stage_sb": [torch.empty(widest, dtype=torch.int32).pin_memory() for _ in range(NS)],
+            "dev_data": [torch.empty(n_freq * widest * n_range, dtype=torch.float32, device=dev) for _ in range(2)],
+            "dev_lab": [torch.empty(widest * n_range, dtype=torch.int16, device=dev) for _ in range(2)],
+            "dev_sb": [torch.empty(widest, dtype=torch.int32, device=dev) for _ in range(2)],
+            "busy": False,
+        }
+        if bufs is None:
+            _STAGING.clear()             # (one geometry at a time: the buffers are large)
+            _STAGING[key] = fresh
+        bufs = fresh
+    bufs["busy"] = True
+    uploaded = [torch.cuda.Event() for _ in range(NS)]        # host slot may be overwritten once this has passed
+    computed = [torch.cuda.Event() for _ in range(2)]         # device slot may be overwritten once this has passed
+    copy_stream = torch.cuda.Stream(device=dev)
+    main = torch.cuda.current_stream()
+
+    def fetch(i, lo, hi):
+        k = i % NS
+        n = hi - lo
+        uploaded[k].synchronize()                             # (no-op until the slot has been used)
+        data = reader.get_data_slice(idx_ping=lo, n_pings=n, frequencies=segpipe.frequencies, return_numpy=True)
+        d_t = bufs["stage_data"][k][:n_freq * n * n_range].view(n_freq, n, n_range)
+        np.copyto(d_t.numpy(), data, casting="same_kind")
+        lab = np.asarray(reader.get_label_slice(idx_ping=lo, n_pings=n, return_numpy=True))
+        if lab.dtype.kind == "f":                             # get_crop_zarr: nan_to_num(labels, nan=LABEL_BOUNDARY_VAL)
+            lab = np.nan_to_num(lab, nan=-100.0)
+        l_t = bufs["stage_lab"][k][:n * n_range].view(n, n_range)
+        np.copyto(l_t.numpy(), lab, casting="unsafe")
+        sb, mask = seabed_vector_or_mask(reader, lo, hi, n_range, sb_all, 0)
+        s_t = bufs["stage_sb"][k][:n]
+        s_t.numpy()[:] = sb[lo:hi]
+        return d_t, l_t, s_t, mask
+
+    t_start = _time.perf_counter()
+    try:
+        with ThreadPoolExecutor(max_workers=1) as pool:
+            fut = pool.submit(fetch, 0, mine[0][1], mine[0][2])
+            for i, (idx, lo, hi) in enumerate(mine):
+                d_t, l_t, s_t, mask = fut.result()
+                if i + 1 < len(mine):
+                    fut = pool.submit(fetch, i + 1, mine[i + 1][1], mine[i + 1][2])
+                slot = i & 1
+                with torch.cuda.stream(copy_stream):
+                    copy_stream.wait_event(computed[slot])        # chunk i-2 is done with this device slot
+                    d_d = bufs["dev_data"][slot][:d_t.numel()].view(d_t.shape)
+                    d_d.copy_(d_t, non_blocking=True)
+                    l_d = bufs["dev_lab"][slot][:l_t.numel()].view(l_t.shape)
+                    l_d.copy_(l_t, non_blocking=True)
+                    s_d = bufs["dev_sb"][slot][:hi - lo]
+                    s_d.copy_(s_t, non_blocking=True)
+                    uploaded[i % NS].record()
+                main.wait_stream(copy_stream)
+                if mask is None:
+                    cp.load_chunk(d_d, lo, l_d, None, lo, hi, seabed=s_d, seabed_ping0=lo, wide=True)
+                else:                                 # (a mask the vector rule cannot express: uploaded as it is)
+                    cp.load_chunk(d_d, lo, l_d, mask, lo, hi, wide=True)
+                cp.evaluate(grid[idx], hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch)
+                computed[slot].record()
+        out = finish_histograms(hist)
+    finally:
+        torch.cuda.current_stream().synchronize()     # (nothing of this survey still reads or writes the staging)
+        bufs["busy"] = False
+    if stats is not None:
+        stats["seconds"] = _time.perf_counter() - t_start
+    return out
+
+
+def evaluate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, eval_mode="all", extend_size=20,
+                           predict_fn=None, meta_channels=None, hist=None, on_batch=None, **kwargs):
+    """Test-set evaluation of one memmap echogram (one Dataset of ``validate_model_survey_memm``, evaluate.py:84-117) on
+    the tiled path.  The echogram is one resident chunk, its grid the echogram's (``plan_eval_grid``); metadata models
+    (late injection and metadata input channels) take ``meta_channels`` exactly as ``predict_echogram_memm`` does.
+
+    ``hist`` (int32 [2, 16384] on the GPU): accumulate into it and return it -- a survey of several echograms, whose caller
+    finishes with ``finish_histograms``; None: returns this echogram's ``(hist_pos, hist_neg)`` int64 numpy (no
+    collective: every rank that calls it evaluates the echogram it passes)."""
+    n_range, n_pings = (int(v) for v in echogram.shape)
+    dev = segpipe.device
+    model = segpipe.model.to(dev).eval()
+    eng = model.infer_engine
+    if not eng.lmi and eng.in_channels > len(segpipe.frequencies) and not meta_channels:
+        raise ValueError(f"the model takes {eng.in_channels} input channels for {len(segpipe.frequencies)} frequencies "
+                         "(metadata planes as input channels): pass meta_channels")
+    boxes = eval_boxes(echogram, eval_mode, extend_size)
+    if boxes is not None:
+        boxes = torch.from_numpy(boxes).to(dev)
+    seabed = np.asarray(echogram.get_seabed(0, n_pings)).astype(np.int32)
+    grid = plan_eval_grid(n_range, seabed, n_pings, patch_size, patch_overlap, memm=True)
+    data = torch.stack([torch.as_tensor(np.ascontiguousarray(m, dtype=np.float32))
+                        for m in echogram.data_memmaps(segpipe.frequencies)]).to(dev)
+    data = data.permute(0, 2, 1).contiguous()                                     # [C, pings, range]
+    labels = torch.as_tensor(np.ascontiguousarray(echogram.label_memmap()).astype(np.int16)).to(dev).t().contiguous()
+    cp = ChunkPredictor(model, n_range, patch_size, patch_overlap, batch_size)
+    if meta_channels:
+        cp.meta_source = MetaSource.from_echogram(echogram, meta_channels, dev)
+    cp.load_chunk(data, 0, labels, None, 0, n_pings, seabed=seabed, flavour="memm", wide=True)
+    own = hist is None
+    if own:
+        hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=dev)
+    cp.evaluate(grid, hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch)
+    return finish_histograms(hist, all_reduce=False) if own else hist

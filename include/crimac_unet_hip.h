@@ -508,6 +508,24 @@ int crimac_scatter_patches_ex(const float* probs, int ncls, const int* centres, 
                               int seabed_ping0, int seabed_pings, const float* data0, int data_ping0, int data_pings,
                               int seabed_pad, int seabed_rule, void* out, int out_f16, void* stream);
 
+/* RAW evaluation crops of P patches from a resident chunk -- what the reference's gridded test Dataset crops per patch
+ * before any transform (evaluate.py:39-117; batch/dataset.py:207-219), i.e. the `data` / `labels` of a batch that
+ * crimac_labels_test_transform, crimac_labels_extend_mask and crimac_augment_db_nhwc take:
+ *   data [C][Wd pings][H range] fp32 linear sv, labels [Wd][H] int16 raw annotation ids (same extent as `data`),
+ *   centres[p] = (range idx, ping idx RELATIVE to the chunk slice);
+ *   data_out [P][C][ph][pw] fp32 linear sv, labels_out [P][ph][pw] int16 raw ids.
+ * flavour 0: get_crop_zarr (batch/dataset.py:358-407) with ping_boundary = the survey: patch placed by
+ *   patch_coord_to_data_coord (utils/np.py:378-380), data 0 / label -100 outside the data, np.nan_to_num on the data in
+ *   the crop's own precision (NaN -> 0, +inf / -inf -> +- the largest finite fp32: an inf sample stays a strong echo, it
+ *   is NOT zeroed as in crimac_gather_patches); the caller applies nan_to_num(nan=-100) to float labels when it stages
+ *   them as int16.  The chunk must cover every ping of the survey a patch touches.
+ * flavour 1: get_crop_memmap (batch/dataset.py:254-287): patch placed by getGrid (utils/np.py:38-46), DATA_BOUNDARY_VAL
+ *   0 / LABEL_BOUNDARY_VAL -100 outside, every non-finite sample 0; when H <= ph (the window covers the whole water column)
+ *   the centre row is H / 2 whatever centres[p][0] says (:259-261).
+ * One launch for all P <= 65535 patches; 16-byte stores when pw % 8 == 0 and both outputs are 16-byte aligned. */
+int crimac_gather_eval_crops(const float* data, int C, int Wd, int H, const short* labels, const int* centres, int P,
+                             int ph, int pw, int flavour, float* data_out, short* labels_out, void* stream);
+
 
 /* Validation metrics (get_predictions_dataloader + compute_evaluation_metrics, pipeline.py:242-295):
  * histograms (16384 bins, indexed by the float16 bit pattern of softmax(logits)[SANDEEL]) of the valid

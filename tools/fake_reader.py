@@ -38,13 +38,18 @@ class FakeZarrReader:
         self.name = name
         self.objects = []
 
+    def _range(self, idx_range, n_range):
+        # (callers that name no range get the whole axis, as before; the reference's get_crop_zarr names one)
+        lo = 0 if idx_range is None else int(idx_range)
+        return slice(lo, self.shape[1] if n_range is None else lo + int(n_range))
+
     def get_data_slice(self, idx_ping, n_pings, idx_range=None, n_range=None, frequencies=None,
                        drop_na=False, return_numpy=True):
-        return self.sv[:, idx_ping:idx_ping + n_pings].copy()
+        return self.sv[:, idx_ping:idx_ping + n_pings, self._range(idx_range, n_range)].copy()
 
     def get_label_slice(self, idx_ping, n_pings, idx_range=None, n_range=None, drop_na=False,
                         categories=None, return_numpy=True, correct_transducer_offset=False, mask=True):
-        return self.labels[idx_ping:idx_ping + n_pings].copy()
+        return self.labels[idx_ping:idx_ping + n_pings, self._range(idx_range, n_range)].copy()
 
     def get_seabed(self, idx_ping, n_pings=1, idx_range=None, n_range=None, return_numpy=True):
         v = self.seabed[idx_ping:idx_ping + n_pings]
@@ -93,6 +98,49 @@ def synth_survey(n_pings=1200, n_range=600, channels=4, seed=7):
             px, py = rng.integers(0, n_pings - 40), rng.integers(0, n_range - 30)
             labels[px:px + rng.integers(8, 40), py:py + rng.integers(6, 30)] = val
     return sv, labels, seabed
+
+
+def synth_eval_survey(n_pings=437, n_range=150, seed=21):
+    """Survey of the whole-survey evaluation fixture (tests/golden/survey_eval.npz; tools/make_golden_survey_eval.py and the
+    tests rebuild it from the seed): linear sv [4, pings, range] at HALF-INTEGER dB (10^((k + 0.5) / 10), k = -75 .. -1: a
+    predictor stub that floors the dB value cannot depend on the last bit of a dB transform), NaN and inf samples, schools
+    (27 sandeel, 1 other, 12 / 5000 unused species, -1 ignore) whose last channel straddles the refine thresholds
+    (-70 dB, -40 dB), an undulating seabed, and the schools' bounding boxes (y0, y1, x0, x1).
+    Returns (sv float32, labels int64 [pings, range], seabed int64 [pings], boxes int64 [n, 4])."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    k = rng.integers(-75, 0, size=(4, n_pings, n_range))
+    labels = np.zeros((n_pings, n_range), dtype=np.int64)
+    boxes = []
+    ids = [27, 1, 27, 12, 5000, -1]
+    for i in range(14):
+        w, h = int(rng.integers(6, 30)), int(rng.integers(5, max(6, min(24, n_range // 3))))
+        x0, y0 = int(rng.integers(0, n_pings - w)), int(rng.integers(0, max(1, n_range - h)))
+        labels[x0:x0 + w, y0:y0 + h] = ids[i % len(ids)]
+        k[3, x0:x0 + w, y0:y0 + h] = rng.integers(-73, -37, size=(w, min(h, n_range - y0)))
+        boxes.append((y0, min(y0 + h, n_range), x0, x0 + w))
+    sv = np.power(10.0, (k + 0.5) / 10.0).astype(np.float32)
+    sv[0][rng.random((n_pings, n_range)) < 2e-3] = np.nan
+    sv[3][rng.random((n_pings, n_range)) < 1e-3] = np.inf
+    sv[0][rng.random((n_pings, n_range)) < 5e-4] = np.inf
+    sv[1][rng.random((n_pings, n_range)) < 5e-4] = np.nan
+    x = np.arange(n_pings)
+    seabed = (0.72 * n_range + 0.1 * n_range * np.sin(x / 61.0) + 0.03 * n_range * np.sin(x / 9.0)).astype(np.int64)
+    seabed = np.clip(seabed, 10, n_range - 5)
+    return sv, labels, seabed, np.array(boxes, dtype=np.int64)
+
+
+def eval_stub_logits(db, floor, remainder, arange):
+    """The predictor stub of the whole-survey evaluation fixture, written once for numpy / torch callers: ``db``
+    [B, 4, H, W] dB data as the network would get it; ``floor`` / ``remainder`` / ``arange`` the array library's functions.
+    k = (q0 + 2 q1 + 3 q2 + 5 q3 + row + 3 col) mod 64 with q = floor(dB) -> logits (0, (k - 32) / 8, (k mod 5 - 2) / 4):
+    every value is exact in float32, and the 64 possible sandeel probabilities keep a relative distance of 1.8e-5 from every
+    float16 rounding boundary (checked by tools/make_golden_survey_eval.py) -- some 30 times the error of a float32 softmax
+    (an exp within 2 ulp, two additions, one division: < 6e-7) -- so every float32 softmax rounds them to the same float16."""
+    B, C, H, W = db.shape
+    q = floor(db)
+    k = q[:, 0] + 2 * q[:, 1] + 3 * q[:, 2] + 5 * q[:, 3] + arange(H).reshape(1, H, 1) + 3 * arange(W).reshape(1, 1, W)
+    k = remainder(k, 64)
+    return k * 0, (k - 32) / 8, (remainder(k, 5) - 2) / 4
 
 
 def linear_predictor(data):
