@@ -1123,7 +1123,9 @@ class UNetEngine:
     # the backward pass.
     eval_two_streams = os.environ.get("CRIMAC_EVAL_STREAMS", "1") != "0"
 
-    def _forward_eval_two_streams(self, x, softmax):
+    def _eval_split(self, B, H, W, run_half):
+        """``run_half(lo, hi, out)`` computes batch rows [lo, hi) into ``out`` = logits[lo:hi]: the first half on the
+        caller's stream, the second on the side stream (uneven halves allowed)."""
         # (a stream of its own: the backward pass's side-stream logic keys on self._side, which must stay None when
         # CRIMAC_WGRAD_STREAM=0 asks for a serialized backward pass or under gloo rehearsals)
         if self._eval_side is None:
@@ -1131,7 +1133,6 @@ class UNetEngine:
             self._eval_events = [torch.cuda.Event() for _ in range(8)]
             self._eval_i = 0
         side = self._eval_side
-        B, _, H, W = x.shape
         h = B // 2
         self._check_versions()
         self._pack_eval()                              # (on the caller's stream, before either half starts)
@@ -1141,17 +1142,23 @@ class UNetEngine:
         ev.record()
         try:
             self._buf_prefix = "h0."
-            xin, _, _, _ = self._input(x[:h])
-            self.forward_nhwc(xin, h, H, W, False, softmax, out=logits[:h])
+            run_half(0, h, logits[:h])
             self._buf_prefix = "h1."
             with torch.cuda.stream(side):
                 side.wait_event(ev)
-                xin, _, _, _ = self._input(x[h:])
-                self.forward_nhwc(xin, B - h, H, W, False, softmax, out=logits[h:])
+                run_half(h, B, logits[h:])
         finally:
             self._buf_prefix = ""
         torch.cuda.current_stream().wait_stream(side)
         return logits
+
+    def _forward_eval_two_streams(self, x, softmax):
+        B, _, H, W = x.shape
+
+        def run_half(lo, hi, out):
+            xin, _, _, _ = self._input(x[lo:hi])
+            self.forward_nhwc(xin, hi - lo, H, W, False, softmax, out=out)
+        return self._eval_split(B, H, W, run_half)
 
     @_on_device
     def forward_nhwc_eval_split(self, xin, B, H, W, softmax=False):
@@ -1160,29 +1167,10 @@ class UNetEngine:
         self.bind()
         if not (self.eval_two_streams and B >= 16 and not self._gloo_ranks() and not self.lmi):
             return self.forward_nhwc(xin, B, H, W, False, softmax)
-        if self._eval_side is None:
-            self._eval_side = torch.cuda.Stream(device=self.device)
-            self._eval_events = [torch.cuda.Event() for _ in range(8)]
-            self._eval_i = 0
-        side = self._eval_side
-        h = B // 2
-        self._check_versions()
-        self._pack_eval()
-        logits = torch.empty((B, self.n_classes, H, W), dtype=torch.float32, device=self.device)
-        ev = self._eval_events[self._eval_i % len(self._eval_events)]
-        self._eval_i += 1
-        ev.record()
-        try:
-            self._buf_prefix = "h0."
-            self.forward_nhwc(xin[:h * H * W], h, H, W, False, softmax, out=logits[:h])
-            self._buf_prefix = "h1."
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                self.forward_nhwc(xin[h * H * W:], B - h, H, W, False, softmax, out=logits[h:])
-        finally:
-            self._buf_prefix = ""
-        torch.cuda.current_stream().wait_stream(side)
-        return logits
+
+        def run_half(lo, hi, out):
+            self.forward_nhwc(xin[lo * H * W:hi * H * W], hi - lo, H, W, False, softmax, out=out)
+        return self._eval_split(B, H, W, run_half)
 
     @_on_device
     def forward_nhwc(self, xin, B, H, W, training, softmax=False, out=None, meta=None):

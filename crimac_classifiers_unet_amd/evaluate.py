@@ -102,11 +102,11 @@ def validate_model_survey_memm(readers, segpipe, meta_channels, patch_size, patc
         import torch
 
         from . import parallel
-        from .tiled_inference import PR_BINS, _dist_rank_world, evaluate_echogram_memm, finish_histograms
+        from .tiled_inference import PR_BINS, evaluate_echogram_memm, finish_histograms
         if not segpipe.model_is_loaded:
             segpipe.load_model_params()
         hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=segpipe.device)
-        rank, world = _dist_rank_world()
+        rank, world = parallel.rank_world()
         for i in parallel.shard_indices(len(readers), rank, world):
             evaluate_echogram_memm(readers[i], segpipe, patch_size, patch_overlap, batch_size, eval_mode=eval_mode,
                                    meta_channels=meta_channels or None, hist=hist)

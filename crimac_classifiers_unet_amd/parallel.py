@@ -171,6 +171,13 @@ class GradSync:
         return self.finish()
 
 
+def rank_world(group=None):
+    """(rank, world size) of this process; (0, 1) when torch.distributed is unavailable, not initialised or of size 1."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        return dist.get_rank(group), dist.get_world_size(group)
+    return 0, 1
+
+
 def shard_indices(n_items, rank, world):
     """Indices of the items (patches) rank ``rank`` owns: round-robin ``p % world == rank``."""
     return list(range(rank, n_items, world))
@@ -182,9 +189,9 @@ def gather_shards(local, n_items, group=None):
     ``local``: [n_local, ...] results for ``shard_indices(n_items, rank, world)``; every rank gets
     the full [n_items, ...] tensor.  Ranks with one item fewer are padded for the collective.
     """
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+    rank, world = rank_world(group)
+    if world == 1:
         return local
-    world, rank = dist.get_world_size(group), dist.get_rank(group)
     n_max = (n_items + world - 1) // world
     pad = torch.zeros((n_max,) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
     pad[: local.shape[0]] = local
@@ -199,6 +206,6 @@ def gather_shards(local, n_items, group=None):
 
 def all_reduce_scalars(t, group=None):
     """Sum a small tensor (loss numerator/denominator) over ranks in place."""
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+    if rank_world(group)[1] > 1:
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
     return t

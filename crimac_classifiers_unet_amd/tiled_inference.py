@@ -26,6 +26,10 @@ that a caller appends with the reference's ``create_xarray_ds_predictions`` / ``
 """
 from __future__ import annotations
 
+import time
+from concurrent.futures import ThreadPoolExecutor
+from contextlib import contextmanager
+
 import numpy as np
 import torch
 
@@ -173,25 +177,10 @@ class ChunkPredictor:
         eng = self.engine
         eng.bind()
         ph, pw = self.patch_size[1], self.patch_size[0]
-        C = self.data.shape[0]
-        world, rank = 1, 0
-        if share_patches and torch.distributed.is_available() and torch.distributed.is_initialized():
-            world, rank = torch.distributed.get_world_size(), torch.distributed.get_rank()
+        rank, world = parallel.rank_world() if share_patches else (0, 1)
         mine = parallel.shard_indices(len(grid), rank, world)
         memm = self.flavour == "memm"
-        early = not eng.lmi and eng.in_channels > C       # metadata planes as extra input channels
-        ms = self.meta_source
-        if early:
-            if ms is None:
-                raise ValueError(f"the model takes {eng.in_channels} input channels and the chunk has {C} data planes: "
-                                 "an early-injection model needs the metadata planes, set ChunkPredictor.meta_source "
-                                 "(MetaSource.from_echogram(...))")
-            if ms.n_planes != eng.in_channels - C:
-                raise ValueError(f"the model takes {eng.in_channels - C} metadata input channels, meta_source builds "
-                                 f"{ms.n_planes}")
-            if not memm:
-                raise NotImplementedError("metadata input channels: memm flavour only (the reference's preload path "
-                                          "builds no metadata, batch/dataset.py:210-216)")
+        self._check_meta()
         step = max(self.batch_size, INTERNAL_BATCH) if predict_fn is None else self.batch_size
         for b0 in range(0, len(mine), step):
             idx = mine[b0:b0 + step]
@@ -199,29 +188,12 @@ class ChunkPredictor:
             if centres_dev is not None and world == 1:
                 cen_d, loc_d = centres_dev[0, b0:b0 + P], centres_dev[1, b0:b0 + P]
             else:
-                cen = np.asarray(grid)[idx].astype(np.int32)
-                local = cen.copy()
-                local[:, 1] -= self.data_ping0
-                both = torch.from_numpy(np.ascontiguousarray(np.stack([cen, local]))).to(self.data.device)
-                cen_d, loc_d = both[0], both[1]
-            x = eng._buf("tiled.x", (P * ph * pw, 16))
-            if early:       # + the metadata planes in channels C.., and db_with_limits_scaled (transforms.py:57-64)
-                call("crimac_gather_patches_memm_meta", eng.prec, ptr(self.data), C, self.data.shape[1], self.n_range,
-                     ptr(loc_d), P, ph, pw, ptr(x), 16, ptr(self.labels), 1, ms.flags, ms.portion_year,
-                     ptr(ms.portion_day), ms.portion_day.numel(), ptr(ms.time_diff), ms.time_diff.numel(),
-                     ptr(ms.seabed), ms.seabed.numel(), ptr(cen_d.contiguous()))
-            elif memm:
-                call("crimac_gather_patches_memm", eng.prec, ptr(self.data), C, self.data.shape[1], self.n_range,
-                     ptr(loc_d), P, ph, pw, ptr(x), 16, ptr(self.labels))
-            else:
-                call("crimac_gather_patches", eng.prec, ptr(self.data), C, self.data.shape[1], self.n_range,
-                     ptr(loc_d), P, ph, pw, ptr(x), 16)
+                cen_d, loc_d = self._centres(np.asarray(grid)[idx])
+            x = self._gather(cen_d, loc_d, P)
             if predict_fn is not None:
                 probs = predict_fn(x, P, ph, pw)
             elif eng.lmi:
-                if self.meta_source is None:
-                    raise ValueError("a UNet_LateMetInject model needs the metadata planes: set ChunkPredictor.meta_source "
-                                     "(MetaSource.from_echogram(...))")
+                self._need_meta_source()
                 meta = self.meta_source.planes(cen_d.contiguous(), self.patch_size)
                 probs = eng.forward_nhwc(x, P, ph, pw, False, softmax=True, meta=meta)
             else:
@@ -236,11 +208,13 @@ class ChunkPredictor:
             torch.distributed.all_reduce(self.out)      # interiors are disjoint: sum == union (exact in fp16 too)
         return self.out
 
-    def _check_meta(self, C):
-        """Early-injection models (metadata planes as extra input channels): the conditions of ``predict``."""
-        eng, ms = self.engine, self.meta_source
-        early = not eng.lmi and eng.in_channels > C
-        if early:
+    def _early(self):       # metadata planes as extra input channels
+        return not self.engine.lmi and self.engine.in_channels > self.data.shape[0]
+
+    def _check_meta(self):
+        """Early-injection models: what the chunk must bring along."""
+        eng, ms, C = self.engine, self.meta_source, self.data.shape[0]
+        if self._early():
             if ms is None:
                 raise ValueError(f"the model takes {eng.in_channels} input channels and the chunk has {C} data planes: "
                                  "an early-injection model needs the metadata planes, set ChunkPredictor.meta_source "
@@ -251,7 +225,41 @@ class ChunkPredictor:
             if self.flavour != "memm":
                 raise NotImplementedError("metadata input channels: memm flavour only (the reference's preload path "
                                           "builds no metadata, batch/dataset.py:210-216)")
-        return early
+
+    def _need_meta_source(self):
+        if self.meta_source is None:
+            raise ValueError("a UNet_LateMetInject model needs the metadata planes: set ChunkPredictor.meta_source "
+                             "(MetaSource.from_echogram(...))")
+
+    def _centres(self, cen):
+        """Grid rows [P, 2] (global centres) -> int32 [P, 2] (global centres, centres relative to the data slice) on the
+        device, in one upload."""
+        cen = np.asarray(cen).astype(np.int32)
+        local = cen.copy()
+        local[:, 1] -= self.data_ping0
+        both = torch.from_numpy(np.ascontiguousarray(np.stack([cen, local]))).to(self.data.device)
+        return both[0], both[1]
+
+    def _gather(self, cen_d, loc_d, P):
+        """The network input of a batch of P patches, [P*ph*pw, 16] in the engine's storage type, cropped from the chunk by
+        the gather kernel of its kind: zarr -- the data planes through db_with_limits; memm -- + set_data_border_value by
+        the raw annotation ids; early injection -- + the metadata planes in channels C.., and db_with_limits_scaled
+        (transforms.py:57-64)."""
+        eng, ms = self.engine, self.meta_source
+        ph, pw = self.patch_size[1], self.patch_size[0]
+        C, Wd = self.data.shape[0], self.data.shape[1]
+        x = eng._buf("tiled.x", (P * ph * pw, 16))
+        if self._early():
+            call("crimac_gather_patches_memm_meta", eng.prec, ptr(self.data), C, Wd, self.n_range, ptr(loc_d), P, ph, pw,
+                 ptr(x), 16, ptr(self.labels), 1, ms.flags, ms.portion_year, ptr(ms.portion_day), ms.portion_day.numel(),
+                 ptr(ms.time_diff), ms.time_diff.numel(), ptr(ms.seabed), ms.seabed.numel(), ptr(cen_d.contiguous()))
+        elif self.flavour == "memm":
+            call("crimac_gather_patches_memm", eng.prec, ptr(self.data), C, Wd, self.n_range, ptr(loc_d), P, ph, pw,
+                 ptr(x), 16, ptr(self.labels))
+        else:
+            call("crimac_gather_patches", eng.prec, ptr(self.data), C, Wd, self.n_range, ptr(loc_d), P, ph, pw,
+                 ptr(x), 16)
+        return x
 
     def evaluate(self, grid, hist, eval_mode="all", boxes=None, predict_fn=None, on_batch=None):
         """Test-set evaluation of the patches of ``grid`` ([P, 2] global centres) on a ``wide`` chunk: what the reference's
@@ -286,23 +294,18 @@ class ChunkPredictor:
         if tuple(self.labels.shape) != (Wd, self.n_range):
             raise ValueError(f"labels {tuple(self.labels.shape)} do not cover the data extent {(Wd, self.n_range)}")
         memm = self.flavour == "memm"
-        early = self._check_meta(C)
-        ms = self.meta_source
-        if eng.lmi and ms is None:
-            raise ValueError("a UNet_LateMetInject model needs the metadata planes: set ChunkPredictor.meta_source "
-                             "(MetaSource.from_echogram(...))")
+        self._check_meta()
+        early = self._early()
+        if eng.lmi:
+            self._need_meta_source()
         if (eng.lmi or early) and not memm:
             raise NotImplementedError("metadata planes: memm flavour only (the zarr path builds none)")
         grid = np.asarray(grid)
         step = max(self.batch_size, INTERNAL_BATCH) if predict_fn is None else self.batch_size
-        dev = self.data.device
         for b0 in range(0, len(grid), step):
             cen = grid[b0:b0 + step].astype(np.int32)
             P = len(cen)
-            local = cen.copy()
-            local[:, 1] -= self.data_ping0
-            both = torch.from_numpy(np.ascontiguousarray(np.stack([cen, local]))).to(dev)
-            cen_d, loc_d = both[0].contiguous(), both[1].contiguous()
+            cen_d, loc_d = self._centres(cen)
             raw = eng._buf("eval.raw", (P, C, ph, pw), torch.float32)
             lab = eng._buf("eval.lab", (P, ph, pw), torch.int16)
             call("crimac_gather_eval_crops", ptr(self.data), C, Wd, self.n_range, ptr(self.labels), ptr(loc_d), P, ph,
@@ -316,17 +319,9 @@ class ChunkPredictor:
                     raise NotImplementedError(f"eval_mode={eval_mode!r} with metadata planes on the tiled path; use "
                                               "eval_mode='all' or the DataLoader path")
             elif memm:
-                x = eng._buf("tiled.x", (P * ph * pw, 16))
-                if early:
-                    call("crimac_gather_patches_memm_meta", eng.prec, ptr(self.data), C, Wd, self.n_range, ptr(loc_d), P,
-                         ph, pw, ptr(x), 16, ptr(self.labels), 1, ms.flags, ms.portion_year, ptr(ms.portion_day),
-                         ms.portion_day.numel(), ptr(ms.time_diff), ms.time_diff.numel(), ptr(ms.seabed),
-                         ms.seabed.numel(), ptr(cen_d))
-                else:
-                    call("crimac_gather_patches_memm", eng.prec, ptr(self.data), C, Wd, self.n_range, ptr(loc_d), P, ph,
-                         pw, ptr(x), 16, ptr(self.labels))
+                x = self._gather(cen_d, loc_d, P)
                 if eng.lmi:
-                    meta = ms.planes(cen_d, self.patch_size)
+                    meta = self.meta_source.planes(cen_d, self.patch_size)
             logits, labels_t = raw_crops_to_logits(
                 eng, raw, lab, cen_d.long().contiguous(), thr_channel=C - 1, seabed=self.seabed,
                 seabed_ping0=self.seabed_ping0, seabed_pings=0 if self.seabed is None else self.seabed.numel(),
@@ -503,6 +498,25 @@ def release_staging():
     _STAGING.clear()
 
 
+@contextmanager
+def _staging(key, factory):
+    """The staging buffers (pinned host + device) of one survey flow, kept between surveys of the same geometry:
+    ``factory()`` builds the dict of a new set.  Busy while the ``with`` block runs."""
+    bufs = _STAGING.get(key)
+    if bufs is None or bufs["busy"]:     # (busy: another flow over the same geometry is still running)
+        fresh = dict(factory(), busy=False)
+        if bufs is None:
+            _STAGING.clear()             # (one geometry at a time: the buffers are large)
+            _STAGING[key] = fresh
+        bufs = fresh
+    bufs["busy"] = True
+    try:
+        yield bufs
+    finally:
+        torch.cuda.current_stream().synchronize()     # (nothing of this survey still reads or writes the staging)
+        bufs["busy"] = False
+
+
 def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings,
                    start_ping=0, labels_available=True, out_dtype=np.float32, stats=None, predict_fn=None,
                    shard="chunk", ordered_to_rank0=False, **kwargs):
@@ -536,7 +550,6 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
     (numpy / zarr I/O, no GPU calls) while the GPU uploads (copy stream), gathers, predicts and scatters chunk i, and
     the result of chunk i-1 comes back through a pinned buffer (asynchronous D2H) before it is handed to the caller.
     """
-    from concurrent.futures import ThreadPoolExecutor
     n_pings, n_range = reader.shape
     dev = segpipe.device
     model = segpipe.model.to(dev).eval()
@@ -546,14 +559,13 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
     if shard not in ("chunk", "patch"):
         raise ValueError(f"predict_survey: shard must be 'chunk' or 'patch', got {shard!r}")
     share_patches = shard == "patch"
-    dist = torch.distributed
-    multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    rank, world = parallel.rank_world()
+    multi = world > 1
     if ordered_to_rank0 and share_patches:
         raise ValueError("predict_survey: ordered_to_rank0 belongs to shard='chunk' (with shard='patch' every rank already "
                          "yields every chunk)")
     ordered = multi and not share_patches and bool(ordered_to_rank0)
     all_chunks = chunks
-    rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
     if multi and not share_patches:
         chunks = chunks[rank::world]
     sender = ordered and rank != 0
@@ -573,10 +585,8 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
     n_misc = (widest + 2 * halo) + 4 * max_patches            # int32: seabed | global centres | slice-relative centres
     # staging (pinned host + device) is kept between surveys of the same geometry: page-locking 3 x 75 MB + the result
     # buffers costs 10-20 ms per call, a tenth of a 65536-ping survey
-    key = (str(dev), n_data, widest, n_range, n_misc, f16)
-    bufs = _STAGING.get(key)
-    if bufs is None or bufs["busy"]:     # (busy: another generator over the same geometry is still running)
-        fresh = {
+    def new_staging():
+        return {
             "stage_data": [torch.empty(n_data, dtype=torch.float32).pin_memory() for _ in range(NS)],
             "stage_lab": [torch.empty((widest, n_range), dtype=torch.int16).pin_memory() for _ in range(NS)],
             "stage_misc": [torch.empty(n_misc, dtype=torch.int32).pin_memory() for _ in range(NS)],
@@ -585,144 +595,157 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
             "dev_lab": [torch.empty((widest, n_range), dtype=torch.int16, device=dev) for _ in range(2)],
             "pinned": [torch.empty(2 * n_range * widest, dtype=torch.float16 if f16 else torch.float32).pin_memory()
                        for _ in range(2)],
-            "busy": False,
         }
-        if bufs is None:
-            _STAGING.clear()             # (one geometry at a time: the buffers are large)
-            _STAGING[key] = fresh
-        bufs = fresh
-    bufs["busy"] = True
-    stage_data, stage_lab, stage_misc = bufs["stage_data"], bufs["stage_lab"], bufs["stage_misc"]
-    dev_misc = bufs["dev_misc"]
-    uploaded = [torch.cuda.Event() for _ in range(NS)]        # host slot k may be overwritten once this has passed
-    # device side: two resident chunk buffers; chunk i is uploaded on the copy stream while chunk i-1 computes
-    dev_data, dev_lab = bufs["dev_data"], bufs["dev_lab"]
-    computed = [torch.cuda.Event() for _ in range(2)]         # device slot may be overwritten once this has passed
-    copy_stream = torch.cuda.Stream(device=dev)
 
-    import time as _time
-    tick = _time.perf_counter
+    with _staging((str(dev), n_data, widest, n_range, n_misc, f16), new_staging) as bufs:
+        stage_data, stage_lab, stage_misc = bufs["stage_data"], bufs["stage_lab"], bufs["stage_misc"]
+        dev_misc = bufs["dev_misc"]
+        uploaded = [torch.cuda.Event() for _ in range(NS)]        # host slot k may be overwritten once this has passed
+        # device side: two resident chunk buffers; chunk i is uploaded on the copy stream while chunk i-1 computes
+        dev_data, dev_lab = bufs["dev_data"], bufs["dev_lab"]
+        computed = [torch.cuda.Event() for _ in range(2)]         # device slot may be overwritten once this has passed
+        copy_stream = torch.cuda.Stream(device=dev)
 
-    def note(key, t0):
-        if stats is not None:
-            stats.setdefault(key, []).append(tick() - t0)
+        tick = time.perf_counter
 
-    def fetch(i, s, e):
-        t0 = tick()
-        k = i % NS
-        # ping extent of the data a patch of the chunk can touch (dataset.py:175-177): the patch columns depend on
-        # (s, e) only, so the seabed of [lo, hi) -- which contains [s, e) -- is read ONCE (the zarr reader derives it from
-        # the full 2-D mask every time, data_reader.py:864-865)
-        xs = np.arange(s - (patch_overlap + 1), e - (patch_overlap + 1), patch_size[0] - 2 * patch_overlap) + patch_size[0] // 2
-        lo = max(0, int(xs[0]) - patch_size[1] // 2)
-        hi = min(n_pings, int(xs[-1]) + patch_size[1] // 2)
-        sb = np.asarray(reader.get_seabed(lo, hi - lo, return_numpy=True)).astype(np.int32)
-        seabed = sb[max(s - lo, 0):e - lo] if lo <= s else np.asarray(reader.get_seabed(s, e - s, return_numpy=True)).astype(np.int32)
-        grid = plan_grid(n_range, int(seabed.max()), s, e, patch_size, patch_overlap)
-        assert lo == max(0, int(grid[0, 1]) - patch_size[1] // 2) and hi == min(n_pings, int(grid[-1, 1]) + patch_size[1] // 2)
-        uploaded[k].synchronize()                                        # (no-op until the slot has been used)
-        data = reader.get_data_slice(idx_ping=lo, n_pings=hi - lo, frequencies=segpipe.frequencies,
-                                     return_numpy=True)
-        d_t = stage_data[k][:n_freq * (hi - lo) * n_range].view(n_freq, hi - lo, n_range)     # contiguous
-        np.copyto(d_t.numpy(), data, casting="same_kind")
-        l_t = None
-        if labels_available:
-            lab = reader.get_label_slice(idx_ping=s, n_pings=e - s, return_numpy=True)
-            l_t = stage_lab[k][:e - s]
-            np.copyto(l_t.numpy(), lab, casting="unsafe")
-        # the seabed of every ping a patch of the chunk can touch (the scatter kernel evaluates the mask from it)
-        sb, mask = seabed_vector_or_mask(reader, s, e, n_range, sb, lo)
-        P = len(grid)
-        assert (hi - lo) + 4 * P <= n_misc, "misc staging too small"
-        m = stage_misc[k].numpy()
-        m[:hi - lo] = sb
-        cen = np.asarray(grid, dtype=np.int32)
-        m[hi - lo:hi - lo + 2 * P] = cen.reshape(-1)
-        loc = cen.copy()
-        loc[:, 1] -= lo
-        m[hi - lo + 2 * P:hi - lo + 4 * P] = loc.reshape(-1)
-        note("fetch_s", t0)
-        return grid, lo, hi, d_t, l_t, stage_misc[k][:hi - lo + 4 * P], mask
+        def note(key, t0):
+            if stats is not None:
+                stats.setdefault(key, []).append(tick() - t0)
 
-    pinned = bufs["pinned"]                      # flat: every chunk's [2, range, e - s] view of it is contiguous
-    events = [torch.cuda.Event() for _ in range(2)]
-    pending = None                      # (s, e, slot) of the chunk whose D2H copy is in flight
-    main = torch.cuda.current_stream()
-    def _loop():
-        nonlocal pending
-        with ThreadPoolExecutor(max_workers=2) as pool:
-            futs = {j: pool.submit(fetch, j, *chunks[j]) for j in range(min(2, len(chunks)))}
-            for i, (s, e) in enumerate(chunks):
-                t0 = tick()
-                grid, lo, hi, d_t, l_t, sb, mask = futs.pop(i).result()
-                note("wait_fetch_s", t0)
-                t0 = tick()
-                if i + 2 < len(chunks):
-                    futs[i + 2] = pool.submit(fetch, i + 2, *chunks[i + 2])
-                slot = i & 1
-                with torch.cuda.stream(copy_stream):
-                    copy_stream.wait_event(computed[slot])                   # chunk i-2 is done with this device slot
-                    d_d = dev_data[slot][:d_t.numel()].view(d_t.shape)
-                    d_d.copy_(d_t, non_blocking=True)
-                    l_d = None
-                    if l_t is not None:
-                        l_d = dev_lab[slot][:e - s]
-                        l_d.copy_(l_t, non_blocking=True)
-                    m_d = dev_misc[slot][:sb.numel()]
-                    m_d.copy_(sb, non_blocking=True)                        # (sb: seabed | centres, pinned)
-                    uploaded[i % NS].record()
-                note("enq_upload_s", t0)
-                t1 = tick()
-                main.wait_stream(copy_stream)
-                P = len(grid)
-                if stats is not None:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record()
-                if mask is None:
-                    cp.load_chunk(d_d, lo, l_d, None, s, e, seabed=m_d[:hi - lo], seabed_ping0=lo)
-                else:                                 # (a mask the vector rule cannot express: uploaded as it is)
-                    cp.load_chunk(d_d, lo, l_d, mask, s, e)
-                note("enq_load_s", t1)
-                t1 = tick()
-                out = cp.predict(grid, predict_fn=predict_fn, centres_dev=m_d[hi - lo:].view(2, P, 2),
-                                 share_patches=share_patches)
-                note("enq_predict_s", t1)
-                if stats is not None:
-                    ev1.record()
-                    stats.setdefault("gpu_events", []).append((ev0, ev1))
-                computed[slot].record()
-                if sender:                            # ordered hand-off: the chunk goes to rank 0, nothing comes back here
-                    hand.send(out)
+        def fetch(i, s, e):
+            t0 = tick()
+            k = i % NS
+            # ping extent of the data a patch of the chunk can touch (dataset.py:175-177): the patch columns depend on
+            # (s, e) only, so the seabed of [lo, hi) -- which contains [s, e) -- is read ONCE (the zarr reader derives it from
+            # the full 2-D mask every time, data_reader.py:864-865)
+            xs = np.arange(s - (patch_overlap + 1), e - (patch_overlap + 1), patch_size[0] - 2 * patch_overlap) + patch_size[0] // 2
+            lo = max(0, int(xs[0]) - patch_size[1] // 2)
+            hi = min(n_pings, int(xs[-1]) + patch_size[1] // 2)
+            sb = np.asarray(reader.get_seabed(lo, hi - lo, return_numpy=True)).astype(np.int32)
+            seabed = sb[max(s - lo, 0):e - lo] if lo <= s else np.asarray(reader.get_seabed(s, e - s, return_numpy=True)).astype(np.int32)
+            grid = plan_grid(n_range, int(seabed.max()), s, e, patch_size, patch_overlap)
+            assert lo == max(0, int(grid[0, 1]) - patch_size[1] // 2) and hi == min(n_pings, int(grid[-1, 1]) + patch_size[1] // 2)
+            uploaded[k].synchronize()                                        # (no-op until the slot has been used)
+            data = reader.get_data_slice(idx_ping=lo, n_pings=hi - lo, frequencies=segpipe.frequencies,
+                                         return_numpy=True)
+            d_t = stage_data[k][:n_freq * (hi - lo) * n_range].view(n_freq, hi - lo, n_range)     # contiguous
+            np.copyto(d_t.numpy(), data, casting="same_kind")
+            l_t = None
+            if labels_available:
+                lab = reader.get_label_slice(idx_ping=s, n_pings=e - s, return_numpy=True)
+                l_t = stage_lab[k][:e - s]
+                np.copyto(l_t.numpy(), lab, casting="unsafe")
+            # the seabed of every ping a patch of the chunk can touch (the scatter kernel evaluates the mask from it)
+            sb, mask = seabed_vector_or_mask(reader, s, e, n_range, sb, lo)
+            P = len(grid)
+            assert (hi - lo) + 4 * P <= n_misc, "misc staging too small"
+            m = stage_misc[k].numpy()
+            m[:hi - lo] = sb
+            cen = np.asarray(grid, dtype=np.int32)
+            m[hi - lo:hi - lo + 2 * P] = cen.reshape(-1)
+            loc = cen.copy()
+            loc[:, 1] -= lo
+            m[hi - lo + 2 * P:hi - lo + 4 * P] = loc.reshape(-1)
+            note("fetch_s", t0)
+            return grid, lo, hi, d_t, l_t, stage_misc[k][:hi - lo + 4 * P], mask
+
+        pinned = bufs["pinned"]                      # flat: every chunk's [2, range, e - s] view of it is contiguous
+        events = [torch.cuda.Event() for _ in range(2)]
+        pending = None                      # (s, e, slot) of the chunk whose D2H copy is in flight
+        main = torch.cuda.current_stream()
+        def _loop():
+            nonlocal pending
+            with ThreadPoolExecutor(max_workers=2) as pool:
+                futs = {j: pool.submit(fetch, j, *chunks[j]) for j in range(min(2, len(chunks)))}
+                for i, (s, e) in enumerate(chunks):
+                    t0 = tick()
+                    grid, lo, hi, d_t, l_t, sb, mask = futs.pop(i).result()
+                    note("wait_fetch_s", t0)
+                    t0 = tick()
+                    if i + 2 < len(chunks):
+                        futs[i + 2] = pool.submit(fetch, i + 2, *chunks[i + 2])
+                    slot = i & 1
+                    with torch.cuda.stream(copy_stream):
+                        copy_stream.wait_event(computed[slot])                   # chunk i-2 is done with this device slot
+                        d_d = dev_data[slot][:d_t.numel()].view(d_t.shape)
+                        d_d.copy_(d_t, non_blocking=True)
+                        l_d = None
+                        if l_t is not None:
+                            l_d = dev_lab[slot][:e - s]
+                            l_d.copy_(l_t, non_blocking=True)
+                        m_d = dev_misc[slot][:sb.numel()]
+                        m_d.copy_(sb, non_blocking=True)                        # (sb: seabed | centres, pinned)
+                        uploaded[i % NS].record()
+                    note("enq_upload_s", t0)
+                    t1 = tick()
+                    main.wait_stream(copy_stream)
+                    P = len(grid)
+                    if stats is not None:
+                        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        ev0.record()
+                    if mask is None:
+                        cp.load_chunk(d_d, lo, l_d, None, s, e, seabed=m_d[:hi - lo], seabed_ping0=lo)
+                    else:                                 # (a mask the vector rule cannot express: uploaded as it is)
+                        cp.load_chunk(d_d, lo, l_d, mask, s, e)
+                    note("enq_load_s", t1)
+                    t1 = tick()
+                    out = cp.predict(grid, predict_fn=predict_fn, centres_dev=m_d[hi - lo:].view(2, P, 2),
+                                     share_patches=share_patches)
+                    note("enq_predict_s", t1)
+                    if stats is not None:
+                        ev1.record()
+                        stats.setdefault("gpu_events", []).append((ev0, ev1))
+                    computed[slot].record()
+                    if sender:                            # ordered hand-off: the chunk goes to rank 0, nothing comes back here
+                        hand.send(out)
+                        note("enqueue_s", t0)
+                        continue
+                    pinned[slot][:out.numel()].view(out.shape).copy_(out, non_blocking=True)
+                    events[slot].record()
                     note("enqueue_s", t0)
-                    continue
-                pinned[slot][:out.numel()].view(out.shape).copy_(out, non_blocking=True)
-                events[slot].record()
-                note("enqueue_s", t0)
-                if pending is not None:
-                    ps, pe, pslot = pending
-                    t0 = tick()
-                    events[pslot].synchronize()
-                    note("wait_gpu_s", t0)
-                    t0 = tick()
-                    res = pinned[pslot][:2 * n_range * (pe - ps)].view(2, n_range, pe - ps).numpy().copy()
-                    note("copy_out_s", t0)
-                    yield ps, pe, res
-                pending = (s, e, slot)
-            if sender:
-                hand.flush()
-                return
-            ps, pe, pslot = pending
-            events[pslot].synchronize()
-            yield ps, pe, pinned[pslot][:2 * n_range * (pe - ps)].view(2, n_range, pe - ps).numpy().copy()
+                    if pending is not None:
+                        ps, pe, pslot = pending
+                        t0 = tick()
+                        events[pslot].synchronize()
+                        note("wait_gpu_s", t0)
+                        t0 = tick()
+                        res = pinned[pslot][:2 * n_range * (pe - ps)].view(2, n_range, pe - ps).numpy().copy()
+                        note("copy_out_s", t0)
+                        yield ps, pe, res
+                    pending = (s, e, slot)
+                if sender:
+                    hand.flush()
+                    return
+                ps, pe, pslot = pending
+                events[pslot].synchronize()
+                yield ps, pe, pinned[pslot][:2 * n_range * (pe - ps)].view(2, n_range, pe - ps).numpy().copy()
 
-    try:
         if ordered and rank == 0:
             yield from hand.merge(_loop())
         else:
             yield from _loop()
-    finally:
-        torch.cuda.current_stream().synchronize()     # (nothing of this survey still reads or writes the staging)
-        bufs["busy"] = False
+
+
+def _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels, out_f16, wide):
+    """One memmap echogram as ONE resident chunk (ping_start 0): the arrays are transposed to the ping-major layout of the
+    gather kernel on the GPU.  Returns (the loaded ``ChunkPredictor``, the seabed vector)."""
+    n_range, n_pings = (int(v) for v in echogram.shape)
+    dev = segpipe.device
+    model = segpipe.model.to(dev).eval()
+    eng = model.infer_engine
+    if not eng.lmi and eng.in_channels > len(segpipe.frequencies) and not meta_channels:
+        raise ValueError(f"the model takes {eng.in_channels} input channels for {len(segpipe.frequencies)} frequencies "
+                         "(metadata planes as input channels): pass meta_channels")
+    seabed = np.asarray(echogram.get_seabed(0, n_pings)).astype(np.int32)
+    data = torch.stack([torch.as_tensor(np.ascontiguousarray(m, dtype=np.float32))
+                        for m in echogram.data_memmaps(segpipe.frequencies)]).to(dev)
+    data = data.permute(0, 2, 1).contiguous()                                     # [C, pings, range]
+    labels = torch.as_tensor(np.ascontiguousarray(echogram.label_memmap()).astype(np.int16)).to(dev).t().contiguous()
+    cp = ChunkPredictor(model, n_range, patch_size, patch_overlap, batch_size, out_f16=out_f16)
+    if meta_channels:                    # metadata planes (late or early injection): built on the GPU, per batch of crops
+        cp.meta_source = MetaSource.from_echogram(echogram, meta_channels, dev)
+    cp.load_chunk(data, 0, labels, None, 0, n_pings, seabed=seabed, flavour="memm", wide=wide)
+    return cp, seabed
 
 
 def predict_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, predict_fn=None, meta_channels=None,
@@ -737,26 +760,9 @@ def predict_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_si
     whose input channels outnumber the frequencies (early injection) -- its extra input channels, gathered into the
     crop with the data planes (which then take db_with_limits_scaled, transforms.py:57-64).
     """
-    n_range, n_pings = echogram.shape
-    model = segpipe.model.to(segpipe.device).eval()
-    dev = segpipe.device
-    eng = model.infer_engine
-    if not eng.lmi and eng.in_channels > len(segpipe.frequencies) and not meta_channels:
-        raise ValueError(f"the model takes {eng.in_channels} input channels for {len(segpipe.frequencies)} frequencies "
-                         "(metadata planes as input channels): pass meta_channels")
-    seabed = np.asarray(echogram.get_seabed(0, n_pings)).astype(np.int32)
-    grid = plan_grid(n_range, int(seabed.max()), 0, n_pings, patch_size, patch_overlap)
-    if n_range <= patch_size[1]:
-        grid = grid.copy()
-        grid[:, 0] = n_range // 2            # get_crop_memmap (dataset.py:256-258): window covers the water column
-    data = torch.stack([torch.as_tensor(np.ascontiguousarray(m, dtype=np.float32))
-                        for m in echogram.data_memmaps(segpipe.frequencies)]).to(dev)
-    data = data.permute(0, 2, 1).contiguous()                                     # [C, pings, range]
-    labels = torch.as_tensor(np.ascontiguousarray(echogram.label_memmap()).astype(np.int16)).to(dev).t().contiguous()
-    cp = ChunkPredictor(model, n_range, patch_size, patch_overlap, batch_size, out_f16=True)
-    if meta_channels:                    # metadata planes (late or early injection): built on the GPU, per batch of crops
-        cp.meta_source = MetaSource.from_echogram(echogram, meta_channels, dev)
-    cp.load_chunk(data, 0, labels, None, 0, n_pings, seabed=seabed, flavour="memm")
+    cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
+                                     out_f16=True, wide=False)
+    grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
     out = cp.predict(grid, predict_fn=predict_fn)
     return out.cpu().numpy().astype(np.float64)
 
@@ -798,20 +804,12 @@ def plan_eval_chunks(grid, n_pings, patch_size, preload_n_pings):
 def finish_histograms(hist, all_reduce=True):
     """int32 [2, 16384] on the GPU -> (hist_pos, hist_neg) int64 numpy; with several ranks the ONE collective of the flow
     (the histograms are the metric's sufficient statistic, as in ``SegPipe.get_pr_histograms_dataloader``)."""
-    dist = torch.distributed
-    if all_reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        dist.all_reduce(hist)
+    if all_reduce and parallel.rank_world()[1] > 1:
+        torch.distributed.all_reduce(hist)
     h = hist.cpu().numpy().astype(np.int64)
     if h[:, PR_BINS - 1].any():           # CRIMAC_PR_NAN_BIN: sklearn raises on NaN scores as well
         raise ValueError("Input contains NaN (sandeel probabilities of the validation set)")
     return h[0], h[1]
-
-
-def _dist_rank_world():
-    dist = torch.distributed
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        return dist.get_rank(), dist.get_world_size()
-    return 0, 1
 
 
 def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, eval_mode="all",
@@ -829,8 +827,6 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
     histograms all-reduced once at the end; every rank returns the survey's histograms.
     ``reader``: the reference's zarr reader API (shape, get_data_slice, get_label_slice, get_seabed, get_seabed_mask;
     get_object_bounding_boxes for ``eval_mode`` 'region' / 'trace')."""
-    from concurrent.futures import ThreadPoolExecutor
-    import time as _time
     n_pings, n_range = (int(v) for v in reader.shape)
     dev = segpipe.device
     model = segpipe.model.to(dev).eval()
@@ -845,7 +841,7 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
     sb_all = np.asarray(reader.get_seabed(0, n_pings, return_numpy=True)).astype(np.int32)
     grid = plan_eval_grid(n_range, sb_all, n_pings, patch_size, patch_overlap)
     chunks = plan_eval_chunks(grid, n_pings, patch_size, preload_n_pings)
-    rank, world = _dist_rank_world()
+    rank, world = parallel.rank_world()
     mine = [chunks[i] for i in parallel.shard_indices(len(chunks), rank, world)]
     hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=dev)
     if stats is not None:
@@ -855,23 +851,17 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
         return finish_histograms(hist)
     widest = max(hi - lo for _, lo, hi in mine)
     NS = 2
-    key = ("eval", str(dev), n_freq, widest, n_range)
-    bufs = _STAGING.get(key)
-    if bufs is None or bufs["busy"]:
-        fresh = {
+
+    def new_staging():
+        return {
             "stage_data": [torch.empty(n_freq * widest * n_range, dtype=torch.float32).pin_memory() for _ in range(NS)],
             "stage_lab": [torch.empty(widest * n_range, dtype=torch.int16).pin_memory() for _ in range(NS)],
             "stage_sb": [torch.empty(widest, dtype=torch.int32).pin_memory() for _ in range(NS)],
             "dev_data": [torch.empty(n_freq * widest * n_range, dtype=torch.float32, device=dev) for _ in range(2)],
             "dev_lab": [torch.empty(widest * n_range, dtype=torch.int16, device=dev) for _ in range(2)],
             "dev_sb": [torch.empty(widest, dtype=torch.int32, device=dev) for _ in range(2)],
-            "busy": False,
         }
-        if bufs is None:
-            _STAGING.clear()             # (one geometry at a time: the buffers are large)
-            _STAGING[key] = fresh
-        bufs = fresh
-    bufs["busy"] = True
+
     uploaded = [torch.cuda.Event() for _ in range(NS)]        # host slot may be overwritten once this has passed
     computed = [torch.cuda.Event() for _ in range(2)]         # device slot may be overwritten once this has passed
     copy_stream = torch.cuda.Stream(device=dev)
@@ -894,8 +884,8 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
         s_t.numpy()[:] = sb[lo:hi]
         return d_t, l_t, s_t, mask
 
-    t_start = _time.perf_counter()
-    try:
+    t_start = time.perf_counter()
+    with _staging(("eval", str(dev), n_freq, widest, n_range), new_staging) as bufs:
         with ThreadPoolExecutor(max_workers=1) as pool:
             fut = pool.submit(fetch, 0, mine[0][1], mine[0][2])
             for i, (idx, lo, hi) in enumerate(mine):
@@ -920,11 +910,8 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
                 cp.evaluate(grid[idx], hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch)
                 computed[slot].record()
         out = finish_histograms(hist)
-    finally:
-        torch.cuda.current_stream().synchronize()     # (nothing of this survey still reads or writes the staging)
-        bufs["busy"] = False
     if stats is not None:
-        stats["seconds"] = _time.perf_counter() - t_start
+        stats["seconds"] = time.perf_counter() - t_start
     return out
 
 
@@ -937,26 +924,13 @@ def evaluate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_s
     ``hist`` (int32 [2, 16384] on the GPU): accumulate into it and return it -- a survey of several echograms, whose caller
     finishes with ``finish_histograms``; None: returns this echogram's ``(hist_pos, hist_neg)`` int64 numpy (no
     collective: every rank that calls it evaluates the echogram it passes)."""
-    n_range, n_pings = (int(v) for v in echogram.shape)
+    cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
+                                     out_f16=False, wide=True)
     dev = segpipe.device
-    model = segpipe.model.to(dev).eval()
-    eng = model.infer_engine
-    if not eng.lmi and eng.in_channels > len(segpipe.frequencies) and not meta_channels:
-        raise ValueError(f"the model takes {eng.in_channels} input channels for {len(segpipe.frequencies)} frequencies "
-                         "(metadata planes as input channels): pass meta_channels")
     boxes = eval_boxes(echogram, eval_mode, extend_size)
     if boxes is not None:
         boxes = torch.from_numpy(boxes).to(dev)
-    seabed = np.asarray(echogram.get_seabed(0, n_pings)).astype(np.int32)
-    grid = plan_eval_grid(n_range, seabed, n_pings, patch_size, patch_overlap, memm=True)
-    data = torch.stack([torch.as_tensor(np.ascontiguousarray(m, dtype=np.float32))
-                        for m in echogram.data_memmaps(segpipe.frequencies)]).to(dev)
-    data = data.permute(0, 2, 1).contiguous()                                     # [C, pings, range]
-    labels = torch.as_tensor(np.ascontiguousarray(echogram.label_memmap()).astype(np.int16)).to(dev).t().contiguous()
-    cp = ChunkPredictor(model, n_range, patch_size, patch_overlap, batch_size)
-    if meta_channels:
-        cp.meta_source = MetaSource.from_echogram(echogram, meta_channels, dev)
-    cp.load_chunk(data, 0, labels, None, 0, n_pings, seabed=seabed, flavour="memm", wide=True)
+    grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
     own = hist is None
     if own:
         hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=dev)
