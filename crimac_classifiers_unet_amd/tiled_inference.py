@@ -86,9 +86,10 @@ class MetaSource:
         self.seabed = dev(seabed, np.int64)
 
     @classmethod
-    def from_echogram(cls, echogram, meta_channels, device):
+    def from_echogram(cls, echogram, meta_channels, device, seabed=None):
+        """``seabed``: the vector to build the depth planes from when it is not the reader's own ``_seabed``."""
         return cls(meta_channels, echogram.portion_of_year_scalar, echogram.portion_of_day_vector,
-                   echogram.time_vector_diff, echogram._seabed, device)
+                   echogram.time_vector_diff, echogram._seabed if seabed is None else seabed, device)
 
     def planes(self, centres_dev, patch_size):
         """centres_dev int32 [P, 2] (range idx, ping idx) on the GPU -> float32 [P, Cm, H, W]."""
@@ -726,7 +727,136 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
             yield from _loop()
 
 
-def _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels, out_f16, wide):
+# ---- seabed line of a memmap echogram without a stored seabed.npy (Echogram.get_seabed, data_reader.py:433-507) ---------
+SEABED_REPAIR_THRESHOLD = -8       # data_reader.py:471: standardised log column maximum below which a ping is a drop-out
+SEABED_REPAIR_EDGE = 2             # data_reader.py:474 (i_edge)
+SEABED_CHUNK_PINGS = 4096          # pings uploaded per launch by estimate_seabed (1000 rows x 4 frequencies: 66 MB)
+
+
+def seabed_rows(n_range):
+    """(n, a) of data_reader.py:461-463: the rows at the top that the argmax skips, and the upward shift of the line."""
+    return 10 + int(0.05 * n_range), int(0.004 * n_range)
+
+
+def seabed_columns(chunk, has_left, has_right, n, idx, colmax, ping0=0):
+    """``crimac_seabed_columns`` on one chunk: ``chunk`` float32 [F, Pc, R] on the GPU (up to one halo ping on each side,
+    flagged by ``has_left`` / ``has_right``); writes the owned pings' argmax rows (relative to row ``n``) and column
+    maxima into ``idx`` int32 / ``colmax`` float32 [F, P] from ping ``ping0`` on."""
+    F, Pc, R = (int(v) for v in chunk.shape)
+    owned = Pc - int(bool(has_left)) - int(bool(has_right))
+    if chunk.dtype != torch.float32 or not chunk.is_contiguous():
+        raise ValueError("seabed_columns: the chunk is a contiguous float32 [F, pings, range] tensor")
+    if idx.dtype != torch.int32 or colmax.dtype != torch.float32 or idx.shape != colmax.shape or idx.shape[0] != F \
+            or not idx.is_contiguous() or not colmax.is_contiguous():
+        raise ValueError("seabed_columns: idx int32 / colmax float32, both contiguous [F, P]")
+    if ping0 < 0 or ping0 + owned > idx.shape[1]:
+        raise ValueError(f"seabed_columns: pings [{ping0}, {ping0 + owned}) outside the result's {idx.shape[1]}")
+    with torch.cuda.device(chunk.device):
+        call("crimac_seabed_columns", ptr(chunk), F, Pc, R, int(bool(has_left)), int(bool(has_right)), int(n),
+             ptr(idx, ping0), ptr(colmax, ping0), int(idx.shape[1]))
+
+
+def finish_seabed(idx, colmax, n_range, runs=None):
+    """The host end of ``Echogram.get_seabed`` (data_reader.py:466-504) from the per-column results: ``idx`` int [F, P]
+    (argmax rows relative to row n), ``colmax`` float32 [F, P] -> the seabed vector int64 [P].  It needs every ping at
+    once (the mean and the standard deviation run over the whole echogram) and works in the reference's dtypes, with the
+    reference's own numpy calls on arrays of the reference's layout ([P, F], C order): float32 ``log(1e-10 + max)``
+    standardised per frequency, float64 rows, ``np.rint(np.median(., axis=1))``.  Drop-out runs (standardised value
+    < -8) are repaired per run as the reference's per-ping loop does (:481-502), quirks included: the scan starts at
+    index 2 and ends before P - 2, so a run is not seen before index 2 (one that covers index 2 counts from there and takes
+    the value BEHIND it), a run reaching P - 2 or further takes the value in front of it, every other run the mean of
+    its two neighbours.  ``runs`` (a list): receives ``(frequency, idx_0, idx_1, case)`` of every repaired run, case
+    'behind' / 'front' / 'mean'."""
+    n, a = seabed_rows(n_range)
+    idx = np.asarray(idx)
+    seabed = np.ascontiguousarray((idx.astype(np.int64) + (n - a)).T).astype(np.float64)          # [P, F] (:466-468)
+    sb_max = np.ascontiguousarray(np.asarray(colmax, dtype=np.float32).T)                          # [P, F] (:476)
+    P = sb_max.shape[0]
+    with np.errstate(all="ignore"):          # (a constant column: 0 * inf = nan, which is below no threshold)
+        sb_max = np.log(1e-10 + sb_max)
+        sb_max -= np.mean(sb_max, axis=0)
+        sb_max *= 1 / np.std(sb_max, axis=0)
+    e0 = SEABED_REPAIR_EDGE
+    if P > 2 * e0:
+        below = sb_max < SEABED_REPAIR_THRESHOLD
+        for f in range(sb_max.shape[1]):
+            d = np.diff(np.concatenate(([0], below[e0:, f].astype(np.int8), [0])))
+            starts, ends = np.nonzero(d == 1)[0] + e0, np.nonzero(d == -1)[0] + e0 - 1     # [idx_0, idx_1] of every run
+            for i0, i1 in zip(starts.tolist(), ends.tolist()):
+                if i0 >= P - e0:
+                    break                                                    # (the scan has ended: not seen)
+                if i0 <= e0:
+                    case, v = "behind", seabed[i1 + 1, f]                    # (IndexError if it reaches the end, as there)
+                elif i1 >= P - e0:
+                    case, v = "front", seabed[i0 - 1, f]
+                else:
+                    case, v = "mean", np.mean(seabed[[i0 - 1, i1 + 1], f])
+                seabed[i0:i1 + 1, f] = v
+                if runs is not None:
+                    runs.append((f, i0, i1, case))
+    return np.rint(np.median(seabed, axis=1)).astype(int)
+
+
+def estimate_seabed(planes, chunk_pings=SEABED_CHUNK_PINGS, device=None):
+    """The seabed line ``Echogram.get_seabed`` estimates for an echogram without a stored one, from ALL its frequency
+    planes: int64 [n_pings], the reference's values.  ``planes``: the F arrays [n_range, n_pings] of ``data_memmaps()``
+    (uploaded in chunks of ``chunk_pings`` pings plus one halo ping on each side, transposed on the GPU), or a float32
+    tensor [F, n_pings, n_range] that is already resident (one launch, nothing uploaded).  The stencils, the gated
+    argmax and the column maxima run in ``crimac_seabed_columns``; ``finish_seabed`` ends on the host."""
+    if isinstance(planes, torch.Tensor) and planes.is_cuda:
+        F, P, R = (int(v) for v in planes.shape)
+        dev = planes.device
+    else:
+        planes = list(planes)
+        F, (R, P) = len(planes), (int(v) for v in planes[0].shape)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if any(tuple(m.shape) != (R, P) for m in planes):
+            raise ValueError("estimate_seabed: the frequency planes differ in shape")
+    n = seabed_rows(R)[0]
+    if n >= R:
+        raise ValueError(f"estimate_seabed: {R} range rows leave nothing below the {n} rows the estimate skips")
+    idx = torch.empty((F, P), dtype=torch.int32, device=dev)
+    colmax = torch.empty((F, P), dtype=torch.float32, device=dev)
+    if isinstance(planes, torch.Tensor):
+        seabed_columns(planes.contiguous(), 0, 0, n, idx, colmax)
+    else:
+        step = P if not chunk_pings or chunk_pings <= 0 else int(chunk_pings)
+        for s in range(0, P, step):
+            e = min(P, s + step)
+            lo, hi = max(0, s - 1), min(P, e + 1)
+            slab = torch.stack([torch.as_tensor(np.ascontiguousarray(m[:, lo:hi], dtype=np.float32)) for m in planes])
+            chunk = slab.to(dev).permute(0, 2, 1).contiguous()                        # [F, pings, range]
+            seabed_columns(chunk, lo < s, hi > e, n, idx, colmax, ping0=s)
+    return finish_seabed(idx.cpu().numpy(), colmax.cpu().numpy(), R)
+
+
+def estimate_seabed_memm(echogram, chunk_pings=SEABED_CHUNK_PINGS, device=None):
+    """``estimate_seabed`` for a memmap echogram: every frequency it has (``data_memmaps()`` with no selection, as
+    ``data_numpy()`` in data_reader.py:465), whatever subset the model reads."""
+    return estimate_seabed(echogram.data_memmaps(), chunk_pings=chunk_pings, device=device)
+
+
+def _memm_seabed(echogram, seabed, n_pings, data, frequencies):
+    """The seabed vector of ``predict_echogram_memm`` / ``evaluate_echogram_memm``: ``seabed`` None -> the reader's
+    ``get_seabed``; "estimate" -> the GPU estimate (``data``, the resident [C, pings, range] tensor, is reused when the
+    model's frequencies are exactly the echogram's); an integer array [n_pings] -> taken as given."""
+    if seabed is None:
+        return np.asarray(echogram.get_seabed(0, n_pings)).astype(np.int32)
+    if isinstance(seabed, str):
+        if seabed != "estimate":
+            raise ValueError(f"seabed must be None, 'estimate' or an integer array, got {seabed!r}")
+        own = getattr(echogram, "frequencies", None)
+        if own is not None and [int(f) for f in own] == [int(f) for f in frequencies]:
+            return estimate_seabed(data).astype(np.int32)
+        return estimate_seabed_memm(echogram, device=data.device).astype(np.int32)
+    sb = np.asarray(seabed)
+    if sb.dtype.kind not in "iu" or sb.shape != (n_pings,):
+        raise ValueError(f"seabed: an integer array of the echogram's {n_pings} pings, got {sb.dtype} {sb.shape}")
+    return sb.astype(np.int32)
+
+
+def _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels, out_f16, wide,
+                        seabed=None):
     """One memmap echogram as ONE resident chunk (ping_start 0): the arrays are transposed to the ping-major layout of the
     gather kernel on the GPU.  Returns (the loaded ``ChunkPredictor``, the seabed vector)."""
     n_range, n_pings = (int(v) for v in echogram.shape)
@@ -736,20 +866,21 @@ def _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size
     if not eng.lmi and eng.in_channels > len(segpipe.frequencies) and not meta_channels:
         raise ValueError(f"the model takes {eng.in_channels} input channels for {len(segpipe.frequencies)} frequencies "
                          "(metadata planes as input channels): pass meta_channels")
-    seabed = np.asarray(echogram.get_seabed(0, n_pings)).astype(np.int32)
     data = torch.stack([torch.as_tensor(np.ascontiguousarray(m, dtype=np.float32))
                         for m in echogram.data_memmaps(segpipe.frequencies)]).to(dev)
     data = data.permute(0, 2, 1).contiguous()                                     # [C, pings, range]
+    given = seabed is not None
+    seabed = _memm_seabed(echogram, seabed, n_pings, data, segpipe.frequencies)
     labels = torch.as_tensor(np.ascontiguousarray(echogram.label_memmap()).astype(np.int16)).to(dev).t().contiguous()
     cp = ChunkPredictor(model, n_range, patch_size, patch_overlap, batch_size, out_f16=out_f16)
     if meta_channels:                    # metadata planes (late or early injection): built on the GPU, per batch of crops
-        cp.meta_source = MetaSource.from_echogram(echogram, meta_channels, dev)
+        cp.meta_source = MetaSource.from_echogram(echogram, meta_channels, dev, seabed=seabed if given else None)
     cp.load_chunk(data, 0, labels, None, 0, n_pings, seabed=seabed, flavour="memm", wide=wide)
     return cp, seabed
 
 
 def predict_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, predict_fn=None, meta_channels=None,
-                          **kwargs):
+                          seabed=None, **kwargs):
     """``save_reader_predictions_memm`` (save_predict.py:222-265) for one memmap echogram: returns the
     ``[2, n_range, n_pings]`` float64 array the reference ``np.save``s (probabilities rounded to float16 first, :252).
 
@@ -759,9 +890,12 @@ def predict_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_si
     ``meta_channels`` (the yaml's dict): the metadata planes of a UNet_LateMetInject model, or -- required for a model
     whose input channels outnumber the frequencies (early injection) -- its extra input channels, gathered into the
     crop with the data planes (which then take db_with_limits_scaled, transforms.py:57-64).
+    ``seabed``: None -- the reader's ``get_seabed`` (which, for an echogram without a stored seabed.npy, estimates it on
+    the host); ``"estimate"`` -- the same estimate on the GPU (``estimate_seabed``), the reader is not asked; an integer
+    array [n_pings] -- taken as given.
     """
     cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
-                                     out_f16=True, wide=False)
+                                     out_f16=True, wide=False, seabed=seabed)
     grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
     out = cp.predict(grid, predict_fn=predict_fn)
     return out.cpu().numpy().astype(np.float64)
@@ -916,16 +1050,17 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
 
 
 def evaluate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, eval_mode="all", extend_size=20,
-                           predict_fn=None, meta_channels=None, hist=None, on_batch=None, **kwargs):
+                           predict_fn=None, meta_channels=None, hist=None, on_batch=None, seabed=None, **kwargs):
     """Test-set evaluation of one memmap echogram (one Dataset of ``validate_model_survey_memm``, evaluate.py:84-117) on
     the tiled path.  The echogram is one resident chunk, its grid the echogram's (``plan_eval_grid``); metadata models
-    (late injection and metadata input channels) take ``meta_channels`` exactly as ``predict_echogram_memm`` does.
+    (late injection and metadata input channels) take ``meta_channels`` and ``seabed`` (None / "estimate" / an integer
+    array) exactly as ``predict_echogram_memm`` does.
 
     ``hist`` (int32 [2, 16384] on the GPU): accumulate into it and return it -- a survey of several echograms, whose caller
     finishes with ``finish_histograms``; None: returns this echogram's ``(hist_pos, hist_neg)`` int64 numpy (no
     collective: every rank that calls it evaluates the echogram it passes)."""
     cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
-                                     out_f16=False, wide=True)
+                                     out_f16=False, wide=True, seabed=seabed)
     dev = segpipe.device
     boxes = eval_boxes(echogram, eval_mode, extend_size)
     if boxes is not None:

@@ -132,7 +132,7 @@ extern "C" {
  * binding must refuse a library whose version differs from the header it was written against (an older build that
  * happens to export every symbol would walk a descriptor array with the wrong stride).  crimac_layer_desc_size() is
  * sizeof(crimac_layer_desc) as the library was compiled. */
-#define CRIMAC_ABI_VERSION 9
+#define CRIMAC_ABI_VERSION 10
 int crimac_version(void);
 int crimac_layer_desc_size(void);
 const char* crimac_last_error(void);
@@ -684,6 +684,23 @@ int crimac_upconv2x2_narrow(int prec, const void* in, long in_ld, int B, int H, 
                             const float* bias, void* out, long out_ld, int flags, void* stream);
 int crimac_upconv2x2_dgrad_narrow(int prec, const void* dy, long dy_ld, int B, int H, int W, int Cout, int Cin,
                                   const float* w, void* dx, long dx_ld, void* stream);
+
+/* ---- seabed line of a memmap echogram without a stored seabed.npy (csrc/seabed.hip) -------------------------
+ * The streaming part of Echogram.get_seabed (data/data_reader.py:433-507): per (frequency, ping) column the row of the
+ * largest gated second gradient and the column maximum; the caller finishes on the host (tiled_inference.
+ * finish_seabed: standardised log maxima, repair of drop-out runs, median over the frequencies).
+ *   data [F][Pc][R] fp32 linear sv, range contiguous (the memm chunk layout); Pc = the chunk's pings INCLUDING one halo
+ *   ping on the left / right when has_left / has_right is 1 -- an absent halo is the echogram's edge (zero padding, as
+ *   convolve2d mode='same'); the owned pings are Pc - has_left - has_right.
+ *   Non-finite samples count as 0.  With S1(r) = d[r][p-1] + 2 d[r][p] + d[r][p+1], S2(r) = d[r][p-1] + 5 d[r][p] + d[r][p+1]
+ *   in fp64 (rows outside [0, R) are zeros): grad_1 = S1(r+1) - S1(r-1), grad_2 = (S2(r-1) - 2 S2(r)) + S2(r+1),
+ *   score = grad_1 > 0 ? grad_2 : 0 (the reference's true convolutions with flipped filters, :453-458).
+ *   idx [f * out_ld + j] int32: argmax of score over rows n .. R-1 of owned ping j, RELATIVE to row n, first occurrence;
+ *   colmax [f * out_ld + j] fp32: maximum of the sanitised data over rows n .. R-1.  0 <= n < R; out_ld >= owned pings
+ *   (the caller offsets idx / colmax to the chunk's first owned ping of a whole-echogram [F][P] result).
+ *   Element offsets are 64-bit: F * Pc * R may pass 2^31. */
+int crimac_seabed_columns(const float* data, int F, long Pc, int R, int has_left, int has_right, int n, int* idx,
+                          float* colmax, long out_ld, void* stream);
 
 /* ---- measurement support (bench.py only, not on the product path) --------------------------- */
 
