@@ -320,15 +320,12 @@ int crimac_conv3x3_c16_hp(const void* in, long in_ld, int B, int H, int W, int N
 int crimac_conv3x3_glds_hp(const void* in, long in_ld, int B, int H, int W, int Cin, int N, const void* w,
                            const EpiParams& epi, hipStream_t st, int n_first, int n_count, int out_planes, int wfrag);
 
-// register-staged kernel for one 16-bit storage type (odd channel counts, A/B runs)
+// register-staged kernel for one 16-bit storage type: the channel counts the LDS-DMA kernels do not cover (Cin % 64 != 0).
+// Its 128-pixel tile (2 workgroups/CU) is the one that is built: the 256-pixel tile (4 waves, 1 workgroup/CU) lost 5-20 % on
+// every layer (tools/bench_conv.py) -- occupancy beats LDS traffic here.  (While it still ran the Cin % 64 == 0 layers, 64-deep
+// chunks won for N >= 128 and 32-deep ones, 3-4 workgroups per CU, were 10-16 % faster for N = 64.)
 template <typename T16>
-static int conv3x3_staged16(const ConvParams& p, hipStream_t st, int Cin, bool n128, bool big, int force_bk) {
-  // N = 64 layers (level 0 / decoder 3, also the HBM-heaviest): the 32-deep chunk halves the LDS
-  // footprint -> 3-4 workgroups per CU, measured 10-16 % faster there; 64-deep wins for N >= 128
-  if (Cin % 64 == 0 && force_bk != 32 && (n128 || force_bk == 64)) {
-    if (big) return n128 ? launch<T16, 1, 128, 64, 16>(p, st) : launch<T16, 1, 64, 64, 16>(p, st);
-    return n128 ? launch<T16, 1, 128, 64, 8>(p, st) : launch<T16, 1, 64, 64, 8>(p, st);
-  }
+static int conv3x3_staged16(const ConvParams& p, hipStream_t st, int Cin, bool n128) {
   if (Cin % 32 == 0) return n128 ? launch<T16, 1, 128, 32, 8>(p, st) : launch<T16, 1, 64, 32, 8>(p, st);
   return n128 ? launch<T16, 1, 128, 16, 8>(p, st) : launch<T16, 1, 64, 16, 8>(p, st);
 }
@@ -405,18 +402,12 @@ static int conv3x3_run(int prec, const void* in, long in_ld, int B, int H, int W
   e.pool_out = pool_out; e.pool_ld = pool_ld;
   hipStream_t st = (hipStream_t)stream;
   const bool n128 = N % 128 == 0;
-  // measured (tools/bench_conv.py): the 256-pixel tile of THIS kernel (4 waves, 1 workgroup/CU) loses
-  // 5-20 % to the 128-pixel tile (2 workgroups/CU) on every layer -- occupancy beats LDS traffic here
-  static const int force_tr = getenv("CRIMAC_CONV_TR") ? atoi(getenv("CRIMAC_CONV_TR")) : 0;
-  const bool big = force_tr == 16;
-  static const int force_bk = getenv("CRIMAC_CONV_BK") ? atoi(getenv("CRIMAC_CONV_BK")) : 0;
-  // bf16 with 64-deep channel chunks: LDS-DMA streaming kernels (CRIMAC_CONV_GLDS=0 selects the
-  // register-staged kernel below, kept for A/B measurements and as the fp32-mode structure).
-  // Measured (tools/bench_conv.py, B=32): +8-18 % on every layer with N >= 128 (8-wave kernel), +5-13 % on
-  // the N = 64 layers (4-wave kernel, two workgroups per CU).
-  static const int use_glds = getenv("CRIMAC_CONV_GLDS") ? atoi(getenv("CRIMAC_CONV_GLDS")) : 1;
+  // 16-bit storage with 64-deep channel chunks and plane pairs: the LDS-DMA streaming kernels (conv3x3_glds.hip).
+  // Measured against the register-staged kernel below (tools/bench_conv.py, B=32): +8-18 % on every layer with N >= 128
+  // (8-wave kernel), +5-13 % on the N = 64 layers (4-wave kernel, two workgroups per CU).  The register-staged kernel
+  // keeps the other channel counts and the fp32 modes.
   const bool ranged = n_first != 0 || n_count != N;
-  CRIMAC_REQUIRE(!ranged || (n_first >= 0 && n_count > 0 && n_first + n_count <= N && use_glds &&
+  CRIMAC_REQUIRE(!ranged || (n_first >= 0 && n_count > 0 && n_first + n_count <= N &&
                              ((is16 && Cin % 64 == 0) || (prec == CRIMAC_PREC_H3P && Cin % 32 == 0))),
                  "conv3x3_cols: a channel range needs the LDS-DMA kernels (16-bit storage: Cin %% 64 == 0, plane pairs: "
                  "Cin %% 32 == 0)");
@@ -424,32 +415,26 @@ static int conv3x3_run(int prec, const void* in, long in_ld, int B, int H, int W
     // plane-pair input: the 16-bit LDS-DMA kernels on a tensor of 2 Cin halves per pixel (3 MFMAs per product);
     // the first layer (4 input channels padded to 16) runs on the register-staged kernel, whose staging copies the
     // pre-split halves
-    CRIMAC_REQUIRE(!wfrag || (Cin % 32 == 0 && use_glds),
+    CRIMAC_REQUIRE(!wfrag || Cin % 32 == 0,
                    "conv3x3 (plane pairs): fragment-major weights (CRIMAC_EPI_WFRAG) are read by the channel-split kernel only");
-    if (Cin % 32 == 0 && use_glds)
+    if (Cin % 32 == 0)
       return crimac_conv3x3_glds_hp(in, in_ld, B, H, W, Cin, N, w_hi, e, st, n_first, n_count, out_planes, wfrag);
     CRIMAC_REQUIRE(!pool_out, "conv3x3_pool (plane pairs): Cin %% 32 == 0 only");
     // first layer (4 input channels padded to 16): the persistent 16-channel kernel on hi / lo pseudo-channels
-    static const int c16hp = getenv("CRIMAC_CONV_C16HP") ? atoi(getenv("CRIMAC_CONV_C16HP")) : 1;
-    if (c16hp && cin4 && Cin == 16 && N == 64 && use_glds && stat_mode != 2 && in_ld >= 8)
+    if (cin4 && Cin == 16 && N == 64 && stat_mode != 2 && in_ld >= 8)
       return crimac_conv3x3_c16_hp(in, in_ld, B, H, W, N, w_hi, e, st, out_planes);
-    if (Cin % 32 == 0) {
-      if (out_planes) return n128 ? launch<hp_t, 2, 128, 32, 8, half_t, hp_t>(p, st) : launch<hp_t, 2, 64, 32, 8, half_t, hp_t>(p, st);
-      return n128 ? launch<hp_t, 2, 128, 32, 8, half_t, float>(p, st) : launch<hp_t, 2, 64, 32, 8, half_t, float>(p, st);
-    }
     if (out_planes) return n128 ? launch<hp_t, 2, 128, 16, 8, half_t, hp_t>(p, st) : launch<hp_t, 2, 64, 16, 8, half_t, hp_t>(p, st);
     return n128 ? launch<hp_t, 2, 128, 16, 8, half_t, float>(p, st) : launch<hp_t, 2, 64, 16, 8, half_t, float>(p, st);
   }
-  CRIMAC_REQUIRE(!wfrag || (is16 && Cin % 64 == 0 && use_glds),
+  CRIMAC_REQUIRE(!wfrag || (is16 && Cin % 64 == 0),
                  "conv3x3: fragment-major weights (CRIMAC_EPI_WFRAG) are read by the 16-bit / plane-pair channel-split kernel only");
-  if (is16 && Cin % 64 == 0 && use_glds)
+  if (is16 && Cin % 64 == 0)
     return crimac_conv3x3_glds_16(in, in_ld, B, H, W, Cin, N, w_hi, e, st, n_first, n_count, fp16, wfrag);
   // first layer (4 input channels padded to 16): persistent one-barrier kernel
-  if (is16 && Cin == 16 && N == 64 && use_glds)
+  if (is16 && Cin == 16 && N == 64)
     return crimac_conv3x3_c16_16(in, in_ld, B, H, W, N, w_hi, e, st, fp16);
   if (is16)
-    return fp16 ? conv3x3_staged16<half_t>(p, st, Cin, n128, big, force_bk)
-                : conv3x3_staged16<bf16_t>(p, st, Cin, n128, big, force_bk);
+    return fp16 ? conv3x3_staged16<half_t>(p, st, Cin, n128) : conv3x3_staged16<bf16_t>(p, st, Cin, n128);
   // split planes keep 2-3 planes per operand: 32-deep chunks keep the LDS footprint in bounds
   if (prec == CRIMAC_PREC_F32H3) {       // two fp16 planes (forward operands only: see the header)
     if (Cin % 32 == 0) return n128 ? launch<float, 2, 128, 32, 8, half_t>(p, st) : launch<float, 2, 64, 32, 8, half_t>(p, st);

@@ -124,7 +124,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 // registers (36-72 B-fragments per wave; hipcc spills around the epilogue and every scratch reload
 // drains the DMA queue: 470-610 us).
 // (BN = 128 instantiates too -- 64 x 128 per wave, 2-slot ring, 74 KB -- and was the default for N >= 128 until
-// the channel-split kernel below beat it by 12 %; CRIMAC_CONV_W4=1 selects it for A/B runs.)
+// the channel-split kernel below beat it by 12 %; it still takes the tensors past 2 GB.)
 // PP: plane-pair input (p.Cin / p.in_ld count HALVES: twice the channels), 3 MFMAs per fragment pair; TO: output storage
 template <int BN, typename T16, int MODE, typename TO = T16, bool PP = false>     // MODE: the epilogue's fused reduction (0 none, 1 statistics, 2 BatchNorm-backward sums)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))      // <= 256 registers: 2 workgroups/CU
@@ -380,12 +380,11 @@ struct WchFrags {
   bf16x8 a[2][4];
   bf16x8 b[2][4];        // [tap parity][ks2 * 2 + nb]
 };
-// NQ: groups of 4 image rows per wave (4: the wave covers all 16 rows of the tile; 2: the 2 x 2 form for 64-channel
-// tiles, waves = 2 pixel halves x 2 channel halves, the half's row offset rides in the address registers)
+constexpr int NQ = 4;      // groups of 4 image rows per wave: a wave covers 16 rows of the tile
 // ILV (tall form): the wave's second half of row groups lies 2 NQ image rows further down -- a wave owns rows
 // [8 wp, 8 wp + 8) and [16 + 8 wp, 16 + 8 wp + 8) of the 32-row tile, so that each 16-row slice of the epilogue holds half of
 // EVERY wave's accumulators (with 16 contiguous rows per wave one wave pair stages a slice while the other idles)
-template <int H, int NQ = 4, bool ILV = false>
+template <int H, bool ILV = false>
 __device__ __forceinline__ void wch_issue(const unsigned (&av)[3][2], WchFrags& f) {
   constexpr int t = H / (2 * NQ), ks2 = (H / NQ) % 2, q = H % NQ;
   constexpr int base = (t / 3 + 4 * q + (ILV && q >= NQ / 2 ? 2 * NQ : 0)) * (HP * RB);
@@ -439,7 +438,7 @@ __device__ __forceinline__ void wch_load_b(const unsigned short* s0, const unsig
 // PP (plane pairs): k-step 0 of a chunk is the hi plane of 32 channels, k-step 1 their lo plane, in both operands: the
 // hi fragments of A meet both weight planes (hi*lo, then hi*hi), the lo fragments the hi weights only -- 3 MFMAs per
 // fragment pair, 16 + 8 per pair of groups, on the same reads and weight loads as the 16-bit kernel's 8 + 8.
-template <typename T16, bool PP, int H, int NQ = 4, bool ILV = false, bool WF = false, typename ACC>
+template <typename T16, bool PP, int H, bool ILV = false, bool WF = false, typename ACC>
 __device__ __forceinline__ void wch_step(const unsigned (&av)[3][2], const unsigned short* wtap, long w_tap, long w_nb,
                                            const unsigned short* wnext_chunk, WchFrags& f, ACC& acc) {
   constexpr int t = H / (2 * NQ), ks2 = (H / NQ) % 2, q = H % NQ, NH = 18 * NQ;
@@ -461,14 +460,14 @@ __device__ __forceinline__ void wch_step(const unsigned (&av)[3][2], const unsig
 #ifdef CRIMAC_EXP_WCH_FEWA        // (ablation build, results garbage: 3 of 8 groups of LDS fragment reads -- what a form that uses
   //                                  every halo-row fragment for the three taps of its column would read)
   if constexpr (H + 1 < NH && (H + 1) % 8 < 3) {
-    wch_issue<H + 1, NQ, ILV>(av, f);
+    wch_issue<H + 1, ILV>(av, f);
     wch_release<false>(f, H & 1);
   } else {
     wch_release<true>(f, H & 1);
   }
 #else
   if constexpr (H + 1 < NH) {
-    wch_issue<H + 1, NQ, ILV>(av, f);
+    wch_issue<H + 1, ILV>(av, f);
     wch_release<false>(f, H & 1);
   } else {
     wch_release<true>(f, H & 1);
@@ -487,7 +486,7 @@ __device__ __forceinline__ void wch_step(const unsigned (&av)[3][2], const unsig
     for (int nb = 0; nb < 2; ++nb)
       acc[4 * q + j][nb] = E16<T16>::mfma16(f.a[H & 1][j], f.b[t & 1][(PP ? 0 : ks2 * 2) + nb],
                                                                     acc[4 * q + j][nb]);
-  if constexpr (H + 1 < NH) wch_step<T16, PP, H + 1, NQ, ILV, WF>(av, wtap, w_tap, w_nb, wnext_chunk, f, acc);
+  if constexpr (H + 1 < NH) wch_step<T16, PP, H + 1, ILV, WF>(av, wtap, w_tap, w_nb, wnext_chunk, f, acc);
 }
 
 // FORM 3 ("rows"): 64 output channels of a 32 x 16-pixel tile, waves = 4 channel QUARTERS (16 channels each) of all 32
@@ -555,22 +554,21 @@ __device__ __forceinline__ void wrow_step(const unsigned (&av)[3][2], const unsi
   if constexpr (S + 1 < kRowSteps) wrow_step<T16, S + 1>(av, avh, wch, w_tap, wnext_chunk, f, acc);
 }
 
-// FORM 1 ("S22"): the 2 x 2 form for 64-channel tiles: waves = 2 pixel halves (8 image rows each) x 2 channel halves (32
-// channels each); the wave's weight fragments still come straight from global memory (each half is fetched by two waves).
 // FORM 2 ("tall"): 64 output channels of a 32 x 16-pixel tile: waves = 2 pixel halves of SIXTEEN image rows x 2 channel
 // halves -- every wave is exactly the wave of the 128-channel form (16 M tiles x 32 channels, the same reads, weight
 // loads and MFMAs per tap), so a weight fragment feeds as many MFMAs as there; what differs is the halo (34 x 18 pixels,
 // 76.5 KB per chunk: 1.9x the bytes per MFMA, which is what 64 output channels cost) -- two workgroups per CU.
-// Why: in FORM 1 a wave's tap is 48 MFMAs (plane pairs) between two weight-fragment waits and a workgroup's prologue,
-// halo waits and epilogue (28 k cycles) stand against 13.8 k cycles of MFMA work per SIMD: MFMA busy 0.45 (PMC) where the
-// 128-channel form reaches 0.77.
+// Why: a 2 x 2 form on 16 x 16 pixels (8 image rows per wave, once FORM 1) left 48 MFMAs (plane pairs) per tap between two
+// weight-fragment waits, and a workgroup's prologue, halo waits and epilogue (28 k cycles) stood against 13.8 k cycles of MFMA
+// work per SIMD: MFMA busy 0.45 (PMC) where the 128-channel form reaches 0.77.
 template <typename T16, int MODE, typename TO = T16, bool PP = false, int FORM = 0, bool WF = false>      // MODE: the epilogue's fused reduction (0 none, 1 BatchNorm statistics, 2 BatchNorm-backward sums); WF: fragment-major weight plane
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FORM == 1 ? 3 : 2, FORM == 1 ? 3 : 2))) void conv3x3_wch_kernel(ConvParams p) {
-  constexpr bool S22 = FORM != 0;                  // 64-channel tiles (forms 1, 2: waves = pixel halves x channel halves; 3: channel quarters)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_wch_kernel(ConvParams p) {
+  static_assert(FORM == 0 || FORM == 2 || FORM == 3, "forms: 0 (128 channels), 2 (tall), 3 (rows)");
+  constexpr bool S22 = FORM != 0;                  // 64-channel tiles (form 2: waves = pixel halves x channel halves; 3: channel quarters)
   constexpr bool ROWS = FORM == 3;
   static_assert(!ROWS || (WF && !PP), "the rows form reads fragment-major 16-bit planes");
   constexpr int BN = S22 ? 64 : 128, NW = 4;
-  constexpr int NQ = FORM == 1 ? 2 : 4, WR = ROWS ? 32 : 4 * NQ;       // image rows (16-pixel M tiles) per wave
+  constexpr int WR = ROWS ? 32 : 4 * NQ;                   // image rows (16-pixel M tiles) per wave
   constexpr int WN = ROWS ? 1 : 2;                         // 16-channel tiles per wave
   constexpr int TRK = FORM >= 2 ? 32 : TR;                 // image rows of the workgroup's tile
   constexpr bool ILV = FORM == 2;                          // the wave's rows: two blocks of WR / 2 (wch_issue)
@@ -711,8 +709,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FORM == 1 ?
       wrow_step<T16, 0>(av, avh, wtap, w_tap, wnext, rf, acc);
       wrow_land_b(rf.b[0]);
     } else {
-      wch_issue<0, NQ, ILV>(av, f);
-      wch_step<T16, PP, 0, NQ, ILV, WF>(av, wtap, w_tap, w_nb, wnext, f, acc);
+      wch_issue<0, ILV>(av, f);
+      wch_step<T16, PP, 0, ILV, WF>(av, wtap, w_tap, w_nb, wnext, f, acc);
       wch_land_b(f.b[1]);
     }
     __builtin_amdgcn_s_barrier();
@@ -1609,7 +1607,7 @@ int glds_dispatch(ConvParams p, hipStream_t st) {
                    "conv3x3: fragment-major weights (CRIMAC_EPI_WFRAG) need N and the channel range in multiples of 128 and "
                    "Cin %% 64 == 0 (N=%d range [%d, +%d) Cin=%d)", N, n_first, n_count, Cin);
     CRIMAC_REQUIRE(small_f, "conv3x3: fragment-major weights (CRIMAC_EPI_WFRAG): the input tensor exceeds the 2 GB the "
-                   "channel-split kernel addresses (B=%d H=%d W=%d ld=%ld): pack row-major planes (CRIMAC_WFRAG=0)", B, H, W, in_ld);
+                   "channel-split kernel addresses (B=%d H=%d W=%d ld=%ld): the engine packs row-major planes past 2 GB", B, H, W, in_ld);
     return launch_wch<T16, T16, false, 0, true>(p, st);
   }
   if (n_first != 0 || n_count != N) {
@@ -1627,23 +1625,18 @@ int glds_dispatch(ConvParams p, hipStream_t st) {
                    "64-input-channel convolution with >= 512 tiles)", n_first, n_count, N);
     return launch_wch<T16>(p, st);
   }
-  // N % 128 == 0: channel-split kernel; N = 64 (or 192, ...): pixel-split kernel with the LDS weight ring.
-  // Measured per layer at B = 32 (tools/bench_conv.py): wch 1.1-1.6 PFLOP/s vs 1.0-1.25 (W4<128>); on the two
-  // HBM-heavy N = 64 shapes W4<64> (305 / 423 us) beats a 2x2-wave channel split (319 / 458 us).
-  static const int w4 = getenv("CRIMAC_CONV_W4") ? atoi(getenv("CRIMAC_CONV_W4")) : 0;
-  // N = 64: the tall form of the channel-split kernel (CRIMAC_CONV_TALL16: 0 off, 1 every shape but 64 -> 64, 2 every N = 64
-  // shape).  Measured at B = 32, 256 x 256: 128 -> 64  274-276 us (pixel-split kernel with the LDS weight ring: 373-379);
-  // 64 -> 64  231-238 us against 175-190 of the persistent kernel below, which keeps that shape.
-  static const int tall = getenv("CRIMAC_CONV_TALL16") ? atoi(getenv("CRIMAC_CONV_TALL16")) : 1;
-  const bool small64 = (((long)B * H * W - 1) * in_ld + Cin) * 2 < (1L << 31);
-  if (N == 64 && small64 && (tall == 2 || (tall == 1 && Cin != 64))) return launch_wch<T16, T16, false, 2>(p, st);
-  // 64 -> 64 with many tiles: persistent kernel with LDS-resident weights (CRIMAC_CONV_P64=0: W4 for A/B runs)
-  static const int p64 = getenv("CRIMAC_CONV_P64") ? atoi(getenv("CRIMAC_CONV_P64")) : 1;
-  if (p64 && N == 64 && Cin == 64 && H % TR == 0 && W % TC == 0 && (long)B * (H / TR) * (W / TC) >= 512 && !p.epi.stat_raw)
-    return launch_p64<T16>(p, st);
-  if (N % 128 != 0) return launch_w4<64, T16>(p, st);
   const bool small = (((long)B * H * W - 1) * in_ld + Cin) * 2 < (1L << 31);     // 32-bit buffer offsets in wch
-  return (w4 == 1 || !small) ? launch_w4<128, T16>(p, st) : launch_wch<T16>(p, st);
+  // N = 64, Cin != 64: the tall form of the channel-split kernel.  Measured at B = 32, 256 x 256: 128 -> 64  274-276 us
+  // (pixel-split kernel with the LDS weight ring: 373-379).
+  if (N == 64 && small && Cin != 64) return launch_wch<T16, T16, false, 2>(p, st);
+  // 64 -> 64 with many tiles: persistent kernel with LDS-resident weights (175-190 us at that size, the tall form 231-238)
+  if (N == 64 && Cin == 64 && H % TR == 0 && W % TC == 0 && (long)B * (H / TR) * (W / TC) >= 512 && !p.epi.stat_raw)
+    return launch_p64<T16>(p, st);
+  // other N = 64 (or 192, ...): pixel-split kernel with the LDS weight ring
+  if (N % 128 != 0) return launch_w4<64, T16>(p, st);
+  // N % 128 == 0: channel-split kernel, 1.1-1.6 PFLOP/s per layer at B = 32 (tools/bench_conv.py) against 1.0-1.25 of the
+  // pixel-split kernel, which takes the tensors past 2 GB
+  return small ? launch_wch<T16>(p, st) : launch_w4<128, T16>(p, st);
 }
 }  // namespace
 
@@ -1658,7 +1651,6 @@ int crimac_conv3x3_glds_hp(const void* in, long in_ld, int B, int H, int W, int 
   p.epi = epi;
   p.n_first = n_first; p.n_count = n_count;
   const bool small = (((long)B * H * W - 1) * p.in_ld + p.Cin) * 2 < (1L << 31);     // 32-bit buffer offsets in wch
-  static const int w4 = getenv("CRIMAC_CONV_W4") ? atoi(getenv("CRIMAC_CONV_W4")) : 0;
   CRIMAC_REQUIRE(wfrag != 2, "conv3x3 (plane pairs): no rows form (CRIMAC_EPI_WROWS)");
   if (wfrag) {      // fragment-major plane (rows of 2 Cin halves): the 128-channel form of the channel-split kernel only
     CRIMAC_REQUIRE(N % 128 == 0 && n_count % 128 == 0 && n_first % 128 == 0 && small,
@@ -1666,19 +1658,15 @@ int crimac_conv3x3_glds_hp(const void* in, long in_ld, int B, int H, int W, int 
                    "128 and an input tensor below 2 GB (N=%d range [%d, +%d))", N, n_first, n_count);
     return out_planes ? launch_wch<half_t, hp_t, true, 0, true>(p, st) : launch_wch<half_t, float, true, 0, true>(p, st);
   }
-  if (n_count % 128 == 0 && n_first % 128 == 0 && small && w4 != 1)
+  if (n_count % 128 == 0 && n_first % 128 == 0 && small)
     return out_planes ? launch_wch<half_t, hp_t, true>(p, st) : launch_wch<half_t, float, true>(p, st);
   CRIMAC_REQUIRE(n_first % 64 == 0 && n_count % 64 == 0, "conv3x3 (plane pairs): channel range [%d, +%d) must be "
                  "multiples of 64", n_first, n_count);
   if (n_count % 128 == 0 && n_first % 128 == 0)
     return out_planes ? launch_w4<128, half_t, hp_t, true>(p, st) : launch_w4<128, half_t, float, true>(p, st);
-  // 64-channel ranges: CRIMAC_CONV_S22 = 2 (default) the tall 32 x 16-pixel form, 1 the 2 x 2 form on 16 x 16 pixels,
-  // 0 the pixel-split kernel with the LDS weight ring
-  static const int s22 = getenv("CRIMAC_CONV_S22") ? atoi(getenv("CRIMAC_CONV_S22")) : 2;
-  if (s22 == 2 && small)
+  // 64-channel ranges: the tall 32 x 16-pixel form; past 2 GB the pixel-split kernel with the LDS weight ring
+  if (small)
     return out_planes ? launch_wch<half_t, hp_t, true, 2>(p, st) : launch_wch<half_t, float, true, 2>(p, st);
-  if (s22 && small)
-    return out_planes ? launch_wch<half_t, hp_t, true, 1>(p, st) : launch_wch<half_t, float, true, 1>(p, st);
   return out_planes ? launch_w4<64, half_t, hp_t, true>(p, st) : launch_w4<64, half_t, float, true>(p, st);
 }
 

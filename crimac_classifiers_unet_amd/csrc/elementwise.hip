@@ -57,9 +57,8 @@ static int g_resident_n = 0;
 static std::mutex g_resident_mu;
 template <typename K>
 inline int whole_rounds(K kernel, size_t lds, int grid, int block = 256) {
-  static const int off = getenv("CRIMAC_WHOLE_ROUNDS") ? atoi(getenv("CRIMAC_WHOLE_ROUNDS")) == 0 : 0;      // (A/B runs)
   int dev = 0;
-  if (off || grid <= 256 || hipGetDevice(&dev) != hipSuccess) return grid;
+  if (grid <= 256 || hipGetDevice(&dev) != hipSuccess) return grid;
   const void* fn = reinterpret_cast<const void*>(kernel);
   int blocks = 0;
   {
@@ -1682,8 +1681,7 @@ extern "C" int crimac_bn_bwd_apply(int prec, const void* da, long da_ld, const v
                  "bn_bwd_apply: bad pixel strides");
   const int grid = colreduce_grid(M, C);
   const size_t lds = 2 * C * sizeof(float);
-  static const int stream_form = getenv("CRIMAC_BNB_STREAM") ? atoi(getenv("CRIMAC_BNB_STREAM")) : 1;
-  if (!dbias && stream_form && C <= 2048)
+  if (!dbias)      // (the streaming form has no bias-gradient column sums)
     CRIMAC_FOR_STORAGE2(prec, T, TD, hipLaunchKernelGGL((bn_bwd_apply_stream_kernel<T, TD>), dim3(whole_rounds(bn_bwd_apply_stream_kernel<T, TD>, 0, grid)), dim3(256), 0, ST,
                                                    (const T*)da, da_ld, (const T*)y, y_ld, scale, shift, mean, invstd,
                                                    sum_dz, sum_dz_xhat, M, count, C, (TD*)dy, dy_ld, dgamma, dbeta, 1));

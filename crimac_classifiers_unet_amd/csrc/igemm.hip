@@ -351,13 +351,12 @@ extern "C" int crimac_igemm_conv(int prec, const void* in, long in_ld, int B, in
   }
   if (is16 && !relu) {
     // ConvTranspose2d(k2, s2): forward (1 tap, scatter) and input gradient (4 taps, stride 2) go to upconv.hip
-    static const int use_wch = getenv("CRIMAC_UPCONV_WCH") ? atoi(getenv("CRIMAC_UPCONV_WCH")) : 1;
     const long in_bytes = (((long)B * Hi * Wi - 1) * in_ld + Cin) * 2;
     const bool fwd = out_mode == 1 && ntaps == 1 && stride == 1 && pad == 0 && Hi == Ho && Wi == Wo &&
                      (!bias || bias_mod == cout_up);
     const bool dgr = out_mode == 0 && ntaps == 4 && tw == 2 && stride == 2 && pad == 0 && Hi == 2 * Ho &&
                      Wi == 2 * Wo && !bias;
-    if (use_wch && (fwd || dgr) && crimac_upconv_wch_ok(ntaps, in_bytes, Cin, N, cout_up, out_ld))
+    if ((fwd || dgr) && crimac_upconv_wch_ok(ntaps, in_bytes, Cin, N, cout_up, out_ld))
       return crimac_upconv_wch_16(ntaps, in, in_ld, B, Ho, Wo, Cin, N, w_hi, bias, cout_up, out, out_ld, st,
                                   prec == CRIMAC_PREC_FP16);
   }

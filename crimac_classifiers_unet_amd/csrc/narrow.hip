@@ -14,7 +14,7 @@
 //   * 4-byte storage (the fp32 modes and the plane pairs of H3P): conv3x3_narrow_kernel, fp32 VALU FMAs of the stored
 //     operands against LDS-broadcast fp32 weight rows (2 pixels x N accumulators per thread): these are the parity modes,
 //     whose fp32-equivalent results would need the 3-plane split (6 MFMAs per product) and 3x the LDS of the 16-bit form.
-//     The VALU form also serves the 16-bit modes under CRIMAC_NARROW_VALU=1 (A/B runs; DESIGN.md has the comparison).
+//     (DESIGN.md has the comparison of the two forms on the 16-bit modes.)
 //
 // Weights are read straight from the fp32 master tensors (no packed planes):
 //   conv3x3 forward: w [N][w_cin][3][3] (input channels >= w_cin are zero: the padded first layer), x scale[n] when given
@@ -460,10 +460,11 @@ extern "C" int crimac_conv3x3_narrow(int prec, const void* in, long in_ld, int B
   p.s0 = stat_sum; p.s1 = stat_sumsq; p.reps = stat_replicas > 0 ? stat_replicas : 1; p.stat_ld = stat_ld;
   p.tiles_x = cdiv(W, TW); p.tiles_y = cdiv(H, TH); p.ntiles = (long)B * p.tiles_x * p.tiles_y;
   hipStream_t st = (hipStream_t)stream;
-  static const bool valu = getenv("CRIMAC_NARROW_VALU") && atoi(getenv("CRIMAC_NARROW_VALU")) != 0;
-  if (!valu && prec == CRIMAC_PREC_BF16) return mfma_launch_n<bf16_t>(p, N, st);
-  if (!valu && prec == CRIMAC_PREC_FP16) return mfma_launch_n<half_t>(p, N, st);
-  CRIMAC_NARROW_TYPES(prec, flags & CRIMAC_EPI_OUT_PLANES, TI, TO, return conv_launch_n<TI, TO>(p, N, st));
+  if (prec == CRIMAC_PREC_BF16) return mfma_launch_n<bf16_t>(p, N, st);
+  if (prec == CRIMAC_PREC_FP16) return mfma_launch_n<half_t>(p, N, st);
+  if (prec == CRIMAC_PREC_H3P)
+    return (flags & CRIMAC_EPI_OUT_PLANES) ? conv_launch_n<hp_t, hp_t>(p, N, st) : conv_launch_n<hp_t, float>(p, N, st);
+  return conv_launch_n<float, float>(p, N, st);
 }
 
 extern "C" int crimac_upconv2x2_narrow(int prec, const void* in, long in_ld, int B, int H, int W, int Cin, int Cout,

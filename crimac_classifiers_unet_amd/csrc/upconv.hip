@@ -117,8 +117,8 @@ template <bool PP> __device__ __forceinline__ int src_unit(int u) { return PP ? 
 
 // SCATTER: forward (output on the fine grid, column group (a,b) -> pixel (2y+a, 2x+b)); else dense dgrad tile.
 // PP: plane-pair input (p.K / p.in_ld count halves); TO: output storage type (T16, float, or hp_t plane pairs)
-// NWV: waves per workgroup = 32-column groups sharing the A tile: 4 (128 columns, two workgroups per CU) or 8 (256 columns,
-// one workgroup per CU: an experiment, see launch()).  Every column group of a pixel tile stages the same A chunks
+// NWV: waves per workgroup = 32-column groups sharing the A tile: 4 (128 columns, two workgroups per CU; launch()
+// builds no other).  Every column group of a pixel tile stages the same A chunks
 // (plane pairs, 1024 -> 512 forward: 16 column groups x 33.5 MB = 0.54 GB through the LDS-DMA path in 105 us).
 template <bool SCATTER, typename T16, typename TO = T16, bool PP = false, int NWV = 4>
 __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -295,9 +295,12 @@ void upconv_wch_kernel(UpParams p) {
   }
 }
 
-template <bool SCATTER, typename T16, typename TO, bool PP, int NWV>
-int launch_n(UpParams p, hipStream_t st) {
-  constexpr int BNK = 32 * NWV;
+// 4 waves, 128 columns per workgroup.  An 8-wave form (256 columns) halved the A-tile traffic, but one 8-wave workgroup per
+// CU has no second workgroup to cover its chunk barriers and epilogue: plane pairs 25.56 vs 25.32 ms per step (inference
+// +0.6 %), bf16 equal (inference -2 %) at B = 32 -- not built.
+template <bool SCATTER, typename T16, typename TO = T16, bool PP = false>
+int launch(UpParams p, hipStream_t st) {
+  constexpr int NWV = 4, BNK = 32 * NWV;
   p.tiles_y = cdiv(p.H, TP);
   p.tiles_x = cdiv(p.W, TP);
   const long ntiles = (long)p.B * p.tiles_y * p.tiles_x;
@@ -313,15 +316,6 @@ int launch_n(UpParams p, hipStream_t st) {
                      p);
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
-}
-// CRIMAC_UPCONV_W8=1: 256 columns per workgroup where the column count allows it.  Measured (B = 32, same box): it halves
-// the A-tile traffic, but one 8-wave workgroup per CU has no second workgroup to cover its chunk barriers and epilogue:
-// plane pairs 25.56 vs 25.32 ms per step (inference +0.6 %), bf16 equal (inference -2 %) -- off by default.
-template <bool SCATTER, typename T16, typename TO = T16, bool PP = false>
-int launch(UpParams p, hipStream_t st) {
-  static const int w8 = getenv("CRIMAC_UPCONV_W8") ? atoi(getenv("CRIMAC_UPCONV_W8")) : 0;
-  if (w8 && p.N % 256 == 0) return launch_n<SCATTER, T16, TO, PP, 8>(p, st);
-  return launch_n<SCATTER, T16, TO, PP, 4>(p, st);
 }
 
 }  // namespace

@@ -1614,9 +1614,8 @@ void plan_splits(WgradParams& p, int mode, int target_blocks, int teams) {
   const bool autosplit = target_blocks <= 0;
   // one resident round: 2 workgroups per CU x 256 CUs.  More splits only add partial-sum volume (each workgroup
   // ends with 147 KB of fp32 output) and a second, partially filled round: 512 measured 2 % faster than 1024.
-  static const int auto_blocks = getenv("CRIMAC_WGRAD_BLOCKS") ? atoi(getenv("CRIMAC_WGRAD_BLOCKS")) : 512;
-  if (autosplit) target_blocks = auto_blocks / teams;
   const int round = 512 / teams;               // workgroups of one resident round
+  if (autosplit) target_blocks = round;
   int splits = target_blocks / ch_tiles;
   if (autosplit) {
     // every split adds one pass over dW (fp32 atomics at ~1.3 TB/s chip-wide, or a partial slab written and read
@@ -1671,10 +1670,9 @@ int launch_pp(WgradParams p, int target_blocks, hipStream_t st) {
   return CRIMAC_OK;
 }
 
-// plane pairs, transposed convolution: the 128 x 64 kernel above (CRIMAC_WGRAD_UP_PP=0: the register-staged kernel)
+// plane pairs, transposed convolution: the 128 x 64 kernel above (other shapes and the slab form: the register-staged kernel)
 bool up_pp_ok(int prec, int mode, int CF, int CS, long f_ld, long s_ld, int Wf, long partial_stride) {
-  static const int off = getenv("CRIMAC_WGRAD_UP_PP") ? atoi(getenv("CRIMAC_WGRAD_UP_PP")) == 0 : 0;
-  return !off && prec == CRIMAC_PREC_H3P && mode == 1 && partial_stride == 0 && CF % 128 == 0 && CS % 64 == 0 &&
+  return prec == CRIMAC_PREC_H3P && mode == 1 && partial_stride == 0 && CF % 128 == 0 && CS % 64 == 0 &&
          (2L * Wf + 16) * f_ld * 4 < (1L << 31) && (8L * Wf + 32) * s_ld * 4 < (1L << 31);
 }
 int launch_up_pp(WgradParams p, int target_blocks, hipStream_t st) {
@@ -1697,16 +1695,13 @@ int launch_up_pp(WgradParams p, int target_blocks, hipStream_t st) {
   return CRIMAC_OK;
 }
 
-// 16-bit storage, conv3x3: the two-team kernel (CRIMAC_WGRAD_TEAMS=1 selects the 4-wave kernel for A/B runs)
 // plane pairs, conv3x3, whole 64-channel tiles both ways, 32-bit DMA offsets inside a tile: the 8-wave kernel above
 bool pp_ok(int prec, int mode, int CF, int CS, long f_ld, long s_ld, int Wf) {
-  static const int off = getenv("CRIMAC_WGRAD_PP") ? atoi(getenv("CRIMAC_WGRAD_PP")) == 0 : 0;
-  return !off && prec == CRIMAC_PREC_H3P && mode == 0 && CF % 64 == 0 && (CS % 64 == 0 || CS == 16) &&
+  return prec == CRIMAC_PREC_H3P && mode == 0 && CF % 64 == 0 && (CS % 64 == 0 || CS == 16) &&
          (10L * Wf + 18) * (f_ld > s_ld ? f_ld : s_ld) * 4 < (1L << 31);
 }
+// 16-bit storage, conv3x3: the two-team kernel (8 waves, one workgroup per CU); everything else: 4 waves, two per CU
 int teams_of(int prec, int mode) {
-  static const int forced = getenv("CRIMAC_WGRAD_TEAMS") ? atoi(getenv("CRIMAC_WGRAD_TEAMS")) : 0;
-  if (forced == 1) return 1;
   return (prec == CRIMAC_PREC_BF16 || prec == CRIMAC_PREC_FP16) && mode == 0 ? 2 : 1;
 }
 
@@ -1738,17 +1733,16 @@ int wgrad_run(int prec, int mode, const void* f, long f_ld, int CF, const void* 
     CRIMAC_REQUIRE((20L * Wf + 64) * ldmax * 4 < (1L << 31), "wgrad (H3F_BWD): a tile's DMA offsets exceed 32 bits");
   }
   hipStream_t st = (hipStream_t)stream;
-  const bool two = teams_of(prec, mode) == 2;
   if (prec == CRIMAC_PREC_BF16) {
     if (mode == 0 && CS <= 16)                                                              // first layer
-      return two ? launch<bf16_t, 1, 0, true, 2>(p, target_blocks, st) : launch<bf16_t, 1, 0, true>(p, target_blocks, st);
-    if (mode == 0) return two ? launch<bf16_t, 1, 0, false, 2>(p, target_blocks, st) : launch<bf16_t, 1, 0>(p, target_blocks, st);
+      return launch<bf16_t, 1, 0, true, 2>(p, target_blocks, st);
+    if (mode == 0) return launch<bf16_t, 1, 0, false, 2>(p, target_blocks, st);      // (TEAMS as teams_of says)
     return launch<bf16_t, 1, 1>(p, target_blocks, st);
   }
   if (prec == CRIMAC_PREC_FP16) {
     if (mode == 0 && CS <= 16)
-      return two ? launch<half_t, 1, 0, true, 2>(p, target_blocks, st) : launch<half_t, 1, 0, true>(p, target_blocks, st);
-    if (mode == 0) return two ? launch<half_t, 1, 0, false, 2>(p, target_blocks, st) : launch<half_t, 1, 0>(p, target_blocks, st);
+      return launch<half_t, 1, 0, true, 2>(p, target_blocks, st);
+    if (mode == 0) return launch<half_t, 1, 0, false, 2>(p, target_blocks, st);
     return launch<half_t, 1, 1>(p, target_blocks, st);
   }
   if (prec == CRIMAC_PREC_F32X3)
@@ -1789,10 +1783,9 @@ extern "C" int crimac_wgrad_group_plan(int prec, crimac_wgrad_group_layer* layer
                                        int* items, int cap, int* counts) {
   if (int rc = group_check(prec, layers, n_layers, B)) return rc;
   CRIMAC_REQUIRE(counts, "wgrad_group_plan: counts is NULL");
-  static const int env_items = getenv("CRIMAC_WGRAD_GROUP_ITEMS") ? atoi(getenv("CRIMAC_WGRAD_GROUP_ITEMS")) : 0;
   // 128 items per layer: half the splits (and half the atomic volume) of one launch per layer, whose 256 splits were
   // there to fill the chip; measured equal to 256 within noise (bf16 step 11.73 vs 11.78 ms), 384 slower (11.91)
-  const int target = items_per_layer > 0 ? items_per_layer : (env_items > 0 ? env_items : 128);
+  const int target = items_per_layer > 0 ? items_per_layer : 128;
   int order[CRIMAC_WGRAD_GROUP_MAX_LAYERS];
   for (int i = 0; i < n_layers; ++i) {
     crimac_wgrad_group_layer& l = layers[i];
@@ -1873,24 +1866,18 @@ extern "C" int crimac_wgrad_group(int prec, const crimac_wgrad_group_layer* laye
   if (total == 0) return CRIMAC_OK;
   constexpr size_t lds = 4 * (size_t)((8 * 16 + ((8 + 2) * 18 + 7) / 8 * 8) * 128) + 64;
   hipStream_t st = (hipStream_t)stream;
-  int ncu = crimac_cu_count();
-  ncu = ncu / 8 * 8;                       // (equal shares of the 8 XCD queues)
-  if (ncu < 8) ncu = 8;
-  // Workgroups take `wg_items` items each and exit: the launch is then as many workgroups as that takes (the hardware
-  // keeps one per CU resident and starts the next as one retires), and kernels of OTHER streams get CUs in between -- a
-  // fully persistent grid (CRIMAC_WGRAD_GROUP_WGITEMS=0) holds every CU until its queue is empty, which blocks the input-
-  // gradient chain on the caller's stream for the whole launch.  Measured, bf16 step / serialized sum of the weight-
+  // A workgroup takes ONE item and exits: the launch is as many workgroups as that takes (the hardware keeps one per CU
+  // resident and starts the next as one retires), and kernels of OTHER streams get CUs in between -- a fully persistent
+  // grid (max_items = 0, which the kernels still understand) holds every CU until its queue is empty, which blocks the
+  // input-gradient chain on the caller's stream for the whole launch.  Measured, bf16 step / serialized sum of the weight-
   // gradient launches: persistent 11.79 ms / 2.90 ms, 3 items 11.70 / 3.65 (the last round of workgroups is ragged --
   // in the step the other stream's kernels fill it, alone it is idle CUs), 2 items 11.80 / 3.13, 1 item 11.77 / 2.93;
   // one launch per layer 11.93 / 3.19.  One item per workgroup: nothing left of "persistent" but the shared queue -- the
   // flush of a finished workgroup still drains under its neighbours' MFMAs, which is what the grouping is for.
-  static const int wg_items = getenv("CRIMAC_WGRAD_GROUP_WGITEMS") ? atoi(getenv("CRIMAC_WGRAD_GROUP_WGITEMS")) : 1;
-  gp.max_items = wg_items;
-  if (wg_items > 0) {
-    int per_xcd = 0;
-    for (int x = 0; x < 8; ++x) { const int n = cdiv(counts[x], wg_items); if (n > per_xcd) per_xcd = n; }
-    ncu = 8 * per_xcd;
-  }
+  gp.max_items = 1;
+  int per_xcd = 0;
+  for (int x = 0; x < 8; ++x) if (counts[x] > per_xcd) per_xcd = counts[x];
+  const int ncu = 8 * per_xcd;             // (equal shares of the 8 XCD queues)
   if (prec == CRIMAC_PREC_H3P) {
     static unsigned long long attr_devs = 0;
     if (crimac_first_use_on_device(&attr_devs))

@@ -114,8 +114,7 @@ class UNetEngine:
         # first form that ran the whole fp16 backward pass on fp16 copies of y was 4e-2 off on the first layer's gradient:
         # rounding y flips ReLU masks and pool positions (discrete errors), rounding a gradient does not.
         self.bwd16 = precision == "h3f"
-        env = os.environ.get("CRIMAC_FUSE_UNPOOL_APPLY")
-        self.fuse_unpool_apply = (env != "0") if env is not None else precision not in ("bf16", "fp16")
+        self.fuse_unpool_apply = precision not in ("bf16", "fp16")
         if self.bwd16:
             self.prec_bwd = hip.PREC_H3F_BWD
         self._scale_state = None            # int32[2] on the GPU: [overflow this step, steps skipped]
@@ -170,10 +169,9 @@ class UNetEngine:
             if bad:
                 raise NotImplementedError(f"precision 'h3f': transposed convolutions {bad} lie outside the fused input-gradient "
                                           "kernel (Cout % 64, Cin % 128); precision 'h3p' covers them")
-            off = [n for n, v in (("CRIMAC_FUSE_BNB", self.fuse_bn_bwd), ("CRIMAC_FUSE_UPBNB", self.fuse_up_bnb)) if not v]
-            if off or not self.lds_dma:
+            if not self.fuse_bn_bwd or not self.lds_dma:
                 raise NotImplementedError("precision 'h3f' needs the fused BatchNorm-backward kernels"
-                                          + (f" ({', '.join(off)} = 0 switches them off)" if off else "")
+                                          + ("" if self.fuse_bn_bwd else " (fuse_bn_bwd is off)")
                                           + "; precision 'h3p' runs without them")
         self.blocks = [b for pair in self.enc for b in pair] + [b for pair in self.dec for b in pair]
         for k, b in enumerate(self.blocks):
@@ -283,22 +281,17 @@ class UNetEngine:
             # plane: N = cout in multiples of 128 and whole 64-deep chunks (of halves: 32 channels of a plane pair);
             # input-gradient plane: N = cin likewise -- except a decoder block's conv1 whose two d(concat) halves (cin / 2
             # channels each) are launched separately and are not multiples of 128
-            wf = self.wfrag and (self.is16 or self.is_hp) and self.conv_impl == "halo"
+            wf = self.is16 or self.is_hp
             kq = 32 if self.is_hp else 64
             split_ok = not (b.cin == 2 * b.cout and (b.cin // 2) % 128 != 0)
             self.pk[b.conv_key]["fwd_frag"] = bool(wf and b.cout % 128 == 0 and b.cin_pad % kq == 0)
             self.pk[b.conv_key]["dg_frag"] = bool(wf and has_dg and b.cin % 128 == 0 and b.cout % kq == 0 and split_ok)
-            # rows form of the channel-split kernel (CRIMAC_EPI_WROWS, 16-bit storage): 64-channel tiles, fragment-major planes
-            fr, dr = self._rows_choice(b, has_dg) if (wf and self.is16) else (False, False)
-            self.pk[b.conv_key]["fwd_rows"], self.pk[b.conv_key]["dg_rows"] = fr, dr
-            self.pk[b.conv_key]["fwd_frag"] |= fr
-            self.pk[b.conv_key]["dg_frag"] |= dr
             self.pk[b.conv_key]["frag_ok"] = (self.pk[b.conv_key]["fwd_frag"], self.pk[b.conv_key]["dg_frag"])
             self.pk_eval[b.conv_key] = {
                 "fwd_hi": torch.empty(m_hi * n_f, dtype=i16, device=dev),
                 "fwd_lo": torch.empty(8 if il else n_lo * n_f, dtype=i16, device=dev),
                 "bias": torch.empty(b.cout, dtype=torch.float32, device=dev),
-                "fwd_frag": self.pk[b.conv_key]["fwd_frag"], "fwd_rows": fr,
+                "fwd_frag": self.pk[b.conv_key]["fwd_frag"],
             }
         for u in self.ups:
             if u.narrow:
@@ -331,11 +324,8 @@ class UNetEngine:
                     "dg_lo": torch.empty(8, dtype=i16, device=dev) if has_dg else None,
                     # (the fp16 personality's input-gradient planes: the 16-bit rule)
                     "fwd_frag": False,
-                    "dg_frag": bool(self.wfrag and self.conv_impl == "halo" and has_dg and b.cin % 128 == 0 and b.cout % 64 == 0
+                    "dg_frag": bool(has_dg and b.cin % 128 == 0 and b.cout % 64 == 0
                                     and not (b.cin == 2 * b.cout and (b.cin // 2) % 128 != 0))}
-                dr = self._rows_choice(b, has_dg)[1] if (self.wfrag and self.conv_impl == "halo") else False
-                self.pk16[b.conv_key]["dg_rows"] = dr
-                self.pk16[b.conv_key]["dg_frag"] |= dr
                 self.pk16[b.conv_key]["frag_ok"] = (False, self.pk16[b.conv_key]["dg_frag"])
             for u in self.ups:
                 n = 4 * u.cin * u.cout
@@ -377,7 +367,7 @@ class UNetEngine:
     # launches of a step and their dependency bubbles).  Every consumer workgroup then reads replicas x C fp64 pairs
     # from L2, so wide layers use fewer replicas (they also have fewer producer workgroups per address): replicas x C <= 4096 is
     # 16 pairs per thread, one batch of loads.
-    fold_bn_finalize = os.environ.get("CRIMAC_FOLD_BNFIN", "1") != "0"
+    fold_bn_finalize = True
 
     def _nrep(self, c):
         """Replica accumulators a producer spreads the per-channel sums of a c-channel BatchNorm layer over."""
@@ -554,8 +544,7 @@ class UNetEngine:
     # behind it are filled by the other.  The packed gradients are joined back before they are unpacked.
     # (CRIMAC_WGRAD_STREAM = number of side streams, round-robin; 0 = everything on the caller's stream)
     wgrad_side_streams = int(os.environ.get("CRIMAC_WGRAD_STREAM", "1"))
-    unpack_on_side = os.environ.get("CRIMAC_UNPACK_SIDE", "1") != "0"
-    early_sgd = os.environ.get("CRIMAC_EARLY_SGD", "1") != "0"
+    early_sgd = True
     # N > 1: apply SGD / re-pack per gradient range behind GradSync.finish_range instead of one optimiser step behind
     # finish().  OPT-IN until it has run on a multi-GPU node: its RCCL branches (stream-ordered waits, chained
     # reduce-scatter + all-gather, per-range re-pack) are covered by a single-rank nccl test and a 2-rank test that
@@ -564,8 +553,6 @@ class UNetEngine:
     # bench.py (N > 1): list that receives (event after the backward pass, event after the last collective was waited
     # for) per step -- the part of the gradient exchange the step could not hide
     exchange_probe = None
-    early_pack = os.environ.get("CRIMAC_EARLY_PACK", "1") != "0"
-    split_skip_dgrad = os.environ.get("CRIMAC_SPLIT_SKIP", "1") != "0"    # skip half of decoder dgrads on the side stream
     # launch the gradient collectives from the side stream too (they then never hold up the caller's stream)
     exchange_on_side = os.environ.get("CRIMAC_EXCHANGE_SIDE", "0") != "0"
     _side = None
@@ -587,15 +574,14 @@ class UNetEngine:
     # ending every launch (0.44 ms of the 12.0 ms bf16 step in the no-flush ablation).  The layers are collected while the
     # backward pass walks them (their dy buffers stay alive: one per block) and launched where the group's gradient range
     # is handed on (_unpack_group), or earlier once `wgrad_group_layers` of them are waiting.
-    # CRIMAC_WGRAD_GROUP=0: one launch per layer (crimac_wgrad), as before.
+    # wgrad_group = False: one launch per layer (crimac_wgrad), as before.
     # Plane pairs (h3p): measured SLOWER grouped (step 25.34 ms with one launch per layer; 25.6 grouped with one item per
     # workgroup, 25.8-26.1 with persistent workgroups) although the launches themselves get faster alone (6.54 -> 6.3 ms
     # serialized): the long plane-pair items leave the input-gradient chain on the caller's stream waiting for CUs.  Off
-    # for h3p unless CRIMAC_WGRAD_GROUP_H3P=1.
-    wgrad_group = os.environ.get("CRIMAC_WGRAD_GROUP", "1") != "0"
-    wgrad_group_h3p = os.environ.get("CRIMAC_WGRAD_GROUP_H3P", "0") != "0"
-    wgrad_group_layers = int(os.environ.get("CRIMAC_WGRAD_GROUP_LAYERS", str(hip.WGRAD_GROUP_MAX_LAYERS)))
-    wgrad_group_items = int(os.environ.get("CRIMAC_WGRAD_GROUP_ITEMS", "0"))      # items per layer (0: the library's default)
+    # for h3p unless wgrad_group_h3p is set.
+    wgrad_group = True
+    wgrad_group_h3p = False
+    wgrad_group_layers = hip.WGRAD_GROUP_MAX_LAYERS
     _wg_pending = None
 
     def _groupable(self, prec, mode, cf, cs):
@@ -607,7 +593,7 @@ class UNetEngine:
 
     def _group_plan(self, B, shapes):
         """Planned layer array, device copy of the 8 item queues, their lengths -- cached per geometry."""
-        key = (self.prec_bwd, B, self.wgrad_group_items, shapes)
+        key = (self.prec_bwd, B, shapes)
         plan = self._wg_plans.get(key)
         if plan is None:
             lib = hip.load_library()
@@ -615,12 +601,12 @@ class UNetEngine:
             for d, (cf, cs, h, w, f_ld, s_ld) in zip(arr, shapes):
                 d.CF, d.CS, d.Hf, d.Wf, d.f_ld, d.s_ld = cf, cs, h, w, f_ld, s_ld
             counts = (C.c_int * 8)()
-            cap = lib.crimac_wgrad_group_plan(self.prec_bwd, arr, len(shapes), B, self.wgrad_group_items, None, 0, counts)
+            cap = lib.crimac_wgrad_group_plan(self.prec_bwd, arr, len(shapes), B, 0, None, 0, counts)      # (0 items per layer: the library's 128)
             if cap < 0:
                 raise hip.HipLibraryError("crimac_wgrad_group_plan failed: " + lib.crimac_last_error().decode(errors="replace"))
             items = torch.zeros(8 * max(cap, 1) * 2, dtype=torch.int32)
-            rc = lib.crimac_wgrad_group_plan(self.prec_bwd, arr, len(shapes), B, self.wgrad_group_items,
-                                             C.c_void_p(items.data_ptr()), max(cap, 1), counts)
+            rc = lib.crimac_wgrad_group_plan(self.prec_bwd, arr, len(shapes), B, 0, C.c_void_p(items.data_ptr()), max(cap, 1),
+                                             counts)
             if rc < 0:
                 raise hip.HipLibraryError("crimac_wgrad_group_plan failed: " + lib.crimac_last_error().decode(errors="replace"))
             plan = (arr, items.to(self.device), counts, max(cap, 1))
@@ -665,15 +651,8 @@ class UNetEngine:
             side.wait_event(ev)
             fn()
 
-    # (ablation runs only, tools/runs/r5_14.sh: 'single' skips the launches that are not part of a grouped launch -- first
-    # layer and transposed convolutions --, 'all' skips every weight gradient; gradients are then WRONG, the step time shows
-    # what those launches cost the step beyond what the side stream hides)
-    _skip_wgrad = os.environ.get("CRIMAC_EXP_SKIP_WGRAD", "")
-
     def _wgrad(self, prec, mode, f, f_ld, cf, s_, s_ld, cs, B, h, w, key, flops=None):
         dwt, sp, stride = self._dw(key)
-        if self._skip_wgrad == "all" or (self._skip_wgrad == "single" and not self._groupable(prec, mode, cf, cs)):
-            return
         if self._groupable(prec, mode, cf, cs):
             self._wg_pending.append(dict(f=f, f_ld=f_ld, cf=cf, s=s_, s_ld=s_ld, cs=cs, B=B, h=h, w=w, dw=dwt,
                                          flops=flops or 0.0))
@@ -701,7 +680,7 @@ class UNetEngine:
         self._flush_wgrad_group()                     # the group's conv3x3 weight gradients: one persistent launch
         arr, bounds = self._layer_table()
         first, n = bounds[gi]
-        side = self._side[0] if (self._side is not None and len(self._side) == 1 and self.unpack_on_side) else None
+        side = self._side[0] if (self._side is not None and len(self._side) == 1) else None
         if side is not None:
             # bias / BatchNorm gradients of the range are written on the caller's stream: order them first
             ev = self._side_events[self._side_i % len(self._side_events)]
@@ -820,34 +799,16 @@ class UNetEngine:
     # ------------------------------------------------------------------------------------------
     # kernels wrappers
     # ------------------------------------------------------------------------------------------
-    conv_impl = os.environ.get("CRIMAC_CONV_IMPL", "halo")     # 'halo' (conv3x3.hip) | 'gather' (igemm.hip)
-    fuse_bn_bwd = os.environ.get("CRIMAC_FUSE_BNB", "1") != "0"   # BN-backward sums inside the dgrad conv
+    fuse_bn_bwd = True            # BN-backward sums inside the dgrad conv and the transposed-conv dgrad
     # encoder levels: d(block output) = d(skip) + unpool(d(pooled)) is rebuilt by the BatchNorm-backward apply pass instead
     # of being stored by crimac_unpool_add and read back (crimac_unpool_bn_bwd_apply_replicas).  Default (set in __init__):
     # on where the gradient is stored in 4 bytes (h3p / h3f / fp32 modes: -0.10 to -0.17 ms of an 18 ms h3f step); off for
     # 16-bit storage, where the sums-only pass is bound by its arithmetic, not by the bytes it no longer writes (bf16:
-    # 11.39-11.44 -> 11.42-11.46 ms, same box).  CRIMAC_FUSE_UNPOOL_APPLY=0/1 forces it.
+    # 11.39-11.44 -> 11.42-11.46 ms, same box).
     fuse_unpool_apply = None
-    fuse_eval_pool = os.environ.get("CRIMAC_FUSE_EVAL_POOL", "1") != "0"   # eval: max-pool in the conv epilogue
-    fuse_up_bnb = os.environ.get("CRIMAC_FUSE_UPBNB", "1") != "0"  # ... and inside the transposed-conv dgrad
     # BatchNorm+ReLU of the last decoder block applied inside the 1x1 head (needs fuse_bn_bwd: the head's backward
     # rebuilds its input from the y it reads for the fused sums)
-    fuse_head_bn = fuse_bn_bwd and os.environ.get("CRIMAC_FUSE_HEADBN", "1") != "0"
-    wfrag = os.environ.get("CRIMAC_WFRAG", "1") != "0"      # fragment-major weight planes for the channel-split kernel (16-bit modes)
-    # rows form of the channel-split kernel (CRIMAC_EPI_WROWS): "0" off, "64" the 64-output-channel launches that the tall form
-    # runs otherwise, "all" every legal layer (A/B runs: slower than the 128-channel form wherever that one applies)
-    conv_rows = os.environ.get("CRIMAC_CONV_ROWS", "0")
-
-    def _rows_choice(self, b, has_dg):
-        """(forward, input gradient) of block b on the rows form.  Not where the persistent 64 -> 64 kernel runs (it reads
-        row-major planes): the 64 -> 64 layers and the two 64-channel d(concat) halves of the last decoder block."""
-        if self.conv_rows not in ("64", "all") or self.conv_impl != "halo" or (b.cin == 64 and b.cout == 64):
-            return False, False
-        fwd = b.cout % 64 == 0 and b.cin_pad % 64 == 0
-        dg = has_dg and b.cin % 64 == 0 and b.cout % 64 == 0 and not (b.cin == 2 * b.cout and b.cin // 2 == 64)
-        if self.conv_rows == "64":
-            fwd, dg = fwd and b.cout == 64, dg and b.cin == 64
-        return bool(fwd), bool(dg)
+    fuse_head_bn = True
 
     def _conv3x3(self, x: Act, pk, bias, out: Act, B, H, W, cin, cout, relu, dgrad=False, cin_real=None,
                  stats=None, bnb=None, cols=None, out_planes=False, stat_reps=None):
@@ -865,35 +826,24 @@ class UNetEngine:
         w_hi, w_lo = ptr(pk["dg_hi" if dgrad else "fwd_hi"]), ptr(pk["dg_lo" if dgrad else "fwd_lo"])
         if pk.get("dg_frag" if dgrad else "fwd_frag"):
             relu |= hip.EPI_WFRAG         # (the plane was packed fragment-major: _alloc_static)
-            if pk.get("dg_rows" if dgrad else "fwd_rows"):
-                relu |= hip.EPI_WROWS
         prec = self.prec_bwd if dgrad else self.prec
-        if self.conv_impl == "halo":
-            mode, s0, s1, by, by_ld, bvec = 0, None, None, None, 0, None
-            reps = stat_reps or self._nrep(cout)      # (BatchNorm sums of the cout-channel layer this output belongs to)
-            if stats is not None:
-                mode, s0, s1 = 1, ptr(stats[0]), ptr(stats[1])
-            elif bnb is not None and self.fuse_bn_bwd:
-                blk, y = bnb
-                mode, s0, s1 = 2, ptr(self._stat(blk, 0)), ptr(self._stat(blk, 1))
-                by, by_ld, bvec = y.p, y.ld, ptr(self._bnf(blk, 0))
-            if cols is not None:                      # a range of the output channels (crimac_conv3x3_cols)
-                call("crimac_conv3x3_cols", prec, x.p, x.ld, B, H, W, cin, cout, w_hi, w_lo, ptr(bias),
-                     out.p, out.ld, relu, mode, s0, s1, reps, by, by_ld, bvec, self.cmax,
-                     cols[0], cols[1], flops=flops * cols[1] / cout, mfmas=hip.MFMAS_PER_PRODUCT[prec])
-                return mode != 0
-            call("crimac_conv3x3", prec, x.p, x.ld, B, H, W, cin, cout, w_hi, w_lo, ptr(bias),
+        mode, s0, s1, by, by_ld, bvec = 0, None, None, None, 0, None
+        reps = stat_reps or self._nrep(cout)      # (BatchNorm sums of the cout-channel layer this output belongs to)
+        if stats is not None:
+            mode, s0, s1 = 1, ptr(stats[0]), ptr(stats[1])
+        elif bnb is not None and self.fuse_bn_bwd:
+            blk, y = bnb
+            mode, s0, s1 = 2, ptr(self._stat(blk, 0)), ptr(self._stat(blk, 1))
+            by, by_ld, bvec = y.p, y.ld, ptr(self._bnf(blk, 0))
+        if cols is not None:                      # a range of the output channels (crimac_conv3x3_cols)
+            call("crimac_conv3x3_cols", prec, x.p, x.ld, B, H, W, cin, cout, w_hi, w_lo, ptr(bias),
                  out.p, out.ld, relu, mode, s0, s1, reps, by, by_ld, bvec, self.cmax,
-                 flops=flops, mfmas=hip.MFMAS_PER_PRODUCT[prec])
+                 cols[0], cols[1], flops=flops * cols[1] / cout, mfmas=hip.MFMAS_PER_PRODUCT[prec])
             return mode != 0
-        if self.is_hp:
-            raise NotImplementedError("precision 'h3p' runs on the halo convolution kernels only (CRIMAC_CONV_IMPL=halo)")
-        call("crimac_igemm_conv", prec, x.p, x.ld, B, H, W, H, W, cin, cout, 9, 3, 1, 1, w_hi, w_lo,
-             ptr(bias), cout, out.p, out.ld, relu, 0, 0, flops=flops, mfmas=hip.MFMAS_PER_PRODUCT[prec])
-        if stats:
-            call("crimac_colstats", self.prec, out.p, out.ld, B * H * W, cout, ptr(stats[0]), ptr(stats[1]))
-            return True
-        return False
+        call("crimac_conv3x3", prec, x.p, x.ld, B, H, W, cin, cout, w_hi, w_lo, ptr(bias),
+             out.p, out.ld, relu, mode, s0, s1, reps, by, by_ld, bvec, self.cmax,
+             flops=flops, mfmas=hip.MFMAS_PER_PRODUCT[prec])
+        return mode != 0
 
     def _conv3x3_narrow(self, x: Act, pk, bias, out: Act, B, H, W, cin, cout, flags, dgrad, stats, cols, stat_reps, flops):
         """crimac_conv3x3_narrow: forward (cin = channels read, cout = outputs) or input gradient (cin = the layer's cout,
@@ -910,12 +860,10 @@ class UNetEngine:
              s0, s1, stat_reps or self._nrep(cout), cout, flops=flops * n / cout, mfmas=1 if self._narrow_mfma(prec) else 0)
         return stats is not None
 
-    narrow_valu = os.environ.get("CRIMAC_NARROW_VALU", "0") != "0"     # (csrc/narrow.hip reads the same switch)
-
     def _narrow_mfma(self, prec):
         """crimac_conv3x3_narrow runs on the matrix pipe (16-bit storage) or on the VALU (4-byte storage; profiled with
         mfmas=0 so that no MFMA roofline counts its FLOPs)."""
-        return prec in hip.PREC_16BIT and not self.narrow_valu
+        return prec in hip.PREC_16BIT
 
     def _bnb_args(self, blk, y):
         """The seven trailing arguments of a producer kernel that also takes the BatchNorm-backward sums of the
@@ -967,7 +915,7 @@ class UNetEngine:
         pk = self._pk_bwd(u.key)
         hp_in = self.is_hp and not self.bwd16          # (dy is a plane-pair tensor: 8 bytes per element of halves)
         prec = self.prec_bwd if self.bwd16 else self.prec
-        if (next_bn is not None and self.fuse_bn_bwd and self.fuse_up_bnb and self.lds_dma
+        if (next_bn is not None and self.fuse_bn_bwd and self.lds_dma
                 and u.cout % (32 if hp_in else 64) == 0 and u.cin % 128 == 0
                 and (16 if hp_in else 8) * B * H * W * dy.ld < (1 << 31)):
             blk, y = next_bn
@@ -991,8 +939,6 @@ class UNetEngine:
 
     def _wgrad1x1(self, dz: Act, x: Act, u, M):
         """dW[cout][cin] += dz^T x on the coarse grid (crimac_conv1x1_wgrad), on the weight-gradient side stream."""
-        if self._skip_wgrad in ("all", "single"):
-            return
         dwt, _, _ = self._dw(u.key)
         args = (self.prec_bwd, dz.p, dz.ld, u.cout, x.p, x.ld, u.cin, M, ptr(dwt))
         self._on_side(lambda: call("crimac_conv1x1_wgrad", *args, flops=2.0 * u.cin * u.cout * M, mfmas=1))
@@ -1224,13 +1170,12 @@ class UNetEngine:
                 pe1, pe2 = self.pk_eval[b1.conv_key], self.pk_eval[b2.conv_key]
                 self._conv3x3(cur, pe1, pe1["bias"], a1, B, h, w, b1.cin_pad, c, relu=True, cin_real=b1.cin,
                               out_planes=True)
-                if pool is not None and self.fuse_eval_pool and self.conv_impl == "halo" and not b2.narrow:
+                if pool is not None and not b2.narrow:
                     # the max-pool comes out of the conv epilogue (the tile is still in LDS)
                     call("crimac_conv3x3_pool", self.prec, a1.p, a1.ld, B, h, w, c, c, ptr(pe2["fwd_hi"]),
                          ptr(pe2["fwd_lo"]), ptr(pe2["bias"]), a2.p, a2.ld,
                          hip.EPI_RELU | (hip.EPI_OUT_PLANES if self.is_hp else 0)
-                         | (hip.EPI_WFRAG if pe2.get("fwd_frag") else 0)
-                         | (hip.EPI_WROWS if (pe2.get("fwd_frag") and pe2.get("fwd_rows")) else 0), pool.p, pool.ld,
+                         | (hip.EPI_WFRAG if pe2.get("fwd_frag") else 0), pool.p, pool.ld,
                          flops=2.0 * 9 * c * c * B * h * w, mfmas=hip.MFMAS_PER_PRODUCT[self.prec])
                 else:
                     self._conv3x3(a1, pe2, pe2["bias"], a2, B, h, w, c, c, relu=True, out_planes=True)
@@ -1357,14 +1302,14 @@ class UNetEngine:
         fused = False
         if dx_out is not None:
             stats = None
-            if bias_from_stats is not None and self.conv_impl == "halo":
+            if bias_from_stats is not None:
                 per = 2 * STAT_REPLICAS * 2 * self.cmax                  # this level's slice (zeroed in backward())
                 lvl = bias_from_stats[2]
                 scr = self.bias_scr[lvl * per:(lvl + 1) * per]
                 stats = (scr[:per // 2], scr[per // 2:])
             C_up = bias_from_stats[1] if bias_from_stats is not None else 0
             side = self._side[0] if (self._side is not None and len(self._side) == 1) else None
-            side_ok = side is not None and self.split_skip_dgrad and not self._gloo_ranks()
+            side_ok = side is not None and not self._gloo_ranks()      # skip half of decoder dgrads on the side stream
             if b.narrow and bias_from_stats is not None:
                 # narrow decoder conv1: the up half of d(concat) (plane pairs in h3p: it feeds two contractions) with its
                 # column sums, then the skip half -- on the side stream when there is one, as below
@@ -1759,7 +1704,7 @@ class UNetEngine:
                     scale = grad_sync(self.flat_g)
             self.sgd_step(lr, momentum, grad_scale=scale / ls, guarded=True)
             return (sums[0] / sums[1]).float()
-        if single and self.early_sgd and self._side is not None and len(self._side) == 1 and self.unpack_on_side:
+        if single and self.early_sgd and self._side is not None and len(self._side) == 1:
             self._sgd_left = None
             self.mark_dirty()                         # (before the early re-packs register themselves)
             self.backward(dl, before_join=lambda: self._early_sgd(lr, momentum))
@@ -1786,9 +1731,8 @@ class UNetEngine:
                         e1.record()                   # (the last range's collectives have been waited for)
                         self.exchange_probe.append((e0, e1))
                     self._sgd_range(lo, hi, lr, momentum, scale)
-                    if self.early_pack:
-                        self._pack_group(g)
-                        self._packed_groups.add(g)
+                    self._pack_group(g)
+                    self._packed_groups.add(g)
                 grad_sync.finish()
                 return (sums[0] / sums[1]).float()
             scale = finish_exchange()
@@ -1811,9 +1755,8 @@ class UNetEngine:
                 continue
             torch.cuda.current_stream().wait_event(ev)
             self._sgd_range(lo, hi, lr, momentum)
-            if self.early_pack:
-                self._pack_group(g)                   # its weight planes for the next step, while this stream is idle
-                self._packed_groups.add(g)
+            self._pack_group(g)                       # its weight planes for the next step, while this stream is idle
+            self._packed_groups.add(g)
         self._sgd_left = left
 
     def _sgd_range(self, lo, hi, lr, momentum, grad_scale=1.0):

@@ -12,10 +12,8 @@
  *   - every pointer is a raw DEVICE pointer owned by the caller (workspaces included); the library
  *     allocates nothing; one process per GPU, re-entrant per stream.  Process state it does keep: the
  *     thread-local last-error text; one-time per-DEVICE kernel attribute setup (dynamic-LDS limits, CU count;
- *     keyed on hipGetDevice, so several GPUs in one process work); and A/B tuning switches read ONCE from the
- *     environment at first use and constant afterwards (CRIMAC_CONV_W4, CRIMAC_CONV_P64, CRIMAC_CONV_TR,
- *     CRIMAC_CONV_BK, CRIMAC_CONV_GLDS, CRIMAC_UPCONV_WCH, CRIMAC_WGRAD_BLOCKS, CRIMAC_BNB_STREAM -- kernel-selection experiments
- *     only; results do not depend on them beyond summation order).  Reductions that use floating-point
+ *     keyed on hipGetDevice, so several GPUs in one process work).  The library reads no environment variable: which
+ *     kernel runs depends on the arguments alone.  Reductions that use floating-point
  *     atomics (BatchNorm sums, bias gradients) are not bit-reproducible run to run; everything on the
  *     inference path is
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); all work is asynchronous
@@ -229,7 +227,7 @@ int crimac_wgrad(int prec, int mode, const void* f, long f_ld, int CF, const voi
  * aten::convolution_backward, one layer at a time (loss.backward(), pipeline.py:177).
  *   crimac_wgrad_group_plan (HOST ONLY, no stream): fills the planned fields of layers[] and the queues -- items
  *     [8][cap][2] int32 host array (NULL: sizing call), counts[8]; returns the queue capacity the plan needs (>= 0) or a
- *     negative error.  items_per_layer <= 0: default (128, CRIMAC_WGRAD_GROUP_ITEMS overrides).  The plan depends on the
+ *     negative error.  items_per_layer <= 0: default (128).  The plan depends on the
  *     shapes and B only, not on the pointers.
  *   crimac_wgrad_group: layers[] as planned (f, s, dw set), items = the DEVICE copy of the planned queues, counters =
  *     8 device uint32 ZEROED by the caller before every launch. */

@@ -282,3 +282,22 @@ def test_collate_float32_gives_the_values_of_the_reference_cast(workers):
     assert t.dtype == torch.float64 and t.shape == (2, 3)
     f = staging.collate_float32([{"data": np.ones((2, 2), np.float32)}, {"data": np.zeros((2, 2), np.float32)}])
     assert f["data"].dtype == torch.float32
+
+
+def test_environment_switches_are_the_ones_integration_md_lists():
+    """Every CRIMAC_* variable the C library (getenv) or the package (os.environ) reads is a row of the table "Environment
+    switches that exist" in INTEGRATION.md, and every row of that table is still read somewhere: a switch can neither be
+    added without being documented nor stay documented after it is gone."""
+    import glob
+    read = set()
+    for path in glob.glob(os.path.join(ROOT, "crimac_classifiers_unet_amd", "csrc", "*")):
+        read |= set(re.findall(r"getenv\(\s*\"(CRIMAC_[A-Z0-9_]+)\"", open(path).read()))
+    for path in glob.glob(os.path.join(ROOT, "crimac_classifiers_unet_amd", "**", "*.py"), recursive=True):
+        read |= set(re.findall(r"os\.environ(?:\.get\(|\[)\s*\"(CRIMAC_[A-Z0-9_]+)\"", open(path).read()))
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = text.split("### Environment switches that exist", 1)[1]
+    table = next(par for par in section.split("\n\n") if par.startswith("|"))
+    rows = table.splitlines()
+    listed = set(re.findall(r"^\|\s*`(CRIMAC_[A-Z0-9_]+)`", "\n".join(rows), flags=re.M))
+    assert len(rows) == len(listed) + 2, "one name per row below the two header lines"
+    assert read == listed, f"read but not listed: {sorted(read - listed)}; listed but not read: {sorted(listed - read)}"

@@ -1140,7 +1140,7 @@ def test_grouped_weight_gradients_equal_the_torch_reference(prec, items):
 @pytest.mark.parametrize("prec", list(LOWP) + ["h3p"])
 def test_backward_with_grouped_weight_gradients_equals_the_ungrouped_backward(prec):
     """The engine's backward pass with the conv3x3 weight gradients grouped per gradient range (the default), grouped three
-    layers at a time, and with one launch per layer (CRIMAC_WGRAD_GROUP=0) -- on the SAME saved forward pass (two forward
+    layers at a time, and with one launch per layer (UNetEngine.wgrad_group = False) -- on the SAME saved forward pass (two forward
     passes of a 16-bit net differ at rounding level and their gradients by O(10 %)): every gradient equal up
     to the order of the fp32 atomics."""
     import crimac_classifiers_unet_amd as pkg

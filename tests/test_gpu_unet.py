@@ -994,7 +994,7 @@ def test_fp16_loss_scale_overflow_skips_the_step_and_adapts():
 
 
 def test_bn_finalize_folded_into_the_consumers_equals_the_separate_launches():
-    """CRIMAC_FOLD_BNFIN (the BatchNorm statistics finished inside bn_train_act_pool / bn_bwd_apply_replicas)
+    """UNetEngine.fold_bn_finalize (the BatchNorm statistics finished inside bn_train_act_pool / bn_bwd_apply_replicas)
     against the separate bn_finalize / sum_replicas launches: running statistics, num_batches_tracked and every gradient
     of one training step agree -- on a net whose layers (128, 256, 512 channels) use three different reduced replica
     counts (the architecture admits only channel counts 64 * 2^k: the 1x1 head's kernels need start_filts = 8 * 2^k)."""
@@ -1025,7 +1025,7 @@ def test_bn_finalize_folded_into_the_consumers_equals_the_separate_launches():
 
 @pytest.mark.parametrize("prec", ["bf16", "fp16", "f32x6", "h3p", "h3f"])
 def test_unpool_gradient_rebuilt_by_the_bn_backward_pass_equals_the_stored_one(prec):
-    """CRIMAC_FUSE_UNPOOL_APPLY (round 4): at the encoder levels d(block output) = d(skip) + unpool(d(pooled)) is no longer
+    """UNetEngine.fuse_unpool_apply (round 4): at the encoder levels d(block output) = d(skip) + unpool(d(pooled)) is no longer
     stored by crimac_unpool_add and read back by the BatchNorm-backward apply pass -- the first pass takes the sums only and
     crimac_unpool_bn_bwd_apply_replicas rebuilds the gradient with the same arithmetic and storage rounding.  Every
     gradient of a training step equals the two-kernel path's (up to the order of the fp32 atomics of the weight

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bn_bwd_apply at the U-Net's shapes (B=32, bf16): streaming form vs the colreduce form (CRIMAC_BNB_STREAM=0)."""
+"""bn_bwd_apply at the U-Net's shapes (B=32, bf16): the streaming form (the colreduce form it replaced now runs only with a bias gradient, dbias != NULL)."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
