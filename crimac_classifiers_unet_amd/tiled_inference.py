@@ -28,7 +28,6 @@ from __future__ import annotations
 
 import time
 from concurrent.futures import ThreadPoolExecutor
-from contextlib import contextmanager
 
 import numpy as np
 import torch
@@ -490,7 +489,7 @@ class _OrderedHandoff:
                 yield s, e, buf.cpu().numpy() if self.device_tensors else buf.numpy().copy()      # (.cpu() is a fresh array; the host buffer is reused)
 
 
-_STAGING = {}          # (device, sizes) -> pinned / device staging buffers of predict_survey
+_STAGING = {}          # _ChunkFeed.key -> the staging set (pinned host slots, device slots, the caller's extras) kept last
 
 
 def release_staging():
@@ -499,23 +498,104 @@ def release_staging():
     _STAGING.clear()
 
 
-@contextmanager
-def _staging(key, factory):
-    """The staging buffers (pinned host + device) of one survey flow, kept between surveys of the same geometry:
-    ``factory()`` builds the dict of a new set.  Busy while the ``with`` block runs."""
-    bufs = _STAGING.get(key)
-    if bufs is None or bufs["busy"]:     # (busy: another flow over the same geometry is still running)
-        fresh = dict(factory(), busy=False)
-        if bufs is None:
-            _STAGING.clear()             # (one geometry at a time: the buffers are large)
-            _STAGING[key] = fresh
-        bufs = fresh
-    bufs["busy"] = True
-    try:
-        yield bufs
-    finally:
-        torch.cuda.current_stream().synchronize()     # (nothing of this survey still reads or writes the staging)
-        bufs["busy"] = False
+class _ChunkFeed:
+    """The chunk pipeline of ``predict_survey`` and ``evaluate_survey``: reader threads fill pinned host slots ahead of the
+    GPU, a copy stream uploads each chunk into one of two device slots while the chunk before it computes.
+
+    ``table`` {name: (elements, dtype)}: the flat buffers a chunk is staged in, one of each per host slot and per device
+    slot.  The set (+ the caller's ``extra()`` buffers) is kept in ``_STAGING`` between surveys of the same key -- ``tag``
+    (names the flow and whatever ``extra`` depends on), device, table, ``host_slots`` -- and is busy inside ``with``.
+    ``read(job, slot) -> (uploads, payload)`` runs on a reader thread and makes no GPU call of its own: ``slot()`` waits
+    until the host slot may be overwritten and returns its {name: pinned buffer}; ``uploads`` {name: view of that
+    buffer, or None} goes to the device, ``payload`` is whatever else the chunk's compute needs.
+    Iterating yields ``({name: device view or None}, payload)`` per job, ordered before the current stream; the caller
+    enqueues the chunk's compute there and then calls ``computed()``.  ``note(key, t0)``: host-timing hook
+    (``wait_fetch_s``, ``enq_upload_s``); ``t_taken`` / ``t_uploaded``: when the read was taken / the uploads enqueued."""
+    # Slot reuse.  Chunk j lives in host slot j % host_slots and in device slot j & 1.  host_slots is the read-ahead depth
+    # + 1: while chunk i is uploaded the reads of chunks i+1 .. i+depth run.  The read of chunk j is SUBMITTED only after the
+    # `uploaded` event of chunk j - host_slots, the last user of its host slot, has been RECORDED: the reader's wait on that
+    # event is then a wait for that very upload.  The upload of chunk j waits for the `computed` event of chunk j - 2.
+
+    def __init__(self, dev, tag, table, host_slots, jobs, read, extra=None, note=None):
+        self.dev, self.table, self.slots, self.jobs, self.read, self.extra = dev, dict(table), host_slots, jobs, read, extra
+        self.note = note or (lambda key, t0: None)
+        self.key = (tag, str(dev), tuple(self.table.items()), host_slots)
+
+    def _allocate(self):
+        def slot(**where):
+            return {name: torch.empty(n, dtype=dt, **where) for name, (n, dt) in self.table.items()}
+        return dict({"host": [{name: t.pin_memory() for name, t in slot().items()} for _ in range(self.slots)],
+                     "dev": [slot(device=self.dev) for _ in range(2)], "busy": False}, **(self.extra() if self.extra else {}))
+
+    def __enter__(self):
+        self.uploaded = [torch.cuda.Event() for _ in range(self.slots)]   # host slot may be overwritten once this has passed
+        self.computed_ev = [torch.cuda.Event() for _ in range(2)]         # device slot may be overwritten once this has passed
+        self.copy_stream = torch.cuda.Stream(device=self.dev)
+        self.main = torch.cuda.current_stream()
+        self.n_uploaded = 0
+        bufs = _STAGING.get(self.key)
+        if bufs is None or bufs["busy"]:     # (busy: another flow over the same geometry is still running: a private set)
+            fresh = self._allocate()
+            if bufs is None:
+                _STAGING.clear()             # (one geometry at a time: the buffers are large)
+                _STAGING[self.key] = fresh
+            bufs = fresh
+        self.pool = ThreadPoolExecutor(max_workers=self.slots - 1)
+        self.bufs = bufs
+        bufs["busy"] = True
+        return self
+
+    def __exit__(self, *exc):
+        self.pool.shutdown(wait=True)                 # (no reader of this survey still writes the staging ...
+        torch.cuda.current_stream().synchronize()     #  ... and nothing on the GPU still reads or writes it)
+        self.bufs["busy"] = False
+
+    def _submit(self, j):
+        assert j - self.slots < self.n_uploaded, "chunk feed: the last upload from this host slot has not been recorded"
+        ev, host = self.uploaded[j % self.slots], self.bufs["host"][j % self.slots]
+
+        def slot():
+            ev.synchronize()                          # (no-op until the slot has been used)
+            return host
+        return self.pool.submit(self.read, self.jobs[j], slot)
+
+    def __iter__(self):
+        depth, n = self.slots - 1, len(self.jobs)
+        futs = {j: self._submit(j) for j in range(min(depth, n))}
+        for i in range(n):
+            t0 = time.perf_counter()
+            uploads, payload = futs.pop(i).result()
+            self.note("wait_fetch_s", t0)
+            self.t_taken = time.perf_counter()
+            if i + depth < n:
+                futs[i + depth] = self._submit(i + depth)
+            self.slot = i & 1
+            views = dict.fromkeys(uploads)
+            with torch.cuda.stream(self.copy_stream):
+                self.copy_stream.wait_event(self.computed_ev[self.slot])
+                for name, t in uploads.items():
+                    if t is not None:
+                        views[name] = self.bufs["dev"][self.slot][name][:t.numel()].view(t.shape)
+                        views[name].copy_(t, non_blocking=True)
+                self.uploaded[i % self.slots].record()
+            self.n_uploaded = i + 1
+            self.note("enq_upload_s", self.t_taken)
+            self.t_uploaded = time.perf_counter()
+            self.main.wait_stream(self.copy_stream)
+            yield views, payload
+
+    def computed(self):
+        """The compute of the chunk handed out last has been enqueued on the current stream."""
+        self.computed_ev[self.slot].record()
+
+
+def _load_staged(cp, data, lo, labels, s, e, seabed, mask, wide=False):
+    """``load_chunk`` of an uploaded chunk whose data (and ``seabed`` vector) start at ping ``lo``: by the seabed vector,
+    or -- ``seabed_vector_or_mask`` found a mask the vector rule cannot express -- by that mask, uploaded as it is."""
+    if mask is None:
+        cp.load_chunk(data, lo, labels, None, s, e, seabed=seabed, seabed_ping0=lo, wide=wide)
+    else:
+        cp.load_chunk(data, lo, labels, mask, s, e, wide=wide)
 
 
 def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings,
@@ -581,145 +661,104 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
     widest = max(e - s for s, e in chunks)
     halo = patch_size[1]
     n_data = n_freq * (widest + 2 * halo) * n_range
-    NS = 3                               # host staging slots: two chunks are being read while one is uploaded
     max_patches = 4 * (widest // (patch_size[0] - 2 * patch_overlap) + 2) * (n_range // (patch_size[1] - 2 * patch_overlap) + 2)
     n_misc = (widest + 2 * halo) + 4 * max_patches            # int32: seabed | global centres | slice-relative centres
+    tick = time.perf_counter
+
+    def note(key, t0):
+        if stats is not None:
+            stats.setdefault(key, []).append(tick() - t0)
+
+    def fetch(chunk, slot):
+        t0 = tick()
+        s, e = chunk
+        # ping extent of the data a patch of the chunk can touch (dataset.py:175-177): the patch columns depend on
+        # (s, e) only, so the seabed of [lo, hi) -- which contains [s, e) -- is read ONCE (the zarr reader derives it from
+        # the full 2-D mask every time, data_reader.py:864-865)
+        xs = np.arange(s - (patch_overlap + 1), e - (patch_overlap + 1), patch_size[0] - 2 * patch_overlap) + patch_size[0] // 2
+        lo = max(0, int(xs[0]) - patch_size[1] // 2)
+        hi = min(n_pings, int(xs[-1]) + patch_size[1] // 2)
+        sb = np.asarray(reader.get_seabed(lo, hi - lo, return_numpy=True)).astype(np.int32)
+        seabed = sb[max(s - lo, 0):e - lo] if lo <= s else np.asarray(reader.get_seabed(s, e - s, return_numpy=True)).astype(np.int32)
+        grid = plan_grid(n_range, int(seabed.max()), s, e, patch_size, patch_overlap)
+        assert lo == max(0, int(grid[0, 1]) - patch_size[1] // 2) and hi == min(n_pings, int(grid[-1, 1]) + patch_size[1] // 2)
+        host = slot()
+        data = reader.get_data_slice(idx_ping=lo, n_pings=hi - lo, frequencies=segpipe.frequencies,
+                                     return_numpy=True)
+        d_t = host["data"][:n_freq * (hi - lo) * n_range].view(n_freq, hi - lo, n_range)     # contiguous
+        np.copyto(d_t.numpy(), data, casting="same_kind")
+        l_t = None
+        if labels_available:
+            lab = reader.get_label_slice(idx_ping=s, n_pings=e - s, return_numpy=True)
+            l_t = host["lab"][:(e - s) * n_range].view(e - s, n_range)
+            np.copyto(l_t.numpy(), lab, casting="unsafe")
+        # the seabed of every ping a patch of the chunk can touch (the scatter kernel evaluates the mask from it)
+        sb, mask = seabed_vector_or_mask(reader, s, e, n_range, sb, lo)
+        P = len(grid)
+        assert (hi - lo) + 4 * P <= n_misc, "misc staging too small"
+        m = host["misc"].numpy()
+        m[:hi - lo] = sb
+        cen = np.asarray(grid, dtype=np.int32)
+        m[hi - lo:hi - lo + 2 * P] = cen.reshape(-1)
+        loc = cen.copy()
+        loc[:, 1] -= lo
+        m[hi - lo + 2 * P:hi - lo + 4 * P] = loc.reshape(-1)
+        note("fetch_s", t0)
+        return {"data": d_t, "lab": l_t, "misc": host["misc"][:hi - lo + 4 * P]}, (s, e, lo, hi, grid, mask)
+
     # staging (pinned host + device) is kept between surveys of the same geometry: page-locking 3 x 75 MB + the result
-    # buffers costs 10-20 ms per call, a tenth of a 65536-ping survey
-    def new_staging():
-        return {
-            "stage_data": [torch.empty(n_data, dtype=torch.float32).pin_memory() for _ in range(NS)],
-            "stage_lab": [torch.empty((widest, n_range), dtype=torch.int16).pin_memory() for _ in range(NS)],
-            "stage_misc": [torch.empty(n_misc, dtype=torch.int32).pin_memory() for _ in range(NS)],
-            "dev_misc": [torch.empty(n_misc, dtype=torch.int32, device=dev) for _ in range(2)],
-            "dev_data": [torch.empty(n_data, dtype=torch.float32, device=dev) for _ in range(2)],
-            "dev_lab": [torch.empty((widest, n_range), dtype=torch.int16, device=dev) for _ in range(2)],
-            "pinned": [torch.empty(2 * n_range * widest, dtype=torch.float16 if f16 else torch.float32).pin_memory()
-                       for _ in range(2)],
-        }
+    # buffers costs 10-20 ms per call, a tenth of a 65536-ping survey.  3 host slots: two chunks are being read while
+    # one is uploaded
+    table = {"data": (n_data, torch.float32), "lab": (widest * n_range, torch.int16), "misc": (n_misc, torch.int32)}
+    out_t = torch.float16 if f16 else torch.float32
 
-    with _staging((str(dev), n_data, widest, n_range, n_misc, f16), new_staging) as bufs:
-        stage_data, stage_lab, stage_misc = bufs["stage_data"], bufs["stage_lab"], bufs["stage_misc"]
-        dev_misc = bufs["dev_misc"]
-        uploaded = [torch.cuda.Event() for _ in range(NS)]        # host slot k may be overwritten once this has passed
-        # device side: two resident chunk buffers; chunk i is uploaded on the copy stream while chunk i-1 computes
-        dev_data, dev_lab = bufs["dev_data"], bufs["dev_lab"]
-        computed = [torch.cuda.Event() for _ in range(2)]         # device slot may be overwritten once this has passed
-        copy_stream = torch.cuda.Stream(device=dev)
+    def result_ring():                   # flat: every chunk's [2, range, e - s] view of it is contiguous
+        return {"pinned": [torch.empty(2 * n_range * widest, dtype=out_t).pin_memory() for _ in range(2)]}
 
-        tick = time.perf_counter
-
-        def note(key, t0):
-            if stats is not None:
-                stats.setdefault(key, []).append(tick() - t0)
-
-        def fetch(i, s, e):
-            t0 = tick()
-            k = i % NS
-            # ping extent of the data a patch of the chunk can touch (dataset.py:175-177): the patch columns depend on
-            # (s, e) only, so the seabed of [lo, hi) -- which contains [s, e) -- is read ONCE (the zarr reader derives it from
-            # the full 2-D mask every time, data_reader.py:864-865)
-            xs = np.arange(s - (patch_overlap + 1), e - (patch_overlap + 1), patch_size[0] - 2 * patch_overlap) + patch_size[0] // 2
-            lo = max(0, int(xs[0]) - patch_size[1] // 2)
-            hi = min(n_pings, int(xs[-1]) + patch_size[1] // 2)
-            sb = np.asarray(reader.get_seabed(lo, hi - lo, return_numpy=True)).astype(np.int32)
-            seabed = sb[max(s - lo, 0):e - lo] if lo <= s else np.asarray(reader.get_seabed(s, e - s, return_numpy=True)).astype(np.int32)
-            grid = plan_grid(n_range, int(seabed.max()), s, e, patch_size, patch_overlap)
-            assert lo == max(0, int(grid[0, 1]) - patch_size[1] // 2) and hi == min(n_pings, int(grid[-1, 1]) + patch_size[1] // 2)
-            uploaded[k].synchronize()                                        # (no-op until the slot has been used)
-            data = reader.get_data_slice(idx_ping=lo, n_pings=hi - lo, frequencies=segpipe.frequencies,
-                                         return_numpy=True)
-            d_t = stage_data[k][:n_freq * (hi - lo) * n_range].view(n_freq, hi - lo, n_range)     # contiguous
-            np.copyto(d_t.numpy(), data, casting="same_kind")
-            l_t = None
-            if labels_available:
-                lab = reader.get_label_slice(idx_ping=s, n_pings=e - s, return_numpy=True)
-                l_t = stage_lab[k][:e - s]
-                np.copyto(l_t.numpy(), lab, casting="unsafe")
-            # the seabed of every ping a patch of the chunk can touch (the scatter kernel evaluates the mask from it)
-            sb, mask = seabed_vector_or_mask(reader, s, e, n_range, sb, lo)
-            P = len(grid)
-            assert (hi - lo) + 4 * P <= n_misc, "misc staging too small"
-            m = stage_misc[k].numpy()
-            m[:hi - lo] = sb
-            cen = np.asarray(grid, dtype=np.int32)
-            m[hi - lo:hi - lo + 2 * P] = cen.reshape(-1)
-            loc = cen.copy()
-            loc[:, 1] -= lo
-            m[hi - lo + 2 * P:hi - lo + 4 * P] = loc.reshape(-1)
-            note("fetch_s", t0)
-            return grid, lo, hi, d_t, l_t, stage_misc[k][:hi - lo + 4 * P], mask
-
-        pinned = bufs["pinned"]                      # flat: every chunk's [2, range, e - s] view of it is contiguous
+    with _ChunkFeed(dev, ("predict", f16), table, 3, chunks, fetch, extra=result_ring, note=note) as feed:
+        pinned = feed.bufs["pinned"]
         events = [torch.cuda.Event() for _ in range(2)]
-        pending = None                      # (s, e, slot) of the chunk whose D2H copy is in flight
-        main = torch.cuda.current_stream()
+
+        def take(s, e, ring):            # the chunk whose D2H copy went into pinned[ring]
+            t0 = tick()
+            events[ring].synchronize()
+            note("wait_gpu_s", t0)
+            t0 = tick()
+            res = pinned[ring][:2 * n_range * (e - s)].view(2, n_range, e - s).numpy().copy()
+            note("copy_out_s", t0)
+            return s, e, res
+
         def _loop():
-            nonlocal pending
-            with ThreadPoolExecutor(max_workers=2) as pool:
-                futs = {j: pool.submit(fetch, j, *chunks[j]) for j in range(min(2, len(chunks)))}
-                for i, (s, e) in enumerate(chunks):
-                    t0 = tick()
-                    grid, lo, hi, d_t, l_t, sb, mask = futs.pop(i).result()
-                    note("wait_fetch_s", t0)
-                    t0 = tick()
-                    if i + 2 < len(chunks):
-                        futs[i + 2] = pool.submit(fetch, i + 2, *chunks[i + 2])
-                    slot = i & 1
-                    with torch.cuda.stream(copy_stream):
-                        copy_stream.wait_event(computed[slot])                   # chunk i-2 is done with this device slot
-                        d_d = dev_data[slot][:d_t.numel()].view(d_t.shape)
-                        d_d.copy_(d_t, non_blocking=True)
-                        l_d = None
-                        if l_t is not None:
-                            l_d = dev_lab[slot][:e - s]
-                            l_d.copy_(l_t, non_blocking=True)
-                        m_d = dev_misc[slot][:sb.numel()]
-                        m_d.copy_(sb, non_blocking=True)                        # (sb: seabed | centres, pinned)
-                        uploaded[i % NS].record()
-                    note("enq_upload_s", t0)
-                    t1 = tick()
-                    main.wait_stream(copy_stream)
-                    P = len(grid)
-                    if stats is not None:
-                        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        ev0.record()
-                    if mask is None:
-                        cp.load_chunk(d_d, lo, l_d, None, s, e, seabed=m_d[:hi - lo], seabed_ping0=lo)
-                    else:                                 # (a mask the vector rule cannot express: uploaded as it is)
-                        cp.load_chunk(d_d, lo, l_d, mask, s, e)
-                    note("enq_load_s", t1)
-                    t1 = tick()
-                    out = cp.predict(grid, predict_fn=predict_fn, centres_dev=m_d[hi - lo:].view(2, P, 2),
-                                     share_patches=share_patches)
-                    note("enq_predict_s", t1)
-                    if stats is not None:
-                        ev1.record()
-                        stats.setdefault("gpu_events", []).append((ev0, ev1))
-                    computed[slot].record()
-                    if sender:                            # ordered hand-off: the chunk goes to rank 0, nothing comes back here
-                        hand.send(out)
-                        note("enqueue_s", t0)
-                        continue
-                    pinned[slot][:out.numel()].view(out.shape).copy_(out, non_blocking=True)
-                    events[slot].record()
-                    note("enqueue_s", t0)
-                    if pending is not None:
-                        ps, pe, pslot = pending
-                        t0 = tick()
-                        events[pslot].synchronize()
-                        note("wait_gpu_s", t0)
-                        t0 = tick()
-                        res = pinned[pslot][:2 * n_range * (pe - ps)].view(2, n_range, pe - ps).numpy().copy()
-                        note("copy_out_s", t0)
-                        yield ps, pe, res
-                    pending = (s, e, slot)
-                if sender:
-                    hand.flush()
-                    return
-                ps, pe, pslot = pending
-                events[pslot].synchronize()
-                yield ps, pe, pinned[pslot][:2 * n_range * (pe - ps)].view(2, n_range, pe - ps).numpy().copy()
+            pending = None                      # (s, e, ring) of the chunk whose D2H copy is in flight
+            for i, (d, (s, e, lo, hi, grid, mask)) in enumerate(feed):
+                P = len(grid)
+                if stats is not None:
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ev0.record()
+                _load_staged(cp, d["data"], lo, d["lab"], s, e, d["misc"][:hi - lo], mask)
+                note("enq_load_s", feed.t_uploaded)
+                t1 = tick()
+                out = cp.predict(grid, predict_fn=predict_fn, centres_dev=d["misc"][hi - lo:].view(2, P, 2),
+                                 share_patches=share_patches)
+                note("enq_predict_s", t1)
+                if stats is not None:
+                    ev1.record()
+                    stats.setdefault("gpu_events", []).append((ev0, ev1))
+                feed.computed()
+                if sender:                            # ordered hand-off: the chunk goes to rank 0, nothing comes back here
+                    hand.send(out)
+                    note("enqueue_s", feed.t_taken)
+                    continue
+                pinned[i & 1][:out.numel()].view(out.shape).copy_(out, non_blocking=True)
+                events[i & 1].record()
+                note("enqueue_s", feed.t_taken)
+                if pending is not None:
+                    yield take(*pending)
+                pending = (s, e, i & 1)
+            if sender:
+                hand.flush()
+            else:
+                yield take(*pending)
 
         if ordered and rank == 0:
             yield from hand.merge(_loop())
@@ -984,65 +1023,32 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
     if not mine:
         return finish_histograms(hist)
     widest = max(hi - lo for _, lo, hi in mine)
-    NS = 2
 
-    def new_staging():
-        return {
-            "stage_data": [torch.empty(n_freq * widest * n_range, dtype=torch.float32).pin_memory() for _ in range(NS)],
-            "stage_lab": [torch.empty(widest * n_range, dtype=torch.int16).pin_memory() for _ in range(NS)],
-            "stage_sb": [torch.empty(widest, dtype=torch.int32).pin_memory() for _ in range(NS)],
-            "dev_data": [torch.empty(n_freq * widest * n_range, dtype=torch.float32, device=dev) for _ in range(2)],
-            "dev_lab": [torch.empty(widest * n_range, dtype=torch.int16, device=dev) for _ in range(2)],
-            "dev_sb": [torch.empty(widest, dtype=torch.int32, device=dev) for _ in range(2)],
-        }
-
-    uploaded = [torch.cuda.Event() for _ in range(NS)]        # host slot may be overwritten once this has passed
-    computed = [torch.cuda.Event() for _ in range(2)]         # device slot may be overwritten once this has passed
-    copy_stream = torch.cuda.Stream(device=dev)
-    main = torch.cuda.current_stream()
-
-    def fetch(i, lo, hi):
-        k = i % NS
+    def fetch(job, slot):
+        _, lo, hi = job
         n = hi - lo
-        uploaded[k].synchronize()                             # (no-op until the slot has been used)
+        host = slot()
         data = reader.get_data_slice(idx_ping=lo, n_pings=n, frequencies=segpipe.frequencies, return_numpy=True)
-        d_t = bufs["stage_data"][k][:n_freq * n * n_range].view(n_freq, n, n_range)
+        d_t = host["data"][:n_freq * n * n_range].view(n_freq, n, n_range)
         np.copyto(d_t.numpy(), data, casting="same_kind")
         lab = np.asarray(reader.get_label_slice(idx_ping=lo, n_pings=n, return_numpy=True))
         if lab.dtype.kind == "f":                             # get_crop_zarr: nan_to_num(labels, nan=LABEL_BOUNDARY_VAL)
             lab = np.nan_to_num(lab, nan=-100.0)
-        l_t = bufs["stage_lab"][k][:n * n_range].view(n, n_range)
+        l_t = host["lab"][:n * n_range].view(n, n_range)
         np.copyto(l_t.numpy(), lab, casting="unsafe")
         sb, mask = seabed_vector_or_mask(reader, lo, hi, n_range, sb_all, 0)
-        s_t = bufs["stage_sb"][k][:n]
+        s_t = host["sb"][:n]
         s_t.numpy()[:] = sb[lo:hi]
-        return d_t, l_t, s_t, mask
+        return {"data": d_t, "lab": l_t, "sb": s_t}, mask
 
     t_start = time.perf_counter()
-    with _staging(("eval", str(dev), n_freq, widest, n_range), new_staging) as bufs:
-        with ThreadPoolExecutor(max_workers=1) as pool:
-            fut = pool.submit(fetch, 0, mine[0][1], mine[0][2])
-            for i, (idx, lo, hi) in enumerate(mine):
-                d_t, l_t, s_t, mask = fut.result()
-                if i + 1 < len(mine):
-                    fut = pool.submit(fetch, i + 1, mine[i + 1][1], mine[i + 1][2])
-                slot = i & 1
-                with torch.cuda.stream(copy_stream):
-                    copy_stream.wait_event(computed[slot])        # chunk i-2 is done with this device slot
-                    d_d = bufs["dev_data"][slot][:d_t.numel()].view(d_t.shape)
-                    d_d.copy_(d_t, non_blocking=True)
-                    l_d = bufs["dev_lab"][slot][:l_t.numel()].view(l_t.shape)
-                    l_d.copy_(l_t, non_blocking=True)
-                    s_d = bufs["dev_sb"][slot][:hi - lo]
-                    s_d.copy_(s_t, non_blocking=True)
-                    uploaded[i % NS].record()
-                main.wait_stream(copy_stream)
-                if mask is None:
-                    cp.load_chunk(d_d, lo, l_d, None, lo, hi, seabed=s_d, seabed_ping0=lo, wide=True)
-                else:                                 # (a mask the vector rule cannot express: uploaded as it is)
-                    cp.load_chunk(d_d, lo, l_d, mask, lo, hi, wide=True)
-                cp.evaluate(grid[idx], hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch)
-                computed[slot].record()
+    table = {"data": (n_freq * widest * n_range, torch.float32), "lab": (widest * n_range, torch.int16),
+             "sb": (widest, torch.int32)}
+    with _ChunkFeed(dev, "eval", table, 2, mine, fetch) as feed:      # 2 host slots: one chunk is read while one is uploaded
+        for (idx, lo, hi), (d, mask) in zip(mine, feed):
+            _load_staged(cp, d["data"], lo, d["lab"], lo, hi, d["sb"], mask, wide=True)
+            cp.evaluate(grid[idx], hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch)
+            feed.computed()
         out = finish_histograms(hist)
     if stats is not None:
         stats["seconds"] = time.perf_counter() - t_start

@@ -350,6 +350,104 @@ def test_predict_survey_follows_the_readers_seabed_mask(preload):
             assert np.array_equal(out != 0, o != 0) and np.abs(out - o).max() < 1e-3
 
 
+WRAP_CHUNKS = [(0, 62), (62, 125), (125, 187), (187, 250), (250, 312), (312, 375), (375, 437), (437, 500)]
+
+
+@pytest.fixture(scope="module")
+def wraps():
+    """The holey survey in 8 chunks (preload 70): predict_survey's 3 host slots wrap twice, its 2 device slots three
+    times, chunk widths alternate between 62 and 63 pings; chunks 0, 3, 6, 7 take the plain seabed vector, 1 and 2 the
+    vector with n_range for their no-bottom pings, 4 and 5 the mask upload.  ``run(out_dtype)``: a fresh generator over
+    the survey; ``oracle``: the 8 chunks of the numpy oracle on the reader's mask; ``plain[dtype]``: the chunks of one
+    undisturbed run (fresh staging), computed once."""
+    import types
+    import crimac_classifiers_unet_amd as pkg
+    sv, labels, reader, mask = _holey_case()
+    n_range = sv.shape[2]
+    assert ti.plan_chunks(0, 500, 70) == WRAP_CHUNKS
+    kinds = []
+    for s, e in WRAP_CHUNKS:
+        sb = np.asarray(reader.get_seabed(s, e - s, return_numpy=True)).astype(np.int32)
+        vec, m = ti.seabed_vector_or_mask(reader, s, e, n_range, sb, s)
+        kinds.append("mask" if m is not None else ("no-bottom" if (vec == n_range).any() else "vector"))
+    assert kinds == ["vector", "no-bottom", "no-bottom", "vector", "mask", "mask", "vector", "vector"]
+    model = pkg.UNet_Baseline(3, 4, precision="f32x6").cuda().eval()
+    pipe = types.SimpleNamespace(model=model, device=torch.device("cuda"), frequencies=[18, 38, 120, 200])
+
+    def predict_fn(x, P, H, W):
+        d = x.float().reshape(P, H, W, 16)[..., :4].permute(0, 3, 1, 2).cpu().numpy()
+        return torch.from_numpy(np.stack([linear_predictor(di) for di in d])).cuda().contiguous()
+
+    def run(out_dtype):
+        return ti.predict_survey(reader, pipe, (256, 256), 20, 4, 70, out_dtype=out_dtype, predict_fn=predict_fn)
+
+    oracle = [orc.predict_chunk(sv, labels, reader.seabed, s, e, linear_predictor, (256, 256), 20, seabed_mask=mask)[0]
+              for s, e in WRAP_CHUNKS]
+    ti.release_staging()
+    plain = {dt: list(run(dt)) for dt in (np.float32, np.float16)}
+    ti.release_staging()
+    return types.SimpleNamespace(run=run, oracle=oracle, plain=plain)
+
+
+def _same_chunks(a, b):
+    return [c[:2] for c in a] == [c[:2] for c in b] == WRAP_CHUNKS and \
+        all(x[2].dtype == y[2].dtype and np.array_equal(x[2], y[2]) for x, y in zip(a, b))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("out_dtype", [np.float32, np.float16])
+def test_predict_survey_over_the_staging_slot_wraps_matches_the_oracle(wraps, out_dtype):
+    """8 chunks through 3 host slots and 2 device slots, all three seabed paths: every chunk == the oracle on that chunk
+    (float32: the criterion of the 250-ping case above; float16: that of the f16 chunk loop against its golden)."""
+    got = wraps.plain[out_dtype]
+    assert [c[:2] for c in got] == WRAP_CHUNKS
+    for (s, e, out), o in zip(got, wraps.oracle):
+        assert out.dtype == out_dtype and out.shape == o.shape
+        if out_dtype == np.float32:
+            assert np.array_equal(out != 0, o != 0) and np.abs(out - o).max() < 1e-3
+        else:
+            ref = o.astype(np.float16)
+            assert np.array_equal(out != 0, ref != 0)
+            assert np.abs(out.astype(np.float32) - ref.astype(np.float32)).max() <= 2.0 ** -10
+
+
+@pytest.mark.gpu
+def test_predict_survey_reuses_its_staging_between_surveys_of_one_geometry(wraps):
+    """Twice the same survey: one staging set, the same buffers; then the other output type: the key changes, the old
+    set is dropped, still one set.  Every pass gives the bits of an undisturbed run."""
+    ti.release_staging()
+    first = list(wraps.run(np.float32))
+    assert len(ti._STAGING) == 1
+    (key, bufs), = ti._STAGING.items()
+    ptrs = [t.data_ptr() for slot in bufs["host"] + bufs["dev"] for t in slot.values()] + [t.data_ptr() for t in bufs["pinned"]]
+    second = list(wraps.run(np.float32))
+    assert len(ti._STAGING) == 1 and ti._STAGING[key] is bufs and not bufs["busy"]
+    assert ptrs == [t.data_ptr() for slot in bufs["host"] + bufs["dev"] for t in slot.values()] + [t.data_ptr() for t in bufs["pinned"]]
+    third = list(wraps.run(np.float16))
+    assert len(ti._STAGING) == 1 and key not in ti._STAGING and next(iter(ti._STAGING.values())) is not bufs
+    ti.release_staging()
+    assert not ti._STAGING
+    assert _same_chunks(first, wraps.plain[np.float32]) and _same_chunks(second, wraps.plain[np.float32])
+    assert _same_chunks(third, wraps.plain[np.float16])
+
+
+@pytest.mark.gpu
+def test_a_second_survey_while_the_first_is_open_gets_a_private_staging_set(wraps):
+    """A survey whose generator is still open keeps its staging set busy: a complete second survey of the same geometry
+    runs on a fresh private set, and both give the bits of an undisturbed run."""
+    ti.release_staging()
+    gen = wraps.run(np.float32)
+    first = [next(gen), next(gen)]
+    (key, bufs), = ti._STAGING.items()
+    assert bufs["busy"]
+    second = list(wraps.run(np.float32))
+    assert len(ti._STAGING) == 1 and ti._STAGING[key] is bufs and bufs["busy"]      # (the private set is not kept)
+    first += list(gen)
+    assert not bufs["busy"]
+    ti.release_staging()
+    assert _same_chunks(first, wraps.plain[np.float32]) and _same_chunks(second, wraps.plain[np.float32])
+
+
 @pytest.mark.gpu
 def test_configs3_chunk_of_4096_pings_covers_the_water_column():
     """BASELINE configs[3] geometry at size: one chunk of 4096 pings x 1024 range, flat seabed 900
