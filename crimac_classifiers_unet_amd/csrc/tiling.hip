@@ -31,13 +31,14 @@ constexpr int TS = 32;   // tile side
 // the crop's metadata planes (meta_plane_values, crop centred on meta_centres[p] = (range idx, GLOBAL ping idx)), which
 // neither the dB transform nor the border rule touches (batch/dataset.py:109: np.concatenate((data, meta)) after the
 // data transform); db_scaled: db_with_limits_scaled (1 + dB / 75, define_data_transform_test(use_metadata=True)).
+// The body of one block = one 32 x 32 tile of patch blockIdx.z, shared by the single-source kernel and by the kernel that
+// takes the source of every patch from a descriptor (gather_patches_multi_kernel): one text, the same bits.
 template <typename T>
-__global__ __launch_bounds__(256) void gather_patches_kernel(const float* __restrict__ data, int C, int Wd,
-                                                             int H, const int* __restrict__ centres,
-                                                             int ph, int pw, T* __restrict__ out,
-                                                             int ld, const short* __restrict__ border_labels,
-                                                             int db_scaled, MetaPlaneSrc meta,
-                                                             const int* __restrict__ meta_centres) {
+__device__ __forceinline__ void gather_patch_tile(const float* __restrict__ data, int C, int Wd, int H,
+                                                  const int* __restrict__ centres, int ph, int pw,
+                                                  T* __restrict__ out, int ld,
+                                                  const short* __restrict__ border_labels, int db_scaled,
+                                                  const MetaPlaneSrc& meta, const int* __restrict__ meta_centres) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float* tile = reinterpret_cast<float*>(smem_raw);      // [C][TS (x)][TS + 1 (y)]
   const int p = blockIdx.z;
@@ -98,6 +99,16 @@ __global__ __launch_bounds__(256) void gather_patches_kernel(const float* __rest
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void gather_patches_kernel(const float* __restrict__ data, int C, int Wd,
+                                                             int H, const int* __restrict__ centres,
+                                                             int ph, int pw, T* __restrict__ out,
+                                                             int ld, const short* __restrict__ border_labels,
+                                                             int db_scaled, MetaPlaneSrc meta,
+                                                             const int* __restrict__ meta_centres) {
+  gather_patch_tile<T>(data, C, Wd, H, centres, ph, pw, out, ld, border_labels, db_scaled, meta, meta_centres);
+}
+
 // probs [P][ncls][ph][pw] fp32; centres [P][2] global (cy, cx); out [2][H][n_chunk] fp32 (or fp16).
 struct ScatterParams {
   const float* probs; int ncls; const int* centres; int P, ph, pw, overlap, start_ping, n_chunk, H;
@@ -152,6 +163,66 @@ __global__ __launch_bounds__(256) void scatter_patches_kernel(ScatterParams q) {
     } else {
       reinterpret_cast<float*>(q.out)[d0] = q.probs[src];
       reinterpret_cast<float*>(q.out)[d1] = q.probs[src + (long)ph * pw];   // channel OTHER = 2
+    }
+  }
+}
+
+// ---- batches that span memmap echograms (tiled_inference.predict_echograms_memm) ---------------------------------------
+// The two kernels above read ONE source and write ONE destination, given as scalar arguments.  A forward batch packed
+// from several echograms needs both per patch: src[p] picks the patch's crimac_memm_desc from a device-resident table.
+// A block works on one patch, so the descriptor, src[p] and the centre are uniform over the block.
+
+// crimac_gather_patches_memm's kernel (border rule, no metadata planes, db_with_limits) with the source taken from
+// descs[src[p]]: gather_patch_tile on that echogram.  A descriptor without labels gets no border rule, as a NULL
+// border_labels in the single-source kernel.
+static_assert(sizeof(crimac_memm_desc) == 48, "crimac_memm_desc: six 64-bit fields (hip.MEMM_DESC_WORDS)");
+
+template <typename T>
+__global__ __launch_bounds__(256) void gather_patches_multi_kernel(const crimac_memm_desc* __restrict__ descs,
+                                                                   int n_desc, const int* __restrict__ src, int C,
+                                                                   const int* __restrict__ centres, int ph, int pw,
+                                                                   T* __restrict__ out, int ld) {
+  const int s = src[blockIdx.z];
+  if (s < 0 || s >= n_desc) return;                        // (uniform over the block: nobody waits at the barrier)
+  const crimac_memm_desc d = descs[s];
+  gather_patch_tile<T>(d.data, C, (int)d.n_pings, (int)d.n_range, centres, ph, pw, out, ld, d.labels, 0, MetaPlaneSrc{},
+                       nullptr);
+}
+
+// scatter_patches_kernel with the memm rules only (labels, seabed vector from ping 0, seabed_rule 1, no data0), the
+// destination [2][n_range][n_pings], the labels, the seabed vector and the two extents taken from descs[src[p]].
+// blockIdx.y = patch.  Interiors of different patches are disjoint, within an echogram and across echograms: plain stores.
+struct ScatterMultiParams {
+  const float* probs; int ncls; const crimac_memm_desc* descs; int n_desc; const int* src; const int* centres;
+  int ph, pw, overlap, seabed_pad, out_f16;
+};
+__global__ __launch_bounds__(256) void scatter_patches_multi_kernel(ScatterMultiParams q) {
+  const int ph = q.ph, pw = q.pw, overlap = q.overlap;
+  const int iw = pw - 2 * overlap, ih = ph - 2 * overlap;
+  const int per_patch = ih * iw;
+  const int p = blockIdx.y;
+  const int s = q.src[p];
+  if (s < 0 || s >= q.n_desc) return;
+  const crimac_memm_desc d = q.descs[s];
+  const long H = d.n_range, n_pings = d.n_pings;
+  const int cy = q.centres[2 * p], cx = q.centres[2 * p + 1];
+  for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < per_patch; r += gridDim.x * blockDim.x) {
+    const int py = overlap + r / iw, px = overlap + r % iw;      // mask_label_overlap: rim excluded
+    const int y = cy - ph / 2 + 1 + py, x = cx - pw / 2 + 1 + px;   // patch_coord_to_data_coord
+    if (y < 0 || y >= H || x < 0 || x >= n_pings) continue;         // label crop out of range: -100
+    const int lab = d.labels ? (int)d.labels[x * H + y] : 0;
+    if (lab < 0) continue;                                           // convert_label_indexing: -100
+    if (lab == 0 && d.seabed && y >= q.seabed_pad &&                 // mask_label_seabed (background only), absolute rows
+        (y - q.seabed_pad) >= d.seabed[x])
+      continue;
+    const long sp = (((long)p * q.ncls + 1) * ph + py) * pw + px;    // channel SANDEEL = 1
+    const long d0 = y * n_pings + x, d1 = (H + y) * n_pings + x;
+    if (q.out_f16) {                                                 // the reference stores float16 (save_predict.py:252)
+      reinterpret_cast<half_t*>(d.out)[d0] = (half_t)q.probs[sp];
+      reinterpret_cast<half_t*>(d.out)[d1] = (half_t)q.probs[sp + (long)ph * pw];
+    } else {
+      reinterpret_cast<float*>(d.out)[d0] = q.probs[sp];
+      reinterpret_cast<float*>(d.out)[d1] = q.probs[sp + (long)ph * pw];   // channel OTHER = 2
     }
   }
 }
@@ -381,4 +452,39 @@ extern "C" int crimac_scatter_patches(const float* probs, int ncls, const int* c
   return crimac_scatter_patches_ex(probs, ncls, centres, P, ph, pw, overlap, start_ping, n_chunk, H, labels,
                                    seabed_mask, mask_ping0, mask_pings, nullptr, 0, 0, data0, data_ping0, data_pings,
                                    seabed_pad, 0, out, 0, stream);
+}
+
+extern "C" int crimac_gather_patches_memm_multi(int prec, const crimac_memm_desc* descs, int n_desc, const int* src,
+                                                int C, const int* centres, int P, int ph, int pw, void* out, long ld,
+                                                void* stream) {
+  CRIMAC_REQUIRE(prec >= CRIMAC_PREC_BF16 && prec <= CRIMAC_PREC_MAX, "gather_patches_memm_multi: bad precision %d", prec);
+  CRIMAC_REQUIRE(descs && src && centres && out && n_desc > 0 && C > 0 && C <= 16 && P > 0 && ph > 0 && pw > 0,
+                 "gather_patches_memm_multi: bad arguments (C=%d must be <= 16)", C);
+  CRIMAC_REQUIRE(ld >= C && ld % 8 == 0 && ld <= 16, "gather_patches_memm_multi: ld=%ld must be 8 or 16 and >= C", ld);
+  CRIMAC_REQUIRE(P <= 65535, "gather_patches_memm_multi: at most 65535 patches per call");
+  dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
+  const size_t lds = (size_t)C * TS * (TS + 1) * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(gather_patches_multi_kernel<T>, grid, dim3(256), lds, st, descs,
+                                                 n_desc, src, C, centres, ph, pw, (T*)out, (int)ld));
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}
+
+extern "C" int crimac_scatter_patches_multi(const float* probs, int ncls, const crimac_memm_desc* descs, int n_desc,
+                                            const int* src, const int* centres, int P, int ph, int pw, int overlap,
+                                            int seabed_pad, int out_f16, void* stream) {
+  CRIMAC_REQUIRE(probs && descs && src && centres && n_desc > 0 && P > 0 && ph > 0 && pw > 0,
+                 "scatter_patches_multi: bad arguments");
+  CRIMAC_REQUIRE(ncls >= 3, "scatter_patches_multi: needs the SANDEEL (1) and OTHER (2) channels, ncls=%d", ncls);
+  CRIMAC_REQUIRE(overlap >= 0 && 2 * overlap < ph && 2 * overlap < pw, "scatter_patches_multi: bad overlap %d", overlap);
+  CRIMAC_REQUIRE(P <= 65535, "scatter_patches_multi: at most 65535 patches per call");
+  CRIMAC_REQUIRE((long)ph * pw < (1l << 30), "scatter_patches_multi: patch too large");
+  const long per_patch = (long)(ph - 2 * overlap) * (pw - 2 * overlap);
+  long bx = (per_patch + 255) / 256;
+  if (bx > 64) bx = 64;
+  ScatterMultiParams q{probs, ncls, descs, n_desc, src, centres, ph, pw, overlap, seabed_pad, out_f16};
+  hipLaunchKernelGGL(scatter_patches_multi_kernel, dim3((unsigned)bx, (unsigned)P), dim3(256), 0, (hipStream_t)stream, q);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
 }

@@ -46,7 +46,7 @@ LAYER_CONV3X3, LAYER_UPCONV2X2, LAYER_CONV1X1 = 0, 1, 2     # crimac_layer_desc.
 PREC_BACKWARD = {PREC_F32H3: PREC_F32X3}
 PREC_16BIT = (PREC_BF16, PREC_FP16)
 
-ABI_VERSION = 10        # CRIMAC_ABI_VERSION of include/crimac_unet_hip.h this binding was written against
+ABI_VERSION = 11        # CRIMAC_ABI_VERSION of include/crimac_unet_hip.h this binding was written against
 
 _vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
 
@@ -115,6 +115,8 @@ SIGNATURES = {
                                         _vp, _i, _vp, _i, _vp, _vp],
     "crimac_scatter_patches_ex": [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i,
                                   _i, _i, _vp, _i, _vp],
+    "crimac_gather_patches_memm_multi": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _l, _vp],
+    "crimac_scatter_patches_multi": [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "crimac_gather_eval_crops": [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "crimac_augment_db_nhwc": [_i, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _i, _i, _i, _i, _l, C.c_ulonglong,
                                _i, _i, _i, _vp],
@@ -149,6 +151,7 @@ class WgradGroupLayer(C.Structure):
 
 WGRAD_GROUP_MAX_LAYERS = 16      # CRIMAC_WGRAD_GROUP_MAX_LAYERS
 MASK_PER_PATCH = -2147483648      # CRIMAC_MASK_PER_PATCH
+MEMM_DESC_WORDS = 6      # crimac_memm_desc as int64: data, labels, seabed, out (device addresses), n_pings, n_range
 
 
 _lib = None

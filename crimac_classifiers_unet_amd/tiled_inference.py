@@ -22,10 +22,14 @@ With ``torch.distributed`` initialised, patches of a chunk are dealt round-robin
 (``parallel.shard_indices``) and the per-rank float16 outputs are summed (valid interiors are disjoint, x + 0 is
 exact).  Writing zarr / npy is the caller's business: ``predict_survey`` yields numpy chunks
 that a caller appends with the reference's ``create_xarray_ds_predictions`` / ``append_to_zarr``;
-``predict_echogram_memm`` returns the array ``save_reader_predictions_memm`` would ``np.save``.
+``predict_echogram_memm`` returns the array ``save_reader_predictions_memm`` would ``np.save``;
+``predict_echograms_memm`` does so for a whole memm survey, its forward batches packed across the echograms.
 """
 from __future__ import annotations
 
+import difflib
+import itertools
+import os
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -499,8 +503,9 @@ def release_staging():
 
 
 class _ChunkFeed:
-    """The chunk pipeline of ``predict_survey`` and ``evaluate_survey``: reader threads fill pinned host slots ahead of the
-    GPU, a copy stream uploads each chunk into one of two device slots while the chunk before it computes.
+    """The chunk pipeline of ``predict_survey``, ``evaluate_survey`` and ``predict_echograms_memm`` (whose chunk is a group
+    of echograms): reader threads fill pinned host slots ahead of the GPU, a copy stream uploads each chunk into one of
+    two device slots while the chunk before it computes.  ``jobs`` is any iterable, taken from lazily.
 
     ``table`` {name: (elements, dtype)}: the flat buffers a chunk is staged in, one of each per host slot and per device
     slot.  The set (+ the caller's ``extra()`` buffers) is kept in ``_STAGING`` between surveys of the same key -- ``tag``
@@ -532,7 +537,7 @@ class _ChunkFeed:
         self.computed_ev = [torch.cuda.Event() for _ in range(2)]         # device slot may be overwritten once this has passed
         self.copy_stream = torch.cuda.Stream(device=self.dev)
         self.main = torch.cuda.current_stream()
-        self.n_uploaded = 0
+        self.n_uploaded = self.n_submitted = 0        # (a feed is iterated once per ``with``)
         bufs = _STAGING.get(self.key)
         if bufs is None or bufs["busy"]:     # (busy: another flow over the same geometry is still running: a private set)
             fresh = self._allocate()
@@ -550,25 +555,35 @@ class _ChunkFeed:
         torch.cuda.current_stream().synchronize()     #  ... and nothing on the GPU still reads or writes it)
         self.bufs["busy"] = False
 
-    def _submit(self, j):
+    def _submit(self, j, job):
         assert j - self.slots < self.n_uploaded, "chunk feed: the last upload from this host slot has not been recorded"
         ev, host = self.uploaded[j % self.slots], self.bufs["host"][j % self.slots]
 
         def slot():
             ev.synchronize()                          # (no-op until the slot has been used)
             return host
-        return self.pool.submit(self.read, self.jobs[j], slot)
+        return self.pool.submit(self.read, job, slot)
 
     def __iter__(self):
-        depth, n = self.slots - 1, len(self.jobs)
-        futs = {j: self._submit(j) for j in range(min(depth, n))}
-        for i in range(n):
+        # ``jobs`` is any iterable and is consumed lazily, on this thread: job i + depth is taken from it when job i is
+        # handed out (``predict_echograms_memm`` plans its groups from an iterator of echograms as it goes)
+        depth, jobs, futs = self.slots - 1, iter(self.jobs), []
+
+        def submit():
+            for job in itertools.islice(jobs, 1):
+                futs.append(self._submit(self.n_submitted, job))
+                self.n_submitted += 1
+        assert self.n_submitted == 0, "chunk feed: iterated twice inside one `with`"
+        for _ in range(depth):
+            submit()
+        i = -1
+        while futs:
+            i += 1
             t0 = time.perf_counter()
-            uploads, payload = futs.pop(i).result()
+            uploads, payload = futs.pop(0).result()
             self.note("wait_fetch_s", t0)
             self.t_taken = time.perf_counter()
-            if i + depth < n:
-                futs[i + depth] = self._submit(i + depth)
+            submit()
             self.slot = i & 1
             views = dict.fromkeys(uploads)
             with torch.cuda.stream(self.copy_stream):
@@ -938,6 +953,290 @@ def predict_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_si
     grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
     out = cp.predict(grid, predict_fn=predict_fn)
     return out.cpu().numpy().astype(np.float64)
+
+
+# ---- a memm survey: many small echograms in one prediction feed ----------------------------------------------------------
+MEMM_GROUP_BATCHES = 4            # default ``group_patches``: this many forward batches per group
+MEMM_GROUP_ELEMS = 1 << 24        # pixels (range x pings) a group stages at most: 268 MB of fp32 planes at 4 frequencies
+MEMM_MISC_SHARE = 8               # the int32 staging (descriptors, centres, src, seabed lines) is 1 / 8 of the pixels
+
+
+def plan_memm_groups(items, group_patches, max_elems=None, key=None):
+    """Cut a run of echograms into groups, lazily: yields lists of consecutive ``items``.  ``key(item)`` (default: the
+    item itself) is ``(patches, elems)``.  A group is closed as soon as its patches reach ``group_patches``; an item that
+    reaches ``group_patches`` alone, or whose ``elems`` exceed ``max_elems`` alone, is a group of its own; no other group
+    holds more than ``max_elems`` elements.  An item without patches joins the group that is open."""
+    if group_patches < 1:
+        raise ValueError(f"group_patches must be positive, got {group_patches}")
+    group, n, size = [], 0, 0
+    for item in items:
+        c, e = key(item) if key else item
+        own = c >= group_patches or (max_elems is not None and e > max_elems)
+        if group and (own or (max_elems is not None and size + e > max_elems)):
+            yield group
+            group, n, size = [], 0, 0
+        group.append(item)
+        n, size = n + c, size + e
+        if own or n >= group_patches:
+            yield group
+            group, n, size = [], 0, 0
+    if group:
+        yield group
+
+
+def shard_memm_groups(groups, rank, world):
+    """Groups rank, rank + world, ... of ``groups`` (lazily), as ``predict_survey(shard="chunk")`` deals its chunks: the
+    ranks' shares are disjoint, complete and keep the input order; no collective."""
+    if not 0 <= rank < world:
+        raise ValueError(f"rank {rank} outside the world of {world}")
+    return itertools.islice(groups, rank, None, world)
+
+
+class _MemmRecord:
+    """One echogram of a memm survey as the planner sees it: extents, seabed line, patch grid."""
+
+    def __init__(self, echogram, seabed, patch_size, patch_overlap):
+        self.echogram = echogram
+        self.n_range, self.n_pings = (int(v) for v in echogram.shape)
+        self.seabed = seabed
+        self.grid = plan_eval_grid(self.n_range, seabed, self.n_pings, patch_size, patch_overlap, memm=True)
+        self.pixels = self.n_range * self.n_pings
+        # what the echogram takes of a group's staging: its pixels, or -- a sliver with many pings -- its int32 words
+        self.elems = max(self.pixels, MEMM_MISC_SHARE * (2 * hip.MEMM_DESC_WORDS + 3 * len(self.grid) + self.n_pings))
+
+    def key(self):
+        return len(self.grid), self.elems
+
+
+def _memm_survey_seabed(echogram, seabed, device):
+    """The seabed line of one echogram of a survey: ``seabed`` None -> the reader's ``get_seabed``; "estimate" -> the GPU
+    estimate, on a stream of its own (its read-back does not wait for the survey's forwards); a callable -> its result for
+    this echogram."""
+    n_pings = int(echogram.shape[1])
+    if seabed is None:
+        return np.asarray(echogram.get_seabed(0, n_pings)).astype(np.int32)
+    if isinstance(seabed, str):
+        if seabed != "estimate":
+            raise ValueError(f"seabed must be None, 'estimate' or a callable, got {seabed!r}")
+        with torch.cuda.stream(_seabed_stream(device)):
+            return estimate_seabed_memm(echogram, device=device).astype(np.int32)
+    return _memm_seabed(echogram, np.asarray(seabed(echogram)), n_pings, None, None)
+
+
+_SEABED_STREAMS = {}
+
+
+def _seabed_stream(device):
+    device = torch.device(device)
+    if device not in _SEABED_STREAMS:
+        _SEABED_STREAMS[device] = torch.cuda.Stream(device=device)
+    return _SEABED_STREAMS[device]
+
+
+def iter_memm_groups(echograms, patch_size, patch_overlap, group_patches, seabed=None, max_elems=MEMM_GROUP_ELEMS,
+                     rank=0, world=1, device=None, skip=None):
+    """The host-side plan of ``predict_echograms_memm``: consumes ``echograms`` lazily and yields this rank's groups, each
+    a list of records (``.echogram``, ``.seabed`` int32 [n_pings], ``.grid`` = ``plan_eval_grid(..., memm=True)`` with the
+    echogram's own seabed).  Every rank walks every echogram's seabed line (the grouping depends on the patch counts) and
+    reads the data of its own groups only.
+    ``skip(echogram) -> bool`` (the resume rule of ``save_predictions_memm``) is asked AFTER the deal, about the echograms of
+    this rank's own groups only: the groups and their owners are planned over the whole input, which is the same on every
+    rank, so what one rank skips -- files another rank is writing meanwhile -- cannot move an echogram to another rank or
+    to none.  A group of which nothing is left is dropped."""
+    records = (_MemmRecord(eg, _memm_survey_seabed(eg, seabed, device), patch_size, patch_overlap) for eg in echograms)
+    mine = shard_memm_groups(plan_memm_groups(records, group_patches, max_elems, key=_MemmRecord.key), rank, world)
+    if skip is None:
+        return mine
+    kept = ([r for r in g if not skip(r.echogram)] for g in mine)
+    return (g for g in kept if g)
+
+
+def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn=None, meta_channels=None,
+                           seabed=None, group_patches=None, stats=None, group_elems=None, skip=None, **kwargs):
+    """``save_reader_predictions_memm`` (save_predict.py:222-265) for a whole memm survey -- a directory of many small
+    echograms: a generator of ``(echogram, float64 [2, n_range, n_pings])`` in input order, every array equal to
+    ``predict_echogram_memm`` of that echogram (probabilities rounded to float16 on the GPU, then widened).
+
+    ``echograms``: any iterable of the reference's ``Echogram`` API, consumed lazily (a few groups ahead of the result
+    handed out).  Consecutive echograms form *groups* (``plan_memm_groups``): a group is closed when its patches reach
+    ``group_patches`` (default ``MEMM_GROUP_BATCHES`` forward batches) or its pixels ``group_elems`` (default
+    ``MEMM_GROUP_ELEMS``: the staging is allocated for that many).  All patches of a group form ONE patch list, cut into
+    forward batches of ``max(batch_size, INTERNAL_BATCH)`` (``batch_size`` with a ``predict_fn``, as in
+    ``ChunkPredictor.predict``): only the last batch of a group is short.  ``crimac_gather_patches_memm_multi`` /
+    ``crimac_scatter_patches_multi`` take each patch's source and destination from a descriptor table that goes up with
+    the group's centres and seabed lines in one pinned copy.  Reader threads copy the next groups' memmaps into pinned
+    staging (``_ChunkFeed``), the copy stream uploads and transposes them while the current group computes, and the
+    float16 results leave through a non-blocking download into a ring of two pinned buffers.
+
+    ``seabed``: None (the reader's ``get_seabed``), ``"estimate"`` (``estimate_seabed_memm`` per echogram) or a callable
+    ``echogram -> integer array [n_pings]``; not an array, which belongs to one echogram.
+    **Models with metadata planes** (``UNet_LateMetInject``, or metadata input channels): the metadata sources are per
+    echogram and the metadata kernels read one source, so these models take the per-echogram path --
+    ``predict_echogram_memm`` for one echogram after the other, one echogram per "group"; same interface, same results,
+    none of the packing.  An echogram larger than ``group_elems`` takes that path too.
+    Multi-GPU (torch.distributed initialised): the *groups* are dealt round-robin to the ranks, no collective; each rank
+    yields the echograms of its own groups only.
+    ``skip(echogram) -> bool``: echograms to leave out (``save_predictions_memm``'s resume rule); it is asked after the
+    groups have been planned and dealt over the WHOLE input (``iter_memm_groups``), so every echogram keeps its rank
+    whatever the ranks skip.
+    ``stats`` (a dict): receives ``groups``, ``batches`` (the patches of every forward batch), ``fallback_echograms``
+    (per-echogram path: metadata model) and ``solo_echograms`` (per-echogram path: too large for the staging).
+    ``kwargs``: the other keys of the reference's ``config_args`` are accepted and ignored, as by the sibling calls; a
+    keyword that is a near miss of one of this function's own (``difflib.get_close_matches``: ``group_patch``,
+    ``group_elem``, ``seabeds``, ``stat`` ...) is refused, it is a misspelling."""
+    own = ("group_patches", "group_elems", "seabed", "skip", "stats", "predict_fn", "meta_channels")
+    typos = {k: difflib.get_close_matches(k, own, n=1, cutoff=0.8) for k in kwargs}
+    typos = {k: m[0] for k, m in typos.items() if m}
+    if typos:
+        raise TypeError("predict_echograms_memm: unknown keyword(s) " +
+                        ", ".join(f"{k!r} (did you mean {m!r}?)" for k, m in sorted(typos.items())))
+    if not (seabed is None or callable(seabed) or (isinstance(seabed, str) and seabed == "estimate")):
+        raise TypeError("predict_echograms_memm: seabed is None, 'estimate' or a callable(echogram) -> integer array "
+                        f"[n_pings], got {type(seabed).__name__}; an array belongs to a single echogram "
+                        "(predict_echogram_memm takes one)")
+    dev = segpipe.device
+    model = segpipe.model.to(dev).eval()
+    eng = model.infer_engine
+    C = len(segpipe.frequencies)
+    pw, ph = (int(v) for v in patch_size)
+    overlap = int(patch_overlap)
+    step = max(int(batch_size), INTERNAL_BATCH) if predict_fn is None else int(batch_size)
+    group_patches = MEMM_GROUP_BATCHES * step if group_patches is None else int(group_patches)
+    cap = MEMM_GROUP_ELEMS if group_elems is None else int(group_elems)
+    rank, world = parallel.rank_world()
+    stats = {} if stats is None else stats
+    stats.update(groups=0, batches=[], fallback_echograms=0, solo_echograms=0)
+
+    if eng.lmi or eng.in_channels > C:        # metadata planes: one echogram per group, the per-echogram path
+        for eg in shard_memm_groups(echograms, rank, world):
+            if skip is not None and skip(eg):
+                continue
+            sb = None if seabed is None or isinstance(seabed, str) else _memm_survey_seabed(eg, seabed, dev)
+            stats["fallback_echograms"] += 1
+            yield eg, predict_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, predict_fn=predict_fn,
+                                            meta_channels=meta_channels, seabed=seabed if sb is None else sb)
+        return
+
+    groups = iter_memm_groups(echograms, patch_size, patch_overlap, group_patches, seabed, cap, rank, world, dev, skip)
+    first = next(groups, None)
+    if first is None:                                # nothing to do (an empty survey, everything skipped): no staging
+        return
+    groups = itertools.chain([first], groups)
+    W = hip.MEMM_DESC_WORDS
+    n_misc = cap // MEMM_MISC_SHARE + 2 * W
+    table = {"data": (C * cap, torch.float32), "lab": (cap, torch.int16), "misc": (n_misc, torch.int32)}
+
+    def extra():            # transposed planes per device slot, the group's predictions, the result ring
+        return {"data_t": [torch.empty(C * cap, dtype=torch.float32, device=dev) for _ in range(2)],
+                "lab_t": [torch.empty(cap, dtype=torch.int16, device=dev) for _ in range(2)],
+                "out": torch.empty(2 * cap, dtype=torch.float16, device=dev),
+                "pinned": [torch.empty(2 * cap, dtype=torch.float16).pin_memory() for _ in range(2)]}
+
+    def read(job, slot):
+        k, group = job
+        if group[0].elems > cap:                     # too large for the staging: predict_echogram_memm, nothing staged
+            return {}, (group, None, 0)
+        host, bufs = slot(), feed.bufs
+        n, P = len(group), sum(len(r.grid) for r in group)
+        misc = host["misc"].numpy()
+        desc = misc[:2 * W * n].view(np.int64).reshape(n, W)
+        o_cen, o_src, o_sb = 2 * W * n, 2 * W * n + 2 * P, 2 * W * n + 3 * P
+        offs, off, p0 = [], 0, 0
+        for i, r in enumerate(group):
+            R, Wp, npx, Pe = r.n_range, r.n_pings, r.pixels, len(r.grid)
+            assert o_sb + Wp <= n_misc and off + npx <= cap, "memm group staging too small"
+            d = host["data"][C * off:C * (off + npx)].view(C, R, Wp).numpy()
+            for c, m in enumerate(r.echogram.data_memmaps(segpipe.frequencies)):
+                np.copyto(d[c], m, casting="unsafe")
+            np.copyto(host["lab"][off:off + npx].view(R, Wp).numpy(), r.echogram.label_memmap(), casting="unsafe")
+            misc[o_sb:o_sb + Wp] = r.seabed
+            misc[o_cen + 2 * p0:o_cen + 2 * (p0 + Pe)] = np.asarray(r.grid, dtype=np.int32).reshape(-1)
+            misc[o_src + p0:o_src + p0 + Pe] = i
+            desc[i] = (bufs["data_t"][k & 1].data_ptr() + 4 * C * off, bufs["lab_t"][k & 1].data_ptr() + 2 * off,
+                       bufs["dev"][k & 1]["misc"].data_ptr() + 4 * o_sb, bufs["out"].data_ptr() + 2 * 2 * off, Wp, R)
+            offs.append(off)
+            off, p0, o_sb = off + npx, p0 + Pe, o_sb + Wp
+        return ({"data": host["data"][:C * off], "lab": host["lab"][:off], "misc": host["misc"][:o_sb]},
+                (group, offs, off))
+
+    with _ChunkFeed(dev, ("memm", C), table, 3, enumerate(groups), read, extra=extra) as feed:
+        bufs = feed.bufs
+        pinned, out = bufs["pinned"], bufs["out"]
+        events = [torch.cuda.Event() for _ in range(2)]
+        eng.bind()
+
+        def take(group, offs, ring):            # the group whose download went into pinned[ring]
+            events[ring].synchronize()
+            for r, off in zip(group, offs):
+                res = pinned[ring][2 * off:2 * (off + r.pixels)].view(2, r.n_range, r.n_pings)
+                yield r.echogram, res.numpy().astype(np.float64)
+
+        pending = None
+        for k, (d, (group, offs, total)) in enumerate(feed):
+            stats["groups"] += 1
+            if offs is None:                         # the per-echogram path, in its place in the order
+                feed.computed()
+                if pending is not None:
+                    yield from take(*pending)
+                    pending = None
+                r = group[0]
+                stats["solo_echograms"] += 1
+                yield r.echogram, predict_echogram_memm(r.echogram, segpipe, patch_size, patch_overlap, batch_size,
+                                                        predict_fn=predict_fn, seabed=r.seabed)
+                continue
+            n, P = len(group), sum(len(r.grid) for r in group)
+            data_t, lab_t = bufs["data_t"][k & 1], bufs["lab_t"][k & 1]
+            with torch.cuda.stream(feed.copy_stream):        # to the ping-major layout of the gather kernel
+                for r, off in zip(group, offs):
+                    R, Wp, npx = r.n_range, r.n_pings, r.pixels
+                    data_t[C * off:C * (off + npx)].view(C, Wp, R).copy_(
+                        d["data"][C * off:C * (off + npx)].view(C, R, Wp).permute(0, 2, 1))
+                    lab_t[off:off + npx].view(Wp, R).copy_(d["lab"][off:off + npx].view(R, Wp).t())
+            feed.main.wait_stream(feed.copy_stream)
+            misc = d["misc"]
+            cen, src = misc[2 * W * n:], misc[2 * W * n + 2 * P:]
+            out[:2 * total].zero_()
+            for b0 in range(0, P, step):
+                Pb = min(step, P - b0)
+                stats["batches"].append(Pb)
+                x = eng._buf("tiled.x", (Pb * ph * pw, 16))
+                call("crimac_gather_patches_memm_multi", eng.prec, ptr(misc), n, ptr(src, b0), C, ptr(cen, 2 * b0), Pb, ph,
+                     pw, ptr(x), 16)
+                if predict_fn is not None:
+                    probs = predict_fn(x, Pb, ph, pw)
+                else:
+                    probs = eng.forward_nhwc_eval_split(x, Pb, ph, pw, softmax=True)
+                call("crimac_scatter_patches_multi", ptr(probs), probs.shape[1], ptr(misc), n, ptr(src, b0),
+                     ptr(cen, 2 * b0), Pb, ph, pw, overlap, SEABED_PAD, 1)
+            feed.computed()
+            pinned[k & 1][:2 * total].copy_(out[:2 * total], non_blocking=True)
+            events[k & 1].record()
+            if pending is not None:
+                yield from take(*pending)
+            pending = (group, offs, k & 1)
+        if pending is not None:
+            yield from take(*pending)
+
+
+def save_predictions_memm(echograms, segpipe, target_dir, patch_size, patch_overlap, batch_size, resume=True,
+                          suffix=".npy", **kwargs):
+    """The loop over ``save_reader_predictions_memm`` (save_predict.py:222-265, :304-307) for a memm survey: one
+    ``<echogram.name><suffix>`` per echogram in ``target_dir`` (the reference's caller names them ``<name>_pred.npy``),
+    written with ``np.save`` from ``predict_echograms_memm``; ``resume``: an echogram whose file exists is skipped
+    (:233-235) -- nothing of its data is read; its seabed line still is, because the groups and their ranks are planned
+    over ALL echograms (``iter_memm_groups``): with several ranks writing into ``target_dir`` at once, the files a rank
+    happens to see cannot change which rank owns an echogram.  ``kwargs`` go to ``predict_echograms_memm``.  Returns the
+    number of files written (with several ranks: by this rank)."""
+    os.makedirs(target_dir, exist_ok=True)
+
+    def path(eg):
+        return os.path.join(target_dir, eg.name + suffix)
+    skip = (lambda eg: os.path.isfile(path(eg))) if resume else None
+    written = 0
+    for eg, out in predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, skip=skip, **kwargs):
+        np.save(path(eg), out)
+        written += 1
+    return written
 
 
 # ---- whole-survey evaluation (evaluate.py:39-117 of the reference) on the tiled path -------------------------------------

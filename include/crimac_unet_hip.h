@@ -130,7 +130,7 @@ extern "C" {
  * binding must refuse a library whose version differs from the header it was written against (an older build that
  * happens to export every symbol would walk a descriptor array with the wrong stride).  crimac_layer_desc_size() is
  * sizeof(crimac_layer_desc) as the library was compiled. */
-#define CRIMAC_ABI_VERSION 10
+#define CRIMAC_ABI_VERSION 11
 int crimac_version(void);
 int crimac_layer_desc_size(void);
 const char* crimac_last_error(void);
@@ -505,6 +505,29 @@ int crimac_scatter_patches_ex(const float* probs, int ncls, const int* centres, 
                               const unsigned char* seabed_mask, int mask_ping0, int mask_pings, const int* seabed,
                               int seabed_ping0, int seabed_pings, const float* data0, int data_ping0, int data_pings,
                               int seabed_pad, int seabed_rule, void* out, int out_f16, void* stream);
+
+/* Forward batches packed from SEVERAL memmap echograms (tiled_inference.predict_echograms_memm): the two entry points
+ * above read one source and write one destination; here each patch names its echogram, src[p] = index into a
+ * device-resident table of descriptors (n_desc entries; a patch whose src lies outside the table is skipped).  Every
+ * field is 64 bits wide, so a host writes the table as int64 [n_desc][6]; the pointers are device addresses and are
+ * indexed with 64-bit arithmetic -- the echograms of a group may lie anywhere, more than 2^31 bytes apart. */
+typedef struct crimac_memm_desc {
+  const float* data;    /* [C][n_pings][n_range] fp32 linear sv (C is common to the table) */
+  const short* labels;  /* [n_pings][n_range] int16 raw annotation ids (NULL: gather -- no border rule; scatter -- background) */
+  const int* seabed;    /* [n_pings] seabed index per ping from ping 0 (scatter only; NULL = no seabed rule) */
+  void* out;            /* [2][n_range][n_pings] float16 / fp32 predictions (scatter only) */
+  long long n_pings, n_range;
+} crimac_memm_desc;
+/* crimac_gather_patches_memm with the source taken from descs[src[p]]: the same crop, border rule, dB transform,
+ * storage types and NHWC output, bit for bit; centres[p] = (range idx, ping idx) in the patch's own echogram. */
+int crimac_gather_patches_memm_multi(int prec, const crimac_memm_desc* descs, int n_desc, const int* src, int C,
+                                     const int* centres, int P, int ph, int pw, void* out, long ld, void* stream);
+/* crimac_scatter_patches_ex with the memm rules only -- labels, seabed vector (from ping 0), seabed_rule 1, no mask, no
+ * data0 -- and the destination, labels, seabed vector and both extents taken from descs[src[p]] (start_ping 0, n_chunk =
+ * n_pings, H = n_range).  Valid interiors are disjoint across patches and echograms: plain stores, no atomics. */
+int crimac_scatter_patches_multi(const float* probs, int ncls, const crimac_memm_desc* descs, int n_desc, const int* src,
+                                 const int* centres, int P, int ph, int pw, int overlap, int seabed_pad, int out_f16,
+                                 void* stream);
 
 /* RAW evaluation crops of P patches from a resident chunk -- what the reference's gridded test Dataset crops per patch
  * before any transform (evaluate.py:39-117; batch/dataset.py:207-219), i.e. the `data` / `labels` of a batch that
