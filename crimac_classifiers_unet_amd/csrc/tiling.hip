@@ -31,19 +31,25 @@ constexpr int TS = 32;   // tile side
 // the crop's metadata planes (meta_plane_values, crop centred on meta_centres[p] = (range idx, GLOBAL ping idx)), which
 // neither the dB transform nor the border rule touches (batch/dataset.py:109: np.concatenate((data, meta)) after the
 // data transform); db_scaled: db_with_limits_scaled (1 + dB / 75, define_data_transform_test(use_metadata=True)).
-// The body of one block = one 32 x 32 tile of patch blockIdx.z, shared by the single-source kernel and by the kernel that
+// PATCH_LABELS (crimac_gather_patches_memm_labels): the border rule is read off patch_labels [P][ph][pw] int16 instead --
+// the labels of the patch AFTER the test-time label transform, which is what set_data_border_value sees
+// (batch/dataset.py:229-235): a pixel whose transformed label is -100 gets 0.0, every other pixel its dB value, in or
+// outside the extent of `data`.  The labels are those of get_crop_memmap's crop (crimac_gather_eval_crops, flavour 1), so
+// the data crop takes its centre row too: H / 2 when the window covers the whole water column (dataset.py:259-261).
+// The body of one block = one 32 x 32 tile of patch blockIdx.z, shared by the single-source kernels and by the kernel that
 // takes the source of every patch from a descriptor (gather_patches_multi_kernel): one text, the same bits.
-template <typename T>
+template <typename T, bool PATCH_LABELS = false>
 __device__ __forceinline__ void gather_patch_tile(const float* __restrict__ data, int C, int Wd, int H,
                                                   const int* __restrict__ centres, int ph, int pw,
                                                   T* __restrict__ out, int ld,
                                                   const short* __restrict__ border_labels, int db_scaled,
-                                                  const MetaPlaneSrc& meta, const int* __restrict__ meta_centres) {
+                                                  const MetaPlaneSrc& meta, const int* __restrict__ meta_centres,
+                                                  const short* __restrict__ patch_labels = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float* tile = reinterpret_cast<float*>(smem_raw);      // [C][TS (x)][TS + 1 (y)]
   const int p = blockIdx.z;
   const int ty0 = blockIdx.y * TS, tx0 = blockIdx.x * TS;
-  const int cy = centres[2 * p], cx = centres[2 * p + 1];
+  const int cy = PATCH_LABELS && H <= ph ? H / 2 : centres[2 * p], cx = centres[2 * p + 1];
   const int y_base = cy - ((ph + 1) / 2) + 1 + ty0;        // data row of tile row 0 (np.py:40-46)
   const int x_base = cx - ((pw + 1) / 2) + 1 + tx0;
   const int tx = threadIdx.x & 31, tr = threadIdx.x >> 5;  // tr 0..7
@@ -81,6 +87,8 @@ __device__ __forceinline__ void gather_patch_tile(const float* __restrict__ data
     const int py = ty0 + yi, px = tx0 + tx;
     if (py >= ph || px >= pw) continue;
     T* dst = out + (((long)p * ph + py) * pw + px) * ld;
+    // (lanes along ping: the labels of the patch are read as they are written, contiguously)
+    const bool keep = !PATCH_LABELS || patch_labels[((long)p * ph + py) * pw + px] != -100;
     float mv[CRIMAC_MAX_META_PLANES];
     int Cm = 0;
     if (meta.flags) {
@@ -92,7 +100,7 @@ __device__ __forceinline__ void gather_patch_tile(const float* __restrict__ data
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int ch = c0 + j;
-        v[j] = ch < C ? tile[(ch * TS + tx) * (TS + 1) + yi] : ch < C + Cm ? mv[ch - C] : 0.f;
+        v[j] = ch < C ? (keep ? tile[(ch * TS + tx) * (TS + 1) + yi] : 0.f) : ch < C + Cm ? mv[ch - C] : 0.f;
       }
       store8(dst + c0, v);
     }
@@ -107,6 +115,17 @@ __global__ __launch_bounds__(256) void gather_patches_kernel(const float* __rest
                                                              int db_scaled, MetaPlaneSrc meta,
                                                              const int* __restrict__ meta_centres) {
   gather_patch_tile<T>(data, C, Wd, H, centres, ph, pw, out, ld, border_labels, db_scaled, meta, meta_centres);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void gather_patches_labels_kernel(const float* __restrict__ data, int C, int Wd,
+                                                                    int H, const int* __restrict__ centres,
+                                                                    int ph, int pw, T* __restrict__ out, int ld,
+                                                                    const short* __restrict__ patch_labels,
+                                                                    int db_scaled, MetaPlaneSrc meta,
+                                                                    const int* __restrict__ meta_centres) {
+  gather_patch_tile<T, true>(data, C, Wd, H, centres, ph, pw, out, ld, nullptr, db_scaled, meta, meta_centres,
+                             patch_labels);
 }
 
 // probs [P][ncls][ph][pw] fp32; centres [P][2] global (cy, cx); out [2][H][n_chunk] fp32 (or fp16).
@@ -375,7 +394,7 @@ extern "C" int crimac_pr_histogram(const float* logits, int ncls, const void* la
 
 static int gather_run(int prec, const float* data, int C, int Wd, int H, const int* centres, int P, int ph, int pw,
                       void* out, long ld, const short* border_labels, int db_scaled, const MetaPlaneSrc& meta,
-                      const int* meta_centres, void* stream) {
+                      const int* meta_centres, void* stream, const short* patch_labels = nullptr) {
   CRIMAC_REQUIRE(prec >= CRIMAC_PREC_BF16 && prec <= CRIMAC_PREC_MAX, "gather_patches: bad precision %d", prec);
   CRIMAC_REQUIRE(data && centres && out && C > 0 && C <= 16 && Wd > 0 && H > 0 && P > 0 && ph > 0 && pw > 0,
                  "gather_patches: bad arguments (C=%d must be <= 16)", C);
@@ -386,9 +405,15 @@ static int gather_run(int prec, const float* data, int C, int Wd, int H, const i
   dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
   const size_t lds = (size_t)C * TS * (TS + 1) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(gather_patches_kernel<T>, grid, dim3(256), lds, st, data, C, Wd, H,
-                                                 centres, ph, pw, (T*)out, (int)ld, border_labels, db_scaled, meta,
-                                                 meta_centres));
+  if (patch_labels) {
+    CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(gather_patches_labels_kernel<T>, grid, dim3(256), lds, st, data, C,
+                                                   Wd, H, centres, ph, pw, (T*)out, (int)ld, patch_labels, db_scaled,
+                                                   meta, meta_centres));
+  } else {
+    CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(gather_patches_kernel<T>, grid, dim3(256), lds, st, data, C, Wd, H,
+                                                   centres, ph, pw, (T*)out, (int)ld, border_labels, db_scaled, meta,
+                                                   meta_centres));
+  }
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
 }
@@ -419,6 +444,23 @@ extern "C" int crimac_gather_patches_memm_meta(int prec, const float* data, int 
   const MetaPlaneSrc meta{flags, portion_year, portion_day, n_day, time_diff, n_td, seabed, n_sb};
   return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, border_labels, db_scaled ? 1 : 0, meta,
                     meta_centres, stream);
+}
+
+extern "C" int crimac_gather_patches_memm_labels(int prec, const float* data, int C, int Wd, int H, const int* centres,
+                                                 int P, int ph, int pw, void* out, long ld, const short* patch_labels,
+                                                 int db_scaled, int flags, double portion_year,
+                                                 const double* portion_day, int n_day, const double* time_diff, int n_td,
+                                                 const long long* seabed, int n_sb, const int* meta_centres,
+                                                 void* stream) {
+  CRIMAC_REQUIRE(patch_labels, "gather_patches_memm_labels: needs the transformed labels of the patches (border rule)");
+  CRIMAC_REQUIRE(flags >= 0 && flags < 64, "gather_patches_memm_labels: bad metadata flags %d", flags);
+  CRIMAC_REQUIRE(!flags || meta_centres, "gather_patches_memm_labels: metadata planes need the global centres");
+  CRIMAC_REQUIRE(!(flags & 2) || (portion_day && n_day > 0), "gather_patches_memm_labels: portion_day needs its vector");
+  CRIMAC_REQUIRE(!(flags & 4) || (time_diff && n_td > 0), "gather_patches_memm_labels: time_diff needs its vector");
+  CRIMAC_REQUIRE(!(flags & 56) || (seabed && n_sb > 0), "gather_patches_memm_labels: the depth planes need the seabed vector");
+  const MetaPlaneSrc meta{flags, portion_year, portion_day, n_day, time_diff, n_td, seabed, n_sb};
+  return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, nullptr, db_scaled ? 1 : 0, meta, meta_centres,
+                    stream, patch_labels);
 }
 
 extern "C" int crimac_scatter_patches_ex(const float* probs, int ncls, const int* centres, int P, int ph, int pw,

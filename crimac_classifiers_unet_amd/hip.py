@@ -46,7 +46,7 @@ LAYER_CONV3X3, LAYER_UPCONV2X2, LAYER_CONV1X1 = 0, 1, 2     # crimac_layer_desc.
 PREC_BACKWARD = {PREC_F32H3: PREC_F32X3}
 PREC_16BIT = (PREC_BF16, PREC_FP16)
 
-ABI_VERSION = 11        # CRIMAC_ABI_VERSION of include/crimac_unet_hip.h this binding was written against
+ABI_VERSION = 12        # CRIMAC_ABI_VERSION of include/crimac_unet_hip.h this binding was written against
 
 _vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
 
@@ -113,6 +113,8 @@ SIGNATURES = {
     "crimac_gather_patches_memm": [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _l, _vp, _vp],
     "crimac_gather_patches_memm_meta": [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _l, _vp, _i, _i, C.c_double, _vp, _i,
                                         _vp, _i, _vp, _i, _vp, _vp],
+    "crimac_gather_patches_memm_labels": [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _l, _vp, _i, _i, C.c_double, _vp, _i,
+                                          _vp, _i, _vp, _i, _vp, _vp],
     "crimac_scatter_patches_ex": [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i,
                                   _i, _i, _vp, _i, _vp],
     "crimac_gather_patches_memm_multi": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _l, _vp],

@@ -244,16 +244,24 @@ class ChunkPredictor:
         both = torch.from_numpy(np.ascontiguousarray(np.stack([cen, local]))).to(self.data.device)
         return both[0], both[1]
 
-    def _gather(self, cen_d, loc_d, P):
+    def _gather(self, cen_d, loc_d, P, labels_t=None):
         """The network input of a batch of P patches, [P*ph*pw, 16] in the engine's storage type, cropped from the chunk by
         the gather kernel of its kind: zarr -- the data planes through db_with_limits; memm -- + set_data_border_value by
         the raw annotation ids; early injection -- + the metadata planes in channels C.., and db_with_limits_scaled
-        (transforms.py:57-64)."""
+        (transforms.py:57-64).  ``labels_t`` int16 [P, ph, pw] (memm, ``evaluate`` with eval_mode 'region' / 'trace'): the
+        transformed labels of the patches, which set_data_border_value then goes by instead of the raw ids."""
         eng, ms = self.engine, self.meta_source
         ph, pw = self.patch_size[1], self.patch_size[0]
         C, Wd = self.data.shape[0], self.data.shape[1]
         x = eng._buf("tiled.x", (P * ph * pw, 16))
-        if self._early():
+        early = self._early()
+        if labels_t is not None:
+            vec = (ms.flags, ms.portion_year, ptr(ms.portion_day), ms.portion_day.numel(), ptr(ms.time_diff),
+                   ms.time_diff.numel(), ptr(ms.seabed), ms.seabed.numel(), ptr(cen_d.contiguous())) if early else \
+                  (0, 0.0, None, 0, None, 0, None, 0, None)
+            call("crimac_gather_patches_memm_labels", eng.prec, ptr(self.data), C, Wd, self.n_range, ptr(loc_d), P, ph, pw,
+                 ptr(x), 16, ptr(labels_t), 1 if early else 0, *vec)
+        elif early:
             call("crimac_gather_patches_memm_meta", eng.prec, ptr(self.data), C, Wd, self.n_range, ptr(loc_d), P, ph, pw,
                  ptr(x), 16, ptr(self.labels), 1, ms.flags, ms.portion_year, ptr(ms.portion_day), ms.portion_day.numel(),
                  ptr(ms.time_diff), ms.time_diff.numel(), ptr(ms.seabed), ms.seabed.numel(), ptr(cen_d.contiguous()))
@@ -276,9 +284,12 @@ class ChunkPredictor:
         'trace'; ``boxes`` int32 [n, 4] on the GPU, already extended: ``eval_boxes``) -> network input -> eval forward
         (logits) -> ``crimac_pr_histogram``.  The network input follows the reference's per-patch chain: zarr -- the raw
         crop through remove_nan_inf + db_with_limits (``augment_batch``; the crop's nan_to_num came first, so an inf
-        sample reaches the network as 0 dB, not as -75 dB as on the preload path); memm -- ``crimac_gather_patches_memm``
-        (``_meta``) straight from the chunk, which ends with set_data_border_value (define_data_transform_test) exactly
-        as ``predict`` feeds it.
+        sample reaches the network as 0 dB, not as -75 dB as on the preload path); memm -- gathered straight from the
+        chunk, ending with set_data_border_value (define_data_transform_test): 'all' -- by the raw ids,
+        ``crimac_gather_patches_memm`` (``_meta``) exactly as ``predict`` feeds it; 'region' / 'trace' -- the extended mask
+        has turned -100 pixels outside the boxes into -1 BEFORE set_data_border_value looks for -100
+        (batch/dataset.py:229-235), so the rule goes by the TRANSFORMED labels: ``crimac_gather_patches_memm_labels``,
+        with or without metadata planes.
         ``predict_fn(x_nhwc, P, H, W) -> logits [P, 3, H, W]`` replaces the network; ``on_batch(centres [P, 2] numpy,
         labels int16 [P, H, W], logits [P, 3, H, W])`` sees the transformed labels and the logits of every batch, on the
         GPU (tests)."""
@@ -314,25 +325,19 @@ class ChunkPredictor:
             lab = eng._buf("eval.lab", (P, ph, pw), torch.int16)
             call("crimac_gather_eval_crops", ptr(self.data), C, Wd, self.n_range, ptr(self.labels), ptr(loc_d), P, ph,
                  pw, 1 if memm else 0, ptr(raw), ptr(lab))
-            x = meta = None
-            if memm and boxes is not None:
-                # 'region' / 'trace': the extended mask turns -100 pixels outside the boxes into -1 BEFORE
-                # set_data_border_value looks for -100 (batch/dataset.py:229-235), so the border rule follows the
-                # transformed labels and cannot be read off the raw ids as crimac_gather_patches_memm does
-                if eng.lmi or early:
-                    raise NotImplementedError(f"eval_mode={eval_mode!r} with metadata planes on the tiled path; use "
-                                              "eval_mode='all' or the DataLoader path")
-            elif memm:
-                x = self._gather(cen_d, loc_d, P)
-                if eng.lmi:
-                    meta = self.meta_source.planes(cen_d, self.patch_size)
-            logits, labels_t = raw_crops_to_logits(
-                eng, raw, lab, cen_d.long().contiguous(), thr_channel=C - 1, seabed=self.seabed,
-                seabed_ping0=self.seabed_ping0, seabed_pings=0 if self.seabed is None else self.seabed.numel(),
-                mask=self.mask, mask_ping0=self.data_ping0, mask_pings=0 if self.mask is None else self.mask.shape[0],
-                n_range=self.n_range, pad=SEABED_PAD, seabed_rule=1 if memm else 0, overlap=self.patch_overlap,
-                boxes=boxes, meta=meta, x=x, predict_fn=predict_fn, split=True,
-                border_to_0db=memm and boxes is not None)
+            chain = dict(thr_channel=C - 1, seabed=self.seabed, seabed_ping0=self.seabed_ping0,
+                         seabed_pings=0 if self.seabed is None else self.seabed.numel(), mask=self.mask,
+                         mask_ping0=self.data_ping0, mask_pings=0 if self.mask is None else self.mask.shape[0],
+                         n_range=self.n_range, pad=SEABED_PAD, seabed_rule=1 if memm else 0, overlap=self.patch_overlap,
+                         boxes=boxes)
+            cen64 = cen_d.long().contiguous()
+            if memm:
+                labels_t = transform_test_labels(raw, lab, cen64, **chain)
+                x = self._gather(cen_d, loc_d, P, labels_t if boxes is not None else None)
+                meta = self.meta_source.planes(cen_d, self.patch_size) if eng.lmi else None
+                logits = eval_logits(eng, x, P, ph, pw, meta=meta, predict_fn=predict_fn, split=True)
+            else:
+                logits, labels_t = raw_crops_to_logits(eng, raw, lab, cen64, predict_fn=predict_fn, split=True, **chain)
             if on_batch is not None:
                 on_batch(cen, labels_t, logits)
             B, nc, H, W = logits.shape
@@ -341,44 +346,61 @@ class ChunkPredictor:
         return hist
 
 
-def raw_crops_to_logits(eng, data, labels, centres, *, thr_channel, seabed, seabed_ping0, seabed_pings, mask, mask_ping0,
-                        mask_pings, n_range, pad, seabed_rule, overlap, boxes, db_scaled=False, meta=None, batch_in=None,
-                        n_data=None, x=None, predict_fn=None, split=False, border_to_0db=False):
-    """The body the two evaluation flows share -- DataLoader batches of RAW crops (``SegPipe._predict_raw_batch``) and
-    crops gathered from a resident chunk (``ChunkPredictor.evaluate``): data [B, C, H, W] fp32 linear sv, labels [B, H, W]
-    raw annotation ids, centres int64 [B, 2] (range idx, global ping idx), all on the GPU ->
-    (logits [B, ncls, H, W], transformed int16 labels [B, H, W]).
-
-    ``crimac_labels_test_transform`` (seabed vector OR mask, as ``crimac_scatter_patches_ex`` takes them) ->
-    ``crimac_labels_extend_mask`` when ``boxes`` is given -> network input ``x`` (given, or remove_nan_inf + db_with_limits
-    of ``data`` -- of ``batch_in`` = data | metadata planes with ``n_data`` data channels for an early-injection model)
-    -> eval forward (``split``: the two-stream form of the tiled path) or ``predict_fn(x, B, H, W)``.
-    ``border_to_0db``: set_data_border_value by the TRANSFORMED labels (the memm flavour's define_data_transform_test,
-    transforms.py:57-64): a pixel whose label came out as -100 enters the dB transform as 1.0 and leaves it as 0.0 dB."""
-    dev = data.device
+def transform_test_labels(data, labels, centres, *, thr_channel, seabed, seabed_ping0, seabed_pings, mask, mask_ping0,
+                          mask_pings, n_range, pad, seabed_rule, overlap, boxes):
+    """define_label_transform_test (batch/transforms.py:78-92) of a batch of RAW crops on the GPU: data [B, C, H, W] fp32
+    linear sv, labels [B, H, W] raw annotation ids, centres int64 [B, 2] (range idx, global ping idx) -> transformed int16
+    labels [B, H, W].  ``crimac_labels_test_transform`` (seabed vector OR mask, as ``crimac_scatter_patches_ex`` takes
+    them) -> ``crimac_labels_extend_mask`` when ``boxes`` is given (eval_mode 'region' / 'trace')."""
     B, C, H, W = data.shape
-    out = torch.empty((B, H, W), dtype=torch.int16, device=dev)
-    with torch.no_grad(), torch.cuda.device(dev):
+    out = torch.empty((B, H, W), dtype=torch.int16, device=data.device)
+    with torch.cuda.device(data.device):
         call("crimac_labels_test_transform", ptr(labels), labels.element_size(), ptr(data), thr_channel, 1e-7, 1e-4,
              ptr(centres), ptr(seabed), seabed_ping0, seabed_pings, ptr(mask), mask_ping0, mask_pings, n_range, pad,
              seabed_rule, overlap, ptr(out), B, C, H, W)
-        if boxes is not None:                    # eval_mode 'region' / 'trace'
+        if boxes is not None:
             call("crimac_labels_extend_mask", ptr(out), ptr(data), C, ptr(centres), ptr(boxes), int(boxes.shape[0]), -1,
                  B, H, W)
-        if x is None:                            # remove_nan_inf + db_with_limits (db_with_limits_scaled with metadata)
-            if border_to_0db:
-                data = data.masked_fill((out == -100).unsqueeze(1), 1.0)
-            if batch_in is not None:
-                x, _ = eng.augment_batch(batch_in, None, 0, do_noise=False, do_flip=False, db_scaled=True, n_data=n_data)
-            else:
-                x, _ = eng.augment_batch(data, None, 0, do_noise=False, do_flip=False, db_scaled=db_scaled)
+    return out
+
+
+def eval_logits(eng, x, B, H, W, meta=None, predict_fn=None, split=False):
+    """Eval forward of a network input ``x`` [B*H*W, 16] -> logits [B, ncls, H, W]: ``predict_fn(x, B, H, W)`` when given,
+    else the engine (``split``: the two-stream form of the tiled path, which takes no metadata planes)."""
+    with torch.no_grad(), torch.cuda.device(x.device):
         if predict_fn is not None:
-            logits = predict_fn(x, B, H, W)
-        elif split and meta is None:
-            logits = eng.forward_nhwc_eval_split(x, B, H, W, softmax=False)
+            return predict_fn(x, B, H, W)
+        if split and meta is None:
+            return eng.forward_nhwc_eval_split(x, B, H, W, softmax=False)
+        return eng.forward_nhwc(x, B, H, W, training=False, meta=meta)
+
+
+def raw_crops_to_logits(eng, data, labels, centres, *, thr_channel, seabed, seabed_ping0, seabed_pings, mask, mask_ping0,
+                        mask_pings, n_range, pad, seabed_rule, overlap, boxes, db_scaled=False, meta=None, batch_in=None,
+                        n_data=None, predict_fn=None, split=False, border_to_0db=False):
+    """Batches of RAW crops that have no resident chunk behind them -- the DataLoader flow
+    (``SegPipe._predict_raw_batch``) and the zarr flavour of ``ChunkPredictor.evaluate``: data [B, C, H, W] fp32 linear sv,
+    labels [B, H, W] raw annotation ids, centres int64 [B, 2] (range idx, global ping idx), all on the GPU ->
+    (logits [B, ncls, H, W], transformed int16 labels [B, H, W]).
+
+    ``transform_test_labels`` -> network input: remove_nan_inf + db_with_limits of
+    ``data`` -- of ``batch_in`` = data | metadata planes with ``n_data`` data channels for an early-injection model ->
+    ``eval_logits``.
+    ``border_to_0db``: set_data_border_value by the TRANSFORMED labels (the memm flavour's define_data_transform_test,
+    transforms.py:57-64): a pixel whose label came out as -100 enters the dB transform as 1.0 and leaves it as 0.0 dB.
+    (A resident memm chunk gets the same from ``crimac_gather_patches_memm_labels`` in one pass.)"""
+    B, C, H, W = data.shape
+    out = transform_test_labels(data, labels, centres, thr_channel=thr_channel, seabed=seabed, seabed_ping0=seabed_ping0,
+                                seabed_pings=seabed_pings, mask=mask, mask_ping0=mask_ping0, mask_pings=mask_pings,
+                                n_range=n_range, pad=pad, seabed_rule=seabed_rule, overlap=overlap, boxes=boxes)
+    with torch.no_grad(), torch.cuda.device(data.device):
+        if border_to_0db:
+            data = data.masked_fill((out == -100).unsqueeze(1), 1.0)
+        if batch_in is not None:         # remove_nan_inf + db_with_limits_scaled of the data planes, the rest as it is
+            x, _ = eng.augment_batch(batch_in, None, 0, do_noise=False, do_flip=False, db_scaled=True, n_data=n_data)
         else:
-            logits = eng.forward_nhwc(x, B, H, W, training=False, meta=meta)
-    return logits, out
+            x, _ = eng.augment_batch(data, None, 0, do_noise=False, do_flip=False, db_scaled=db_scaled)
+    return eval_logits(eng, x, B, H, W, meta=meta, predict_fn=predict_fn, split=split), out
 
 
 def eval_boxes(reader, eval_mode, extend_size=20):

@@ -126,11 +126,11 @@ extern "C" {
 #define CRIMAC_EPI_WROWS 32
 
 /* Library identity / error text.  crimac_version() returns CRIMAC_ABI_VERSION of the build: it is bumped whenever a
- * struct passed by pointer (crimac_layer_desc), the meaning of an argument or the set of precisions changes, and a
- * binding must refuse a library whose version differs from the header it was written against (an older build that
- * happens to export every symbol would walk a descriptor array with the wrong stride).  crimac_layer_desc_size() is
- * sizeof(crimac_layer_desc) as the library was compiled. */
-#define CRIMAC_ABI_VERSION 11
+ * struct passed by pointer (crimac_layer_desc), the meaning of an argument, the set of precisions or the set of entry
+ * points changes, and a binding must refuse a library whose version differs from the header it was written against (an
+ * older build that happens to export every symbol would walk a descriptor array with the wrong stride).
+ * crimac_layer_desc_size() is sizeof(crimac_layer_desc) as the library was compiled. */
+#define CRIMAC_ABI_VERSION 12
 int crimac_version(void);
 int crimac_layer_desc_size(void);
 const char* crimac_last_error(void);
@@ -477,6 +477,23 @@ int crimac_gather_patches_memm_meta(int prec, const float* data, int C, int Wd, 
                                     int flags, double portion_year, const double* portion_day, int n_day,
                                     const double* time_diff, int n_td, const long long* seabed, int n_sb,
                                     const int* meta_centres, void* stream);
+/* The same crop for the test-set evaluation with eval_mode 'region' / 'trace' (ChunkPredictor.evaluate): there
+ * get_extended_label_mask_for_crop turns -100 pixels outside the school boxes into -1 BEFORE set_data_border_value looks
+ * for -100 (batch/dataset.py:229-235; transforms.py:57-64, :87-90), so the border rule cannot be read off the raw
+ * annotation ids.  patch_labels [P][ph][pw] int16: the labels of the patches as crimac_labels_test_transform (+
+ * crimac_labels_extend_mask) left them; a pixel whose label is -100 is set to 0.0 after the dB transform, every other
+ * pixel keeps its dB value -- -75 dB (0.0 with db_scaled) outside the extent of `data`.  The labels belong to
+ * get_crop_memmap's crop (crimac_gather_eval_crops, flavour 1), and the data crop is placed as that one: centre row H / 2
+ * when H <= ph.  Everything else -- dB transform, db_scaled, channel order, zero padding, storage types, the metadata
+ * planes in channels C.. -- is crimac_gather_patches_memm_meta's, bit for bit; flags == 0 (a model without metadata
+ * input channels: no planes, the vectors and meta_centres are not read) is allowed here.  Where patch_labels is -100
+ * exactly on the pixels whose raw id is negative or which lie outside `data` (eval_mode 'all'), the output equals
+ * crimac_gather_patches_memm's / _meta's. */
+int crimac_gather_patches_memm_labels(int prec, const float* data, int C, int Wd, int H, const int* centres, int P,
+                                      int ph, int pw, void* out, long ld, const short* patch_labels, int db_scaled,
+                                      int flags, double portion_year, const double* portion_day, int n_day,
+                                      const double* time_diff, int n_td, const long long* seabed, int n_sb,
+                                      const int* meta_centres, void* stream);
 
 /* fill_out_array (save_predict.py:41-65) for P patches: probs [P][ncls][ph][pw] fp32 softmax;
  * centres[p] = (range idx, GLOBAL ping idx); writes channels SANDEEL(1), OTHER(2) of every valid
