@@ -14,12 +14,12 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_NAME = "libcrimac_unet_hip.so"
 LIB_PATH = os.path.join(PKG_DIR, LIB_NAME)
+HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "crimac_unet_hip.h")      # the C ABI: compiled from, and read by hip.py
 SOURCES = ["conv3x3.hip", "conv3x3_glds.hip", "igemm.hip", "upconv.hip", "wgrad.hip", "elementwise.hip", "pack.hip", "upsample.hip", "narrow.hip", "tiling.hip", "augment.hip", "labels.hip", "meta.hip", "seabed.hip", "calib.hip"]
 def _headers():
     """Every header a source may include: csrc/*.h plus the public C-ABI header."""
     import glob
-    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [
-        os.path.join(os.path.dirname(PKG_DIR), "include", "crimac_unet_hip.h")]
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [HEADER]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-munsafe-fp-atomics",
          "-Wno-unused-value"] + os.environ.get("CRIMAC_HIPCC_EXTRA", "").split()
 

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -46,121 +47,117 @@ LAYER_CONV3X3, LAYER_UPCONV2X2, LAYER_CONV1X1 = 0, 1, 2     # crimac_layer_desc.
 PREC_BACKWARD = {PREC_F32H3: PREC_F32X3}
 PREC_16BIT = (PREC_BF16, PREC_FP16)
 
-ABI_VERSION = 12        # CRIMAC_ABI_VERSION of include/crimac_unet_hip.h this binding was written against
 
-_vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
+class HipLibraryError(RuntimeError):
+    pass
 
-# name -> argtypes, exactly the prototypes of include/crimac_unet_hip.h
-SIGNATURES = {
-    "crimac_igemm_conv": [_i, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i,
-                          _vp, _l, _i, _i, _i, _vp],
-    "crimac_conv3x3": [_i, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _i,
-                       _vp, _l, _vp, _l, _vp],
-    "crimac_conv3x3_pool": [_i, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _l, _i, _vp, _l, _vp],
-    "crimac_conv3x3_cols": [_i, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _i,
-                            _vp, _l, _vp, _l, _i, _i, _vp],
-    "crimac_upconv2x2_dgrad_bnb": [_vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _i, _vp],
-    "crimac_upconv2x2_dgrad_bnb_prec": [_i, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _i,
-                                        _vp],
-    "crimac_sum_replicas": [_vp, _i, _l, _i, _vp, _vp, _vp, _vp, _vp],
-    "crimac_wgrad": [_i, _i, _vp, _l, _i, _vp, _l, _i, _i, _i, _i, _vp, _i, _vp],
-    "crimac_wgrad_partials": [_i, _i, _vp, _l, _i, _vp, _l, _i, _i, _i, _i, _vp, _l, _i, _vp],
-    "crimac_wgrad_group": [_i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp],
-    "crimac_conv1x1_up2x": [_i, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp],
-    "crimac_up2x_adjoint": [_i, _vp, _l, _i, _i, _i, _i, _vp, _l, _vp],
-    "crimac_conv1x1_dgrad": [_i, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _vp],
-    "crimac_conv1x1_wgrad": [_i, _vp, _l, _i, _vp, _l, _i, _l, _vp, _vp],
-    "crimac_conv3x3_narrow": [_i, _vp, _l, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _l, _vp, _vp, _i, _i,
-                              _vp],
-    "crimac_upconv2x2_narrow": [_i, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp, _l, _i, _vp],
-    "crimac_upconv2x2_dgrad_narrow": [_i, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _l, _vp],
-    "crimac_pack_conv3x3": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
-    "crimac_pack_upconv2x2": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "crimac_unpack_wgrad_conv3x3": [_vp, _i, _i, _i, _vp, _vp],
-    "crimac_unpack_wgrad_upconv2x2": [_vp, _i, _i, _vp, _vp],
-    "crimac_pack_layers": [_vp, _i, _i, _vp],
-    "crimac_unpack_wgrad_layers": [_vp, _i, _vp],
-    "crimac_nchw_to_nhwc": [_i, _vp, _vp, _i, _i, _i, _i, _l, _vp],
-    "crimac_colstats": [_i, _vp, _l, _l, _i, _vp, _vp, _vp],
-    "crimac_colsum_f32": [_i, _vp, _l, _l, _i, _vp, _vp],
-    "crimac_bn_finalize": [_vp, _vp, _i, _l, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "crimac_bn_act_pool": [_i, _vp, _l, _vp, _vp, _i, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp],
-    "crimac_bn_train_act_pool": [_i, _vp, _l, _vp, _vp, _i, _l, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _l, _i, _vp, _l,
-                                 _vp, _l, _i, _i, _i, _i, _vp],
-    "crimac_unpool_add": [_i, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp, _i,
-                          _vp],
-    "crimac_bn_bwd_reduce": [_i, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _l, _i, _vp, _vp, _vp],
-    "crimac_bn_bwd_apply": [_i, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _i, _vp, _l, _vp,
-                            _vp, _vp, _vp],
-    "crimac_bn_bwd_apply_replicas": [_i, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _i, _l, _l, _i, _vp, _l, _vp, _vp, _vp],
-    "crimac_unpool_bn_bwd_apply_replicas": [_i, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _i, _l, _vp, _l, _i, _i, _i, _i,
-                                            _vp, _vp, _vp],
-    "crimac_head_fwd": [_i, _vp, _l, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
-    "crimac_head_bwd": [_i, _vp, _vp, _l, _i, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp,
-                        _i, _vp],
-    "crimac_softmax_nchw": [_vp, _vp, _i, _i, _i, _i, _vp],
-    "crimac_wce_fwd": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "crimac_wce_bwd": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp],
-    "crimac_sgd_momentum": [_vp, _vp, _vp, _l, _f, _f, _f, _i, _vp],
-    "crimac_grad_overflow_flag": [_vp, _l, _vp, _vp],
-    "crimac_sgd_momentum_guarded": [_vp, _vp, _vp, _l, _f, _f, _f, _i, _vp, _vp],
-    "crimac_meta_planes": [_vp, _i, _i, _i, _i, C.c_double, _vp, _i, _vp, _i, _vp, _i, _vp, _vp],
-    "crimac_meta_mlp_fwd": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "crimac_meta_inject_fwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "crimac_meta_bwd": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                        _vp, _vp],
-    "crimac_gather_patches": [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _l, _vp],
-    "crimac_gather_patches_memm": [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _l, _vp, _vp],
-    "crimac_gather_patches_memm_meta": [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _l, _vp, _i, _i, C.c_double, _vp, _i,
-                                        _vp, _i, _vp, _i, _vp, _vp],
-    "crimac_gather_patches_memm_labels": [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _l, _vp, _i, _i, C.c_double, _vp, _i,
-                                          _vp, _i, _vp, _i, _vp, _vp],
-    "crimac_scatter_patches_ex": [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i,
-                                  _i, _i, _vp, _i, _vp],
-    "crimac_gather_patches_memm_multi": [_i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _l, _vp],
-    "crimac_scatter_patches_multi": [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "crimac_gather_eval_crops": [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
-    "crimac_augment_db_nhwc": [_i, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _i, _i, _i, _i, _l, C.c_ulonglong,
-                               _i, _i, _i, _vp],
-    "crimac_augment_db_meta_nhwc": [_i, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _i, _i, _i, _i, _l, C.c_ulonglong,
-                                    _i, _i, _i, _i, _vp],
-    "crimac_augment_flip_planes": [_vp, _vp, _i, _i, _i, _i, C.c_ulonglong, _i, _vp],
-    "crimac_refine_labels": [_vp, _i, _vp, _vp, _i, _f, _f, _i, _vp, _i, _i, _i, _i, _vp],
-    "crimac_pr_histogram": [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
-    "crimac_mfma_calibrate": [_i, _i, _vp, _vp],
-    "crimac_labels_test_transform": [_vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i,
-                                     _i, _i],
-    "crimac_labels_extend_mask": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i],
-    "crimac_scatter_patches": [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i,
-                               _i, _vp, _vp],
-    "crimac_seabed_columns": [_vp, _i, _l, _i, _i, _i, _i, _vp, _vp, _l, _vp],
-}
 
+_SCALARS = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "unsigned int": C.c_uint,
+            "unsigned long long": C.c_ulonglong, "float": C.c_float, "double": C.c_double}
+_KEYWORDS = {"const", "void", "char", "short", "signed", "struct", *" ".join(_SCALARS).split()}
+
+
+def _declarator(decl: str, where: str):
+    """``const float* w`` / ``long long n`` -> (name, ctype).  Every pointer is a c_void_p (so ``byref``, ctypes arrays and
+    ``None`` pass at every call site) whatever it points to -- `short* p` and `crimac_x* p` alike: ctypes never looks
+    through it, so the base type needs no entry in the map; scalars come from the closed map above.  Anything else raises."""
+    toks = decl.replace("*", " * ").split()
+    if toks[:1] == ["const"]:
+        del toks[0]
+    *kind, name = toks or [""]
+    if not kind or not re.fullmatch(r"[A-Za-z_]\w*", name) or name in _KEYWORDS:
+        raise HipLibraryError(f"{where}: `{decl.strip()}` is not `<type> <name>`")
+    if len(kind) >= 2 and kind[-1] == "*" and "*" not in kind[:-1]:
+        return name, C.c_void_p
+    if " ".join(kind) not in _SCALARS:
+        raise HipLibraryError(f"{where}: unknown type `{' '.join(kind)}` in `{decl.strip()}`")
+    return name, _SCALARS[" ".join(kind)]
+
+
+def parse_header(text: str):
+    """The C ABI as include/crimac_unet_hip.h states it: (prototypes, structs, defines).
+    prototypes: name -> (restype, argtypes, takes_stream), takes_stream = the last parameter is ``void* stream``;
+    structs: tag -> [(field, ctype)] in declaration order; defines: every ``#define CRIMAC_<NAME> <integer expression>``,
+    evaluated in order.  A declaration this does not recognise raises HipLibraryError naming it: it never guesses."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S).replace("\\\n", " ")
+    protos, structs, defines = {}, {}, {}
+    for line in re.findall(r"^[ \t]*(#.*?)\s*$", text, flags=re.M):
+        m = re.fullmatch(r"#\s*define\s+(CRIMAC_\w+)\s+(\S.*)", line)
+        if m:
+            expr = re.sub(r"CRIMAC_\w+", lambda n: f"({defines.get(n.group(), '?')})", m.group(2))
+            if not re.fullmatch(r"[\d\s()|&<>+*~-]+", expr) or "**" in expr:       # (`**` is Python, not C)
+                raise HipLibraryError(f"#define {m.group(1)}: `{m.group(2)}` is not an integer expression of earlier defines")
+            try:
+                defines[m.group(1)] = int(eval(expr, {"__builtins__": {}}))
+            except Exception as e:
+                raise HipLibraryError(f"#define {m.group(1)}: cannot evaluate `{m.group(2)}` ({e})") from None
+        elif not re.fullmatch(r"#\s*(ifn?def\s+\w+|endif|define\s+\w+)", line):       # include guard, __cplusplus
+            raise HipLibraryError(f"cannot parse the directive `{line}`")
+
+    def struct(m):
+        fields = structs.setdefault(m.group(1), [])
+        for decl in filter(None, map(str.strip, m.group(2).split(";"))):
+            first, *more = map(str.strip, decl.split(","))
+            name, ctype = _declarator(first, f"struct {m.group(1)}")
+            if more and (ctype is C.c_void_p or not all(re.fullmatch(r"[A-Za-z_]\w*", n) for n in more)):
+                raise HipLibraryError(f"struct {m.group(1)}: cannot parse the field list `{decl}`")
+            fields += [(n, ctype) for n in (name, *more)]
+        return ""
+
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\s+(crimac_\w+)\s*\{([^{}]*)\}\s*\1\s*;", struct, text)
+    body = re.fullmatch(r'\s*extern\s+"C"\s*\{(.*)\}\s*', text, flags=re.S)
+    if not body:
+        raise HipLibraryError('the declarations are not one `extern "C" { ... }` block')
+    for stmt in filter(None, map(str.strip, body.group(1).split(";"))):
+        m = re.fullmatch(r"(int|const\s+char\s*\*)\s*(crimac_\w+)\s*\((.*)\)", stmt, flags=re.S)
+        if not m:
+            raise HipLibraryError(f"cannot parse the declaration `{' '.join(stmt.split())}`")
+        params = [] if m.group(3).strip() == "void" else m.group(3).split(",")
+        protos[m.group(2)] = (C.c_int if m.group(1) == "int" else C.c_char_p,
+                              [_declarator(a, m.group(2))[1] for a in params],
+                              bool(params) and params[-1].replace("*", " * ").split() == ["void", "*", "stream"])
+    return protos, structs, defines
+
+
+try:
+    with open(_build.HEADER) as _header:
+        PROTOTYPES, STRUCTS, DEFINES = parse_header(_header.read())
+except OSError as e:
+    raise HipLibraryError(f"cannot read the C-ABI header {_build.HEADER} ({e}): the binding is derived from it, so the "
+                          "package needs include/ next to it (also with a CRIMAC_LIB override)") from None
+del _header
+
+ABI_VERSION = DEFINES["CRIMAC_ABI_VERSION"]      # a built library of another version is stale (load_library)
+PR_BINS = DEFINES["CRIMAC_PR_BINS"]
+# name -> argtypes of every entry point that returns a status and takes the stream as its last argument (`call`)
+SIGNATURES = {name: args for name, (res, args, stream) in PROTOTYPES.items() if stream and res is C.c_int}
 
 
 class LayerDesc(C.Structure):
     """crimac_layer_desc (include/crimac_unet_hip.h): one Conv2d / ConvTranspose2d layer's buffers."""
-    _fields_ = [("w", _vp), ("grad", _vp), ("dw", _vp), ("fwd_hi", _vp), ("fwd_lo", _vp), ("dg_hi", _vp),
-                ("dg_lo", _vp), ("kind", _i), ("Co", _i), ("Ci", _i), ("Ci_pad", _i), ("dw_splits", _i),
-                ("dw_stride", _l)]
+    _fields_ = STRUCTS["crimac_layer_desc"]
 
 
 class WgradGroupLayer(C.Structure):
     """crimac_wgrad_group_layer (include/crimac_unet_hip.h): one conv3x3 layer of a grouped weight-gradient launch."""
-    _fields_ = [("f", _vp), ("f_ld", _l), ("CF", _i), ("s", _vp), ("s_ld", _l), ("CS", _i), ("Hf", _i), ("Wf", _i),
-                ("dw", _vp), ("tiles_y", _i), ("tiles_x", _i), ("ntiles", _l), ("tiles_per_block", _i), ("nsplits", _i)]
+    _fields_ = STRUCTS["crimac_wgrad_group_layer"]
 
+
+class MemmDesc(C.Structure):
+    """crimac_memm_desc (include/crimac_unet_hip.h): one echogram of a multi-source gather / scatter."""
+    _fields_ = STRUCTS["crimac_memm_desc"]
+
+
+if any(C.sizeof(t) != 8 for _, t in MemmDesc._fields_):
+    raise HipLibraryError("crimac_memm_desc has a field that is not 64 bits wide: the host writes the table as int64 words")
+MEMM_DESC_WORDS = C.sizeof(MemmDesc) // 8      # data, labels, seabed, out (device addresses), n_pings, n_range
 
 WGRAD_GROUP_MAX_LAYERS = 16      # CRIMAC_WGRAD_GROUP_MAX_LAYERS
 MASK_PER_PATCH = -2147483648      # CRIMAC_MASK_PER_PATCH
-MEMM_DESC_WORDS = 6      # crimac_memm_desc as int64: data, labels, seabed, out (device addresses), n_pings, n_range
-
 
 _lib = None
-
-
-class HipLibraryError(RuntimeError):
-    pass
+_entry = {}          # name -> bound function of every SIGNATURES entry point, filled by load_library (`call` looks up here)
 
 
 def library_path() -> str:
@@ -178,34 +175,26 @@ def load_library():
             f"{path} is missing: build it with `python -m crimac_classifiers_unet_amd.build` "
             "(hipcc, gfx950). There is no CPU fallback for the U-Net hot path.")
     lib = C.CDLL(path)
-    lib.crimac_version.restype = C.c_int
-    lib.crimac_version.argtypes = []
-    lib.crimac_last_error.restype = C.c_char_p
-    lib.crimac_last_error.argtypes = []
-    ver = lib.crimac_version()
+
+    def declare(name):
+        fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
+        fn.restype, fn.argtypes = PROTOTYPES[name][:2]
+        return fn
+
+    ver = declare("crimac_version")()
     if ver != ABI_VERSION:
         raise HipLibraryError(f"{path} has ABI version {ver}, this binding needs {ABI_VERSION}: rebuild it "
                               "(`python -m crimac_classifiers_unet_amd.build --force`)")
     if not hasattr(lib, "crimac_layer_desc_size"):
         raise HipLibraryError(f"{path} does not export crimac_layer_desc_size: stale build")
-    lib.crimac_layer_desc_size.restype = C.c_int
-    lib.crimac_layer_desc_size.argtypes = []
-    if lib.crimac_layer_desc_size() != C.sizeof(LayerDesc):
-        raise HipLibraryError(f"{path}: crimac_layer_desc is {lib.crimac_layer_desc_size()} bytes in the library, "
-                              f"{C.sizeof(LayerDesc)} in this binding")
-    lib.crimac_wgrad_splits.restype = C.c_int          # (returns a count, not a status; no stream argument)
-    lib.crimac_wgrad_splits.argtypes = [_i, _i, _i, _i, _i, _i, _i, _i]
-    lib.crimac_wgrad_group_layer_size.restype = C.c_int
-    lib.crimac_wgrad_group_layer_size.argtypes = []
-    if lib.crimac_wgrad_group_layer_size() != C.sizeof(WgradGroupLayer):
-        raise HipLibraryError(f"{path}: crimac_wgrad_group_layer is {lib.crimac_wgrad_group_layer_size()} bytes in the "
-                              f"library, {C.sizeof(WgradGroupLayer)} in this binding")
-    lib.crimac_wgrad_group_plan.restype = C.c_int      # (host-only planner: returns the queue capacity, no stream)
-    lib.crimac_wgrad_group_plan.argtypes = [_i, _vp, _i, _i, _i, _vp, _i, _vp]
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
-        fn.restype = C.c_int
-        fn.argtypes = argtypes
+    for size_fn, mirror in (("crimac_layer_desc_size", LayerDesc), ("crimac_wgrad_group_layer_size", WgradGroupLayer)):
+        size = declare(size_fn)()
+        if size != C.sizeof(mirror):
+            raise HipLibraryError(f"{path}: {size_fn[:-5]} is {size} bytes in the library, {C.sizeof(mirror)} in this binding")
+    for name in PROTOTYPES:
+        fn = declare(name)
+        if name in SIGNATURES:
+            _entry[name] = fn
     _lib = lib
     return lib
 
@@ -253,16 +242,25 @@ class Act:
 PROFILE = None
 
 
+def _entry_point(name: str):
+    """What `call` falls back to when `_entry` has no such name: the first launch of the process, or a name to refuse."""
+    if name not in SIGNATURES:
+        raise HipLibraryError(f"{name} is not an entry point that takes a stream (include/crimac_unet_hip.h): "
+                              "call a stream-less one through load_library()")
+    load_library()
+    return _entry[name]
+
+
 def call(name: str, *args, flops=None, mfmas=1):
     """``flops``: algorithmic FLOPs of the launch (profiled launches only); ``mfmas``: MFMAs the kernel spends per
     algorithmic product (1 for 16-bit operands, 3 for plane pairs ...): flops * mfmas is what the MFMA pipe executes, the
     figure a roofline against the dense 16-bit peak needs when one step mixes precisions ('h3f')."""
-    lib = load_library()
+    fn = _entry.get(name) or _entry_point(name)
     if PROFILE is not None and flops is not None:
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
-        _check(getattr(lib, name)(*args, _stream()), name)
+        _check(fn(*args, _stream()), name)
         e.record()
         PROFILE.append((name, flops, s, e, mfmas))
         return
-    _check(getattr(lib, name)(*args, _stream()), name)
+    _check(fn(*args, _stream()), name)

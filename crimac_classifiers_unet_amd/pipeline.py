@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import parallel
+from . import hip, parallel
 from .train_ops import ExponentialLR, SGDMomentum, WeightedCrossEntropy
 from .unet import UNet_Baseline, UNet_LateMetInject
 
@@ -432,7 +432,7 @@ class SegPipe:
         return labels, preds, mean_loss
 
     # -- histogram form of the same metrics: no per-pixel vectors leave the GPU --------------------
-    PR_BINS = 16384            # float16 bit patterns of [0, 1] are 0 .. 0x3C00
+    PR_BINS = hip.PR_BINS      # CRIMAC_PR_BINS: float16 bit patterns of [0, 1] are 0 .. 0x3C00
 
     def get_pr_histograms_dataloader(self, dataloader, criterion=None, disable_tqdm=True):
         """GPU form of get_predictions_dataloader + the masking of validate_model_training

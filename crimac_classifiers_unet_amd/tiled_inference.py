@@ -1262,7 +1262,7 @@ def save_predictions_memm(echograms, segpipe, target_dir, patch_size, patch_over
 
 
 # ---- whole-survey evaluation (evaluate.py:39-117 of the reference) on the tiled path -------------------------------------
-PR_BINS = 16384            # CRIMAC_PR_BINS: float16 bit patterns of [0, 1] are 0 .. 0x3C00
+PR_BINS = hip.PR_BINS      # CRIMAC_PR_BINS: float16 bit patterns of [0, 1] are 0 .. 0x3C00
 
 
 def plan_eval_grid(n_range, seabed, n_pings, patch_size, patch_overlap, memm=False):

@@ -46,6 +46,153 @@ def test_library_exports_every_declared_symbol():
     assert lib2.crimac_wgrad_group_layer_size() == ctypes.sizeof(hip.WgradGroupLayer)
 
 
+def _header_text():
+    return open(build.HEADER).read()
+
+
+def test_binding_reads_these_prototypes_from_the_header():
+    """Written out by hand from include/crimac_unet_hip.h: every scalar type of the parser's map, struct pointers, both
+    return types, entry points with and without a stream."""
+    i, l, f, d, vp = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
+    u64 = ctypes.c_ulonglong
+    protos, _, _ = hip.parse_header(_header_text())
+    assert protos == hip.PROTOTYPES
+    want = {
+        "crimac_meta_planes": (i, [vp, i, i, i, i, d, vp, i, vp, i, vp, i, vp, vp], True),
+        "crimac_augment_db_nhwc": (i, [i, vp, vp, i, vp, vp, vp, i, f, f, i, i, i, i, l, u64, i, i, i, vp], True),
+        "crimac_gather_patches_memm_multi": (i, [i, vp, i, vp, i, vp, i, i, i, vp, l, vp], True),
+        "crimac_wgrad_group_plan": (i, [i, vp, i, i, i, vp, i, vp], False),
+        "crimac_version": (i, [], False),
+        "crimac_last_error": (ctypes.c_char_p, [], False),
+        "crimac_mfma_calibrate": (i, [i, i, vp, vp, vp], True),
+        "crimac_labels_test_transform": (i, [vp, i, vp, i, f, f, vp, vp, i, i, vp, i, i, i, i, i, i, vp, i, i, i, i, vp], True),
+        "crimac_labels_extend_mask": (i, [vp, vp, i, vp, vp, i, i, i, i, i, vp], True),
+    }
+    for name, proto in want.items():
+        assert protos[name] == proto, name
+    # the remaining scalar types of the map, on header text of the same form
+    # (a pointer is a c_void_p whatever its base type: `short` is no scalar of the map, `short*` is a pointer like any other)
+    text = 'extern "C" {\nint crimac_x(long long a, unsigned int b, const unsigned int* c, short* d, void* stream);\n}\n'
+    assert hip.parse_header(text)[0] == {"crimac_x": (i, [ctypes.c_longlong, ctypes.c_uint, vp, vp, vp], True)}
+
+
+def test_every_declared_function_is_bound_as_the_header_declares_it():
+    lib = hip.load_library()
+    assert sorted(hip.PROTOTYPES) == _declared_symbols() and len(hip.PROTOTYPES) >= 70
+    for name, (restype, argtypes, takes_stream) in hip.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+        assert takes_stream == (name in hip.SIGNATURES), name
+    text = re.sub(r"/\*.*?\*/", "", _header_text(), flags=re.S)
+    with_stream = set(re.findall(r"\b(crimac_[a-z0-9_]+)\s*\([^()]*,\s*void\*\s*stream\s*\)", text))
+    assert set(hip.SIGNATURES) == with_stream
+    assert all(hip.SIGNATURES[name] is hip.PROTOTYPES[name][1] for name in with_stream)
+
+
+@pytest.mark.parametrize("decl, named", [
+    ("int crimac_bad(int a, short n, void* stream);", "crimac_bad"),                       # unknown scalar type
+    ("int crimac_bad(int a, const float*, void* stream);", "crimac_bad"),                  # parameter without a name
+    ("int crimac_bad(int, void* stream);", "crimac_bad"),
+    ("int crimac_bad(float** rows, void* stream);", "crimac_bad"),
+    ("typedef struct crimac_s { int a; short b; } crimac_s;", "crimac_s"),                 # struct field of an unknown type
+    ("typedef struct crimac_s { const float* p, q; } crimac_s;", "crimac_s"),              # (q would not be a pointer)
+    ("short crimac_bad(int a);", "crimac_bad"),                                            # unknown return type
+    ("#define CRIMAC_BAD (CRIMAC_LATER | 1)\n#define CRIMAC_LATER 2", "CRIMAC_BAD"),       # not an earlier define
+    ("#define CRIMAC_BAD sizeof(int)", "CRIMAC_BAD"),
+    ("#define CRIMAC_BAD (2**31)", "CRIMAC_BAD"),                                          # Python's power, not C
+])
+def test_header_parser_refuses_what_it_does_not_recognise(decl, named):
+    ok = 'extern "C" {\n%s\nint crimac_good(int a, void* stream);\n}\n'
+    assert "crimac_good" in hip.parse_header(ok % "")[0]
+    with pytest.raises(hip.HipLibraryError, match=named):
+        hip.parse_header(ok % decl)
+
+
+def test_header_parser_evaluates_defines_in_order_and_across_continued_lines():
+    text = ('#define CRIMAC_A 3 /* three */\n#define CRIMAC_B (CRIMAC_A << 4)\n'
+            '#define CRIMAC_C (1 | CRIMAC_B | \\\n                  (CRIMAC_A << 8))\n#define CRIMAC_D (-2147483647 - 1)\n'
+            'extern "C" {\n}\n')
+    assert hip.parse_header(text)[2] == {"CRIMAC_A": 3, "CRIMAC_B": 48, "CRIMAC_C": 1 | 48 | 768, "CRIMAC_D": -2 ** 31}
+    assert hip.DEFINES["CRIMAC_PLANES_H3P"] == 2 | 16 | 32 | 64 | 128 | (8 << 8)          # the header's own continued line
+    assert hip.ABI_VERSION == hip.DEFINES["CRIMAC_ABI_VERSION"] and hip.PR_BINS == hip.DEFINES["CRIMAC_PR_BINS"] == 16384
+    from crimac_classifiers_unet_amd import pipeline, tiled_inference
+    assert pipeline.SegPipe.PR_BINS == tiled_inference.PR_BINS == hip.PR_BINS
+
+
+def test_struct_mirrors_have_the_fields_of_the_header():
+    i, l, vp = ctypes.c_int, ctypes.c_long, ctypes.c_void_p
+    structs = hip.parse_header(_header_text())[1]
+    assert structs == {
+        "crimac_layer_desc": [("w", vp), ("grad", vp), ("dw", vp), ("fwd_hi", vp), ("fwd_lo", vp), ("dg_hi", vp),
+                              ("dg_lo", vp), ("kind", i), ("Co", i), ("Ci", i), ("Ci_pad", i), ("dw_splits", i),
+                              ("dw_stride", l)],
+        "crimac_wgrad_group_layer": [("f", vp), ("f_ld", l), ("CF", i), ("s", vp), ("s_ld", l), ("CS", i), ("Hf", i),
+                                     ("Wf", i), ("dw", vp), ("tiles_y", i), ("tiles_x", i), ("ntiles", l),
+                                     ("tiles_per_block", i), ("nsplits", i)],
+        "crimac_memm_desc": [("data", vp), ("labels", vp), ("seabed", vp), ("out", vp), ("n_pings", ctypes.c_longlong),
+                             ("n_range", ctypes.c_longlong)],
+    }
+    # several declarations on one line and comma lists keep their order
+    one_line = 'extern "C" {\ntypedef struct crimac_t { const void* f; long f_ld; int CF, CS; float x; } crimac_t;\n}\n'
+    assert hip.parse_header(one_line)[1] == {"crimac_t": [("f", vp), ("f_ld", l), ("CF", i), ("CS", i), ("x", ctypes.c_float)]}
+    for cls, tag in ((hip.LayerDesc, "crimac_layer_desc"), (hip.WgradGroupLayer, "crimac_wgrad_group_layer"),
+                     (hip.MemmDesc, "crimac_memm_desc")):
+        assert cls._fields_ == structs[tag]
+    lib = hip.load_library()
+    assert ctypes.sizeof(hip.LayerDesc) == 88 == lib.crimac_layer_desc_size()
+    assert ctypes.sizeof(hip.WgradGroupLayer) == 88 == lib.crimac_wgrad_group_layer_size()
+    assert ctypes.sizeof(hip.MemmDesc) == 48 == 8 * hip.MEMM_DESC_WORDS
+
+
+# hip name -> the #define it mirrors
+MIRRORED = {
+    "PREC_BF16": "CRIMAC_PREC_BF16", "PREC_F32X3": "CRIMAC_PREC_F32X3", "PREC_F32X6": "CRIMAC_PREC_F32X6",
+    "PREC_FP16": "CRIMAC_PREC_FP16", "PREC_F32H3": "CRIMAC_PREC_F32H3", "PREC_H3P": "CRIMAC_PREC_H3P",
+    "PREC_H3F_BWD": "CRIMAC_PREC_H3F_BWD",
+    "PLANES_FP16": "CRIMAC_PLANES_FP16", "PLANES_F32H3": "CRIMAC_PLANES_F32H3", "PLANES_FWD_FRAG": "CRIMAC_PLANES_FWD_FRAG",
+    "PLANES_INTERLEAVED": "CRIMAC_PLANES_INTERLEAVED", "PLANES_H3P": "CRIMAC_PLANES_H3P",
+    "EPI_RELU": "CRIMAC_EPI_RELU", "EPI_OUT_PLANES": "CRIMAC_EPI_OUT_PLANES", "EPI_CIN4": "CRIMAC_EPI_CIN4",
+    "EPI_WFRAG": "CRIMAC_EPI_WFRAG", "EPI_WROWS": "CRIMAC_EPI_WROWS",
+    "LAYER_FWD_FRAG": "CRIMAC_LAYER_FWD_FRAG", "LAYER_DG_FRAG": "CRIMAC_LAYER_DG_FRAG",
+    "NARROW_DGRAD": "CRIMAC_NARROW_DGRAD", "MASK_PER_PATCH": "CRIMAC_MASK_PER_PATCH",
+    "WGRAD_GROUP_MAX_LAYERS": "CRIMAC_WGRAD_GROUP_MAX_LAYERS", "ABI_VERSION": "CRIMAC_ABI_VERSION", "PR_BINS": "CRIMAC_PR_BINS",
+}
+# defines of the four mirrored families that hip.py deliberately has no name for
+UNMIRRORED = {
+    "CRIMAC_EPI_STAT_RAW",         # no Python caller passes it
+    "CRIMAC_PLANES_DG_SCALED",     # only ever part of CRIMAC_PLANES_H3P
+    "CRIMAC_PLANES_FWD_FP16",      # the two _FP16 bits: only ever part of PLANES_FP16 / PLANES_F32H3 / PLANES_H3P
+    "CRIMAC_PLANES_DG_FP16",
+    "CRIMAC_PREC_MAX",             # the library's own range check
+}
+
+
+def test_every_mirrored_constant_equals_its_define():
+    defines = hip.parse_header(_header_text())[2]
+    assert len(defines) >= 34
+    for name, define in MIRRORED.items():
+        assert getattr(hip, name) == defines[define], name
+    families = {d for d in defines if re.match(r"CRIMAC_(PREC|PLANES|EPI|LAYER)_", d)}
+    assert families - set(MIRRORED.values()) == UNMIRRORED and not UNMIRRORED & set(MIRRORED.values())
+    # kind bits 0-1 of crimac_layer_desc have no names in the header, only its comment
+    assert (hip.LAYER_CONV3X3, hip.LAYER_UPCONV2X2, hip.LAYER_CONV1X1) == (0, 1, 2)
+
+
+def test_call_refuses_a_name_that_takes_no_stream(monkeypatch):
+    def unreachable():
+        raise AssertionError("hip.call reached the library")
+    monkeypatch.setattr(hip, "load_library", unreachable)
+    monkeypatch.setattr(hip, "_stream", unreachable)
+    with pytest.raises(hip.HipLibraryError, match="crimac_wgrad_splits"):
+        hip.call("crimac_wgrad_splits", 0, 0, 64, 64, 32, 256, 256, 0)
+    with pytest.raises(hip.HipLibraryError, match="crimac_nonexistent"):
+        hip.call("crimac_nonexistent")
+    # ... and what `call` launches is the function load_library bound, for exactly the entry points that take a stream
+    monkeypatch.undo()
+    lib = hip.load_library()
+    assert set(hip._entry) == set(hip.SIGNATURES) and all(hip._entry[n] is getattr(lib, n) for n in hip.SIGNATURES)
+
+
 def test_grouped_weight_gradient_plan_covers_every_item_exactly_once():
     """crimac_wgrad_group_plan (host only): for the encoder shapes of the benchmark and for ragged tiny shapes, every
     (layer, channel-tile pair, pixel split) appears in exactly one of the 8 queues; whole rounds of 8 splits put split s
