@@ -208,6 +208,22 @@ __global__ __launch_bounds__(256) void gather_patches_multi_kernel(const crimac_
                        nullptr);
 }
 
+// crimac_gather_patches_memm_labels' kernel in its flags == 0 form (border rule by the TRANSFORMED labels of the patches,
+// no metadata planes, db_with_limits) with the source taken from descs[src[p]]; patch_labels belong to the batch, not to
+// a source.  (tiled_inference.evaluate_echograms_memm, eval_mode 'region' / 'trace')
+template <typename T>
+__global__ __launch_bounds__(256) void gather_patches_labels_multi_kernel(const crimac_memm_desc* __restrict__ descs,
+                                                                          int n_desc, const int* __restrict__ src, int C,
+                                                                          const int* __restrict__ centres, int ph, int pw,
+                                                                          T* __restrict__ out, int ld,
+                                                                          const short* __restrict__ patch_labels) {
+  const int s = src[blockIdx.z];
+  if (s < 0 || s >= n_desc) return;
+  const crimac_memm_desc d = descs[s];
+  gather_patch_tile<T, true>(d.data, C, (int)d.n_pings, (int)d.n_range, centres, ph, pw, out, ld, nullptr, 0,
+                             MetaPlaneSrc{}, nullptr, patch_labels);
+}
+
 // scatter_patches_kernel with the memm rules only (labels, seabed vector from ping 0, seabed_rule 1, no data0), the
 // destination [2][n_range][n_pings], the labels, the seabed vector and the two extents taken from descs[src[p]].
 // blockIdx.y = patch.  Interiors of different patches are disjoint, within an echogram and across echograms: plain stores.
@@ -287,11 +303,12 @@ __global__ __launch_bounds__(256) void pr_histogram_kernel(const float* __restri
 // 0, and a water column not deeper than the patch puts the centre row at H / 2.
 // A pure streaming transpose: one 32 x 32 tile per block and plane, lanes along range (contiguous in the chunk) when
 // reading, along ping (contiguous in the crop) when writing; `vec`: 16-byte stores (pw % 8 == 0, 16-byte aligned bases).
-__global__ __launch_bounds__(256) void gather_eval_crops_kernel(const float* __restrict__ data, int C, int Wd, int H,
-                                                                const short* __restrict__ labels,
-                                                                const int* __restrict__ centres, int ph, int pw,
-                                                                int flavour, int vec, float* __restrict__ data_out,
-                                                                short* __restrict__ labels_out) {
+// The body of one block = one 32 x 32 tile of patch blockIdx.z, shared by the single-source kernel and by the kernel that
+// takes the source of every patch from a descriptor (gather_eval_crops_multi_kernel): one text, the same bits.
+__device__ __forceinline__ void eval_crops_tile(const float* __restrict__ data, int C, int Wd, int H,
+                                                const short* __restrict__ labels, const int* __restrict__ centres,
+                                                int ph, int pw, int flavour, int vec, float* __restrict__ data_out,
+                                                short* __restrict__ labels_out) {
   __shared__ float tile[TS][TS + 1];          // [x (ping)][y (range)]
   __shared__ short ltile[TS][TS + 2];
   const int p = blockIdx.z;
@@ -358,6 +375,28 @@ __global__ __launch_bounds__(256) void gather_eval_crops_kernel(const float* __r
     }
     __syncthreads();
   }
+}
+
+__global__ __launch_bounds__(256) void gather_eval_crops_kernel(const float* __restrict__ data, int C, int Wd, int H,
+                                                                const short* __restrict__ labels,
+                                                                const int* __restrict__ centres, int ph, int pw,
+                                                                int flavour, int vec, float* __restrict__ data_out,
+                                                                short* __restrict__ labels_out) {
+  eval_crops_tile(data, C, Wd, H, labels, centres, ph, pw, flavour, vec, data_out, labels_out);
+}
+
+// flavour 1 (get_crop_memmap) with data, labels and both extents taken from descs[src[p]] -- the centre-row rule of a water
+// column not deeper than the patch is then the patch's own echogram's.  A descriptor without data or labels is skipped.
+__global__ __launch_bounds__(256) void gather_eval_crops_multi_kernel(const crimac_memm_desc* __restrict__ descs,
+                                                                      int n_desc, const int* __restrict__ src, int C,
+                                                                      const int* __restrict__ centres, int ph, int pw,
+                                                                      int vec, float* __restrict__ data_out,
+                                                                      short* __restrict__ labels_out) {
+  const int s = src[blockIdx.z];
+  if (s < 0 || s >= n_desc) return;                        // (uniform over the block: nobody waits at a barrier)
+  const crimac_memm_desc d = descs[s];
+  if (!d.data || !d.labels) return;
+  eval_crops_tile(d.data, C, (int)d.n_pings, (int)d.n_range, d.labels, centres, ph, pw, 1, vec, data_out, labels_out);
 }
 
 }  // namespace
@@ -527,6 +566,39 @@ extern "C" int crimac_scatter_patches_multi(const float* probs, int ncls, const 
   if (bx > 64) bx = 64;
   ScatterMultiParams q{probs, ncls, descs, n_desc, src, centres, ph, pw, overlap, seabed_pad, out_f16};
   hipLaunchKernelGGL(scatter_patches_multi_kernel, dim3((unsigned)bx, (unsigned)P), dim3(256), 0, (hipStream_t)stream, q);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}
+
+extern "C" int crimac_gather_eval_crops_multi(const crimac_memm_desc* descs, int n_desc, const int* src, int C,
+                                              const int* centres, int P, int ph, int pw, float* data_out,
+                                              short* labels_out, void* stream) {
+  CRIMAC_REQUIRE(descs && src && centres && data_out && labels_out && n_desc > 0 && C > 0 && P > 0 && ph > 0 && pw > 0,
+                 "gather_eval_crops_multi: bad arguments");
+  CRIMAC_REQUIRE(P <= 65535, "gather_eval_crops_multi: at most 65535 patches per call");
+  const int vec = pw % 8 == 0 && ((uintptr_t)data_out & 15) == 0 && ((uintptr_t)labels_out & 15) == 0;
+  dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
+  hipLaunchKernelGGL(gather_eval_crops_multi_kernel, grid, dim3(256), 0, (hipStream_t)stream, descs, n_desc, src, C,
+                     centres, ph, pw, vec, data_out, labels_out);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}
+
+extern "C" int crimac_gather_patches_memm_labels_multi(int prec, const crimac_memm_desc* descs, int n_desc, const int* src,
+                                                       int C, const int* centres, int P, int ph, int pw, void* out, long ld,
+                                                       const short* patch_labels, void* stream) {
+  CRIMAC_REQUIRE(prec >= CRIMAC_PREC_BF16 && prec <= CRIMAC_PREC_MAX, "gather_patches_memm_labels_multi: bad precision %d",
+                 prec);
+  CRIMAC_REQUIRE(descs && src && centres && out && n_desc > 0 && C > 0 && C <= 16 && P > 0 && ph > 0 && pw > 0,
+                 "gather_patches_memm_labels_multi: bad arguments (C=%d must be <= 16)", C);
+  CRIMAC_REQUIRE(patch_labels, "gather_patches_memm_labels_multi: needs the transformed labels of the patches (border rule)");
+  CRIMAC_REQUIRE(ld >= C && ld % 8 == 0 && ld <= 16, "gather_patches_memm_labels_multi: ld=%ld must be 8 or 16 and >= C", ld);
+  CRIMAC_REQUIRE(P <= 65535, "gather_patches_memm_labels_multi: at most 65535 patches per call");
+  dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
+  const size_t lds = (size_t)C * TS * (TS + 1) * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(gather_patches_labels_multi_kernel<T>, grid, dim3(256), lds, st,
+                                                 descs, n_desc, src, C, centres, ph, pw, (T*)out, (int)ld, patch_labels));
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
 }

@@ -12,7 +12,7 @@ Dataset class and the transform factories are INJECTED (``dataset_cls`` / ``data
 ``evaluate.py`` ``__main__``, :120-167) takes the location of the host data stack as an explicit ``--data-stack`` path.
 
 ``tiled=True`` (``--tiled``) runs the same evaluation without that host chain: ``tiled_inference.evaluate_survey`` /
-``evaluate_echogram_memm`` keep the survey chunk, the crops, the label and data transforms and the PR histograms on the
+``evaluate_echograms_memm`` keep the survey chunk, the crops, the label and data transforms and the PR histograms on the
 GPU and need the readers only -- no Dataset class, no transform factory, no DataLoader workers.
 """
 from __future__ import annotations
@@ -96,21 +96,15 @@ def validate_model_survey_memm(readers, segpipe, meta_channels, patch_size, patc
                                data_transform_factory=None, label_transform_factory=None, worker_init_fn=None,
                                tiled=False, **kwargs):
     """evaluate.py:84-117: one gridded Dataset per echogram, concatenated -> PR curve / F1 of the survey.
-    ``tiled=True``: every echogram on the tiled GPU path (``tiled_inference.evaluate_echogram_memm``; with several ranks
-    the echograms are dealt to the ranks and the histograms all-reduced once); no factory is needed."""
+    ``tiled=True``: the whole survey on the tiled GPU path (``tiled_inference.evaluate_echograms_memm``: forward batches
+    packed across the echograms, one feed; with several ranks the groups of echograms are dealt to the ranks and the
+    histograms all-reduced once; a model with metadata planes goes echogram by echogram); no factory is needed."""
     if tiled:
-        import torch
-
-        from . import parallel
-        from .tiled_inference import PR_BINS, evaluate_echogram_memm, finish_histograms
+        from .tiled_inference import evaluate_echograms_memm
         if not segpipe.model_is_loaded:
             segpipe.load_model_params()
-        hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=segpipe.device)
-        rank, world = parallel.rank_world()
-        for i in parallel.shard_indices(len(readers), rank, world):
-            evaluate_echogram_memm(readers[i], segpipe, patch_size, patch_overlap, batch_size, eval_mode=eval_mode,
-                                   meta_channels=meta_channels or None, hist=hist)
-        hp, hn = finish_histograms(hist)
+        hp, hn = evaluate_echograms_memm(readers, segpipe, patch_size, patch_overlap, batch_size, eval_mode=eval_mode,
+                                         meta_channels=meta_channels or None)
         return _tiled_metrics(segpipe, hp, hn, save_path_metrics, save_path_plot, survey)
     dataset_cls, dtf, ltf = _reference_factories(dataset_cls, data_transform_factory, label_transform_factory, True)
     frequencies = segpipe.frequencies

@@ -23,11 +23,14 @@ With ``torch.distributed`` initialised, patches of a chunk are dealt round-robin
 exact).  Writing zarr / npy is the caller's business: ``predict_survey`` yields numpy chunks
 that a caller appends with the reference's ``create_xarray_ds_predictions`` / ``append_to_zarr``;
 ``predict_echogram_memm`` returns the array ``save_reader_predictions_memm`` would ``np.save``;
-``predict_echograms_memm`` does so for a whole memm survey, its forward batches packed across the echograms.
+``predict_echograms_memm`` does so for a whole memm survey, its forward batches packed across the echograms, and
+``evaluate_echograms_memm`` evaluates one (PR histograms) in the same way.
 """
 from __future__ import annotations
 
 import difflib
+import functools
+import inspect
 import itertools
 import os
 import time
@@ -525,8 +528,8 @@ def release_staging():
 
 
 class _ChunkFeed:
-    """The chunk pipeline of ``predict_survey``, ``evaluate_survey`` and ``predict_echograms_memm`` (whose chunk is a group
-    of echograms): reader threads fill pinned host slots ahead of the GPU, a copy stream uploads each chunk into one of
+    """The chunk pipeline of ``predict_survey``, ``evaluate_survey``, ``predict_echograms_memm`` and
+    ``evaluate_echograms_memm`` (whose chunk is a group of echograms): reader threads fill pinned host slots ahead of the GPU, a copy stream uploads each chunk into one of
     two device slots while the chunk before it computes.  ``jobs`` is any iterable, taken from lazily.
 
     ``table`` {name: (elements, dtype)}: the flat buffers a chunk is staged in, one of each per host slot and per device
@@ -1056,7 +1059,7 @@ def _seabed_stream(device):
 
 
 def iter_memm_groups(echograms, patch_size, patch_overlap, group_patches, seabed=None, max_elems=MEMM_GROUP_ELEMS,
-                     rank=0, world=1, device=None, skip=None):
+                     rank=0, world=1, device=None, skip=None, record=_MemmRecord):
     """The host-side plan of ``predict_echograms_memm``: consumes ``echograms`` lazily and yields this rank's groups, each
     a list of records (``.echogram``, ``.seabed`` int32 [n_pings], ``.grid`` = ``plan_eval_grid(..., memm=True)`` with the
     echogram's own seabed).  Every rank walks every echogram's seabed line (the grouping depends on the patch counts) and
@@ -1064,13 +1067,94 @@ def iter_memm_groups(echograms, patch_size, patch_overlap, group_patches, seabed
     ``skip(echogram) -> bool`` (the resume rule of ``save_predictions_memm``) is asked AFTER the deal, about the echograms of
     this rank's own groups only: the groups and their owners are planned over the whole input, which is the same on every
     rank, so what one rank skips -- files another rank is writing meanwhile -- cannot move an echogram to another rank or
-    to none.  A group of which nothing is left is dropped."""
-    records = (_MemmRecord(eg, _memm_survey_seabed(eg, seabed, device), patch_size, patch_overlap) for eg in echograms)
+    to none.  A group of which nothing is left is dropped.
+    ``record``: the record class (``evaluate_echograms_memm`` plans with ``_MemmEvalRecord``, which carries the boxes)."""
+    records = (record(eg, _memm_survey_seabed(eg, seabed, device), patch_size, patch_overlap) for eg in echograms)
     mine = shard_memm_groups(plan_memm_groups(records, group_patches, max_elems, key=_MemmRecord.key), rank, world)
     if skip is None:
         return mine
     kept = ([r for r in g if not skip(r.echogram)] for g in mine)
     return (g for g in kept if g)
+
+
+def _refuse_near_misses(name, kwargs, own):
+    """``kwargs`` takes the other keys of the reference's ``config_args``; a keyword that is a near miss of one of the
+    function's ``own`` (``difflib.get_close_matches``) is a misspelling: TypeError."""
+    typos = {k: difflib.get_close_matches(k, own, n=1, cutoff=0.8) for k in kwargs}
+    typos = {k: m[0] for k, m in typos.items() if m}
+    if typos:
+        raise TypeError(f"{name}: unknown keyword(s) " +
+                        ", ".join(f"{k!r} (did you mean {m!r}?)" for k, m in sorted(typos.items())))
+
+
+def _check_survey_seabed(name, seabed, single):
+    if not (seabed is None or callable(seabed) or (isinstance(seabed, str) and seabed == "estimate")):
+        raise TypeError(f"{name}: seabed is None, 'estimate' or a callable(echogram) -> integer array "
+                        f"[n_pings], got {type(seabed).__name__}; an array belongs to a single echogram "
+                        f"({single} takes one)")
+
+
+class _MemmGroupStage:
+    """What ``predict_echograms_memm`` and ``evaluate_echograms_memm`` share of moving a group of echograms through a
+    ``_ChunkFeed``: the ``table`` of flat staging buffers (``cap`` pixels of ``C`` planes and of labels, ``n_misc`` int32
+    words), the transposed planes per device slot (``extra``), the reader thread's copy of a group into a pinned slot
+    (``read``) and the transposes on the copy stream (``transpose``).  ``misc`` holds, in this order: the descriptor table
+    int64 [n][MEMM_DESC_WORDS] | the centres int32 [P][2] | src int32 [P] | the seabed lines | the caller's tail."""
+
+    def __init__(self, dev, C, cap, frequencies):
+        self.dev, self.C, self.cap, self.frequencies = dev, C, cap, frequencies
+        self.n_misc = cap // MEMM_MISC_SHARE + 2 * hip.MEMM_DESC_WORDS
+        self.table = {"data": (C * cap, torch.float32), "lab": (cap, torch.int16), "misc": (self.n_misc, torch.int32)}
+
+    def extra(self):
+        return {"data_t": [torch.empty(self.C * self.cap, dtype=torch.float32, device=self.dev) for _ in range(2)],
+                "lab_t": [torch.empty(self.cap, dtype=torch.int16, device=self.dev) for _ in range(2)]}
+
+    def read(self, bufs, host, k, group, out=None, tail=None):
+        """Group ``k`` (device slot k & 1) into the pinned slot ``host``; the descriptors point at the transposed planes,
+        at the seabed lines inside the uploaded ``misc`` and -- ``out``: the flat float16 prediction buffer -- at the
+        echogram's [2, range, pings] share of it.  ``tail(misc, at) -> end``: writes the caller's words behind the seabed
+        lines.  Returns (uploads, the pixel offset of every echogram, the group's pixels, where the tail starts)."""
+        C, W = self.C, hip.MEMM_DESC_WORDS
+        n, P = len(group), sum(len(r.grid) for r in group)
+        misc = host["misc"].numpy()
+        desc = misc[:2 * W * n].view(np.int64).reshape(n, W)
+        o_cen, o_src, o_sb = 2 * W * n, 2 * W * n + 2 * P, 2 * W * n + 3 * P
+        offs, off, p0 = [], 0, 0
+        for i, r in enumerate(group):
+            R, Wp, npx, Pe = r.n_range, r.n_pings, r.pixels, len(r.grid)
+            assert o_sb + Wp <= self.n_misc and off + npx <= self.cap, "memm group staging too small"
+            d = host["data"][C * off:C * (off + npx)].view(C, R, Wp).numpy()
+            for c, m in enumerate(r.echogram.data_memmaps(self.frequencies)):
+                np.copyto(d[c], m, casting="unsafe")
+            np.copyto(host["lab"][off:off + npx].view(R, Wp).numpy(), r.echogram.label_memmap(), casting="unsafe")
+            misc[o_sb:o_sb + Wp] = r.seabed
+            misc[o_cen + 2 * p0:o_cen + 2 * (p0 + Pe)] = np.asarray(r.grid, dtype=np.int32).reshape(-1)
+            misc[o_src + p0:o_src + p0 + Pe] = i
+            desc[i] = (bufs["data_t"][k & 1].data_ptr() + 4 * C * off, bufs["lab_t"][k & 1].data_ptr() + 2 * off,
+                       bufs["dev"][k & 1]["misc"].data_ptr() + 4 * o_sb,
+                       0 if out is None else out.data_ptr() + 2 * 2 * off, Wp, R)
+            offs.append(off)
+            off, p0, o_sb = off + npx, p0 + Pe, o_sb + Wp
+        o_tail = o_sb
+        if tail is not None:
+            o_sb = tail(misc, o_sb)
+            assert o_tail <= o_sb <= self.n_misc, "memm group staging too small"
+        return ({"data": host["data"][:C * off], "lab": host["lab"][:off], "misc": host["misc"][:o_sb]},
+                offs, off, o_tail)
+
+    def transpose(self, feed, k, d, group, offs):
+        """The uploaded planes of group ``k`` to the ping-major layout of the gather kernels, on the copy stream; the
+        main stream waits for it."""
+        C = self.C
+        data_t, lab_t = feed.bufs["data_t"][k & 1], feed.bufs["lab_t"][k & 1]
+        with torch.cuda.stream(feed.copy_stream):
+            for r, off in zip(group, offs):
+                R, Wp, npx = r.n_range, r.n_pings, r.pixels
+                data_t[C * off:C * (off + npx)].view(C, Wp, R).copy_(
+                    d["data"][C * off:C * (off + npx)].view(C, R, Wp).permute(0, 2, 1))
+                lab_t[off:off + npx].view(Wp, R).copy_(d["lab"][off:off + npx].view(R, Wp).t())
+        feed.main.wait_stream(feed.copy_stream)
 
 
 def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn=None, meta_channels=None,
@@ -1106,16 +1190,9 @@ def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_
     ``kwargs``: the other keys of the reference's ``config_args`` are accepted and ignored, as by the sibling calls; a
     keyword that is a near miss of one of this function's own (``difflib.get_close_matches``: ``group_patch``,
     ``group_elem``, ``seabeds``, ``stat`` ...) is refused, it is a misspelling."""
-    own = ("group_patches", "group_elems", "seabed", "skip", "stats", "predict_fn", "meta_channels")
-    typos = {k: difflib.get_close_matches(k, own, n=1, cutoff=0.8) for k in kwargs}
-    typos = {k: m[0] for k, m in typos.items() if m}
-    if typos:
-        raise TypeError("predict_echograms_memm: unknown keyword(s) " +
-                        ", ".join(f"{k!r} (did you mean {m!r}?)" for k, m in sorted(typos.items())))
-    if not (seabed is None or callable(seabed) or (isinstance(seabed, str) and seabed == "estimate")):
-        raise TypeError("predict_echograms_memm: seabed is None, 'estimate' or a callable(echogram) -> integer array "
-                        f"[n_pings], got {type(seabed).__name__}; an array belongs to a single echogram "
-                        "(predict_echogram_memm takes one)")
+    _refuse_near_misses("predict_echograms_memm", kwargs,
+                        ("group_patches", "group_elems", "seabed", "skip", "stats", "predict_fn", "meta_channels"))
+    _check_survey_seabed("predict_echograms_memm", seabed, "predict_echogram_memm")
     dev = segpipe.device
     model = segpipe.model.to(dev).eval()
     eng = model.infer_engine
@@ -1145,43 +1222,20 @@ def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_
         return
     groups = itertools.chain([first], groups)
     W = hip.MEMM_DESC_WORDS
-    n_misc = cap // MEMM_MISC_SHARE + 2 * W
-    table = {"data": (C * cap, torch.float32), "lab": (cap, torch.int16), "misc": (n_misc, torch.int32)}
+    stage = _MemmGroupStage(dev, C, cap, segpipe.frequencies)
 
     def extra():            # transposed planes per device slot, the group's predictions, the result ring
-        return {"data_t": [torch.empty(C * cap, dtype=torch.float32, device=dev) for _ in range(2)],
-                "lab_t": [torch.empty(cap, dtype=torch.int16, device=dev) for _ in range(2)],
-                "out": torch.empty(2 * cap, dtype=torch.float16, device=dev),
-                "pinned": [torch.empty(2 * cap, dtype=torch.float16).pin_memory() for _ in range(2)]}
+        return dict(stage.extra(), out=torch.empty(2 * cap, dtype=torch.float16, device=dev),
+                    pinned=[torch.empty(2 * cap, dtype=torch.float16).pin_memory() for _ in range(2)])
 
     def read(job, slot):
         k, group = job
         if group[0].elems > cap:                     # too large for the staging: predict_echogram_memm, nothing staged
             return {}, (group, None, 0)
-        host, bufs = slot(), feed.bufs
-        n, P = len(group), sum(len(r.grid) for r in group)
-        misc = host["misc"].numpy()
-        desc = misc[:2 * W * n].view(np.int64).reshape(n, W)
-        o_cen, o_src, o_sb = 2 * W * n, 2 * W * n + 2 * P, 2 * W * n + 3 * P
-        offs, off, p0 = [], 0, 0
-        for i, r in enumerate(group):
-            R, Wp, npx, Pe = r.n_range, r.n_pings, r.pixels, len(r.grid)
-            assert o_sb + Wp <= n_misc and off + npx <= cap, "memm group staging too small"
-            d = host["data"][C * off:C * (off + npx)].view(C, R, Wp).numpy()
-            for c, m in enumerate(r.echogram.data_memmaps(segpipe.frequencies)):
-                np.copyto(d[c], m, casting="unsafe")
-            np.copyto(host["lab"][off:off + npx].view(R, Wp).numpy(), r.echogram.label_memmap(), casting="unsafe")
-            misc[o_sb:o_sb + Wp] = r.seabed
-            misc[o_cen + 2 * p0:o_cen + 2 * (p0 + Pe)] = np.asarray(r.grid, dtype=np.int32).reshape(-1)
-            misc[o_src + p0:o_src + p0 + Pe] = i
-            desc[i] = (bufs["data_t"][k & 1].data_ptr() + 4 * C * off, bufs["lab_t"][k & 1].data_ptr() + 2 * off,
-                       bufs["dev"][k & 1]["misc"].data_ptr() + 4 * o_sb, bufs["out"].data_ptr() + 2 * 2 * off, Wp, R)
-            offs.append(off)
-            off, p0, o_sb = off + npx, p0 + Pe, o_sb + Wp
-        return ({"data": host["data"][:C * off], "lab": host["lab"][:off], "misc": host["misc"][:o_sb]},
-                (group, offs, off))
+        uploads, offs, total, _ = stage.read(feed.bufs, slot(), k, group, out=feed.bufs["out"])
+        return uploads, (group, offs, total)
 
-    with _ChunkFeed(dev, ("memm", C), table, 3, enumerate(groups), read, extra=extra) as feed:
+    with _ChunkFeed(dev, ("memm", C), stage.table, 3, enumerate(groups), read, extra=extra) as feed:
         bufs = feed.bufs
         pinned, out = bufs["pinned"], bufs["out"]
         events = [torch.cuda.Event() for _ in range(2)]
@@ -1207,14 +1261,7 @@ def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_
                                                         predict_fn=predict_fn, seabed=r.seabed)
                 continue
             n, P = len(group), sum(len(r.grid) for r in group)
-            data_t, lab_t = bufs["data_t"][k & 1], bufs["lab_t"][k & 1]
-            with torch.cuda.stream(feed.copy_stream):        # to the ping-major layout of the gather kernel
-                for r, off in zip(group, offs):
-                    R, Wp, npx = r.n_range, r.n_pings, r.pixels
-                    data_t[C * off:C * (off + npx)].view(C, Wp, R).copy_(
-                        d["data"][C * off:C * (off + npx)].view(C, R, Wp).permute(0, 2, 1))
-                    lab_t[off:off + npx].view(Wp, R).copy_(d["lab"][off:off + npx].view(R, Wp).t())
-            feed.main.wait_stream(feed.copy_stream)
+            stage.transpose(feed, k, d, group, offs)         # to the ping-major layout of the gather kernel
             misc = d["misc"]
             cen, src = misc[2 * W * n:], misc[2 * W * n + 2 * P:]
             out[:2 * total].zero_()
@@ -1398,3 +1445,185 @@ def evaluate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_s
         hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=dev)
     cp.evaluate(grid, hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch)
     return finish_histograms(hist, all_reduce=False) if own else hist
+
+
+# ---- a memm survey: many small echograms in one evaluation feed ------------------------------------------------------------
+def memm_box_table(boxes):
+    """The box table of a group as ``crimac_labels_extend_mask_multi`` takes it: ``boxes`` -- per echogram an int [n, 4]
+    array of ALREADY extended boxes (``eval_boxes``) or None -> (box_off int32 [echograms + 1], boxes int32 [total, 4]), the
+    tables one after the other.  Patches of echogram i are tested against rows [box_off[i], box_off[i + 1])."""
+    rows = [np.zeros((0, 4), np.int32) if b is None else np.asarray(b, dtype=np.int32).reshape(-1, 4) for b in boxes]
+    off = np.zeros(len(rows) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(b) for b in rows])
+    return off, np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 4), np.int32))
+
+
+class _MemmEvalRecord(_MemmRecord):
+    """``_MemmRecord`` + the echogram's extended school boxes (None for eval_mode 'all'); the int32 words of the boxes and
+    of the echogram's entry in the offset table count towards what the echogram takes of a group's staging."""
+
+    def __init__(self, echogram, seabed, patch_size, patch_overlap, eval_mode="all", extend_size=20):
+        super().__init__(echogram, seabed, patch_size, patch_overlap)
+        self.boxes = eval_boxes(echogram, eval_mode, extend_size)
+        words = 2 * hip.MEMM_DESC_WORDS + 3 * len(self.grid) + self.n_pings + 2 + \
+            (0 if self.boxes is None else 4 * len(self.boxes))
+        self.elems = max(self.elems, MEMM_MISC_SHARE * words)
+
+
+def _takes_keyword(fn, name):
+    """Whether ``fn`` declares the keyword ``name`` (or ``**kwargs``)."""
+    try:
+        params = inspect.signature(fn).parameters.values()
+    except (TypeError, ValueError):
+        return False
+    return any(p.kind is p.VAR_KEYWORD or (p.name == name and p.kind in (p.KEYWORD_ONLY, p.POSITIONAL_OR_KEYWORD))
+               for p in params)
+
+
+def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, eval_mode="all", extend_size=20,
+                            predict_fn=None, meta_channels=None, seabed=None, hist=None, on_batch=None, group_patches=None,
+                            group_elems=None, stats=None, **kwargs):
+    """Test-set evaluation of a whole memm survey (``validate_model_survey_memm``, evaluate.py:84-117) on the tiled path:
+    ``(hist_pos, hist_neg)`` int64 numpy [16384], the sum of ``evaluate_echogram_memm`` over ``echograms``.
+
+    The plan is ``predict_echograms_memm``'s: consecutive echograms form groups (``iter_memm_groups`` with every
+    echogram's own ``plan_eval_grid(..., memm=True)``; ``group_patches``, ``group_elems`` as there -- the int32 words of an
+    echogram's boxes count towards its share of the staging), all patches of a group form one patch list cut into forward
+    batches of ``max(batch_size, INTERNAL_BATCH)`` (``batch_size`` with a ``predict_fn``): only the last batch of a group
+    is short.  Reader threads copy the next groups' memmaps into pinned staging (``_ChunkFeed``), the copy stream uploads
+    and transposes them while the current group computes; nothing but the two histograms comes back.  Per batch:
+    ``crimac_gather_eval_crops_multi`` -> ``crimac_labels_test_transform_multi`` (-> ``crimac_labels_extend_mask_multi``
+    with the group's box table, ``eval_boxes`` per echogram, for ``eval_mode`` 'region' / 'trace') -> network input
+    (``crimac_gather_patches_memm_multi`` for 'all', ``crimac_gather_patches_memm_labels_multi`` for 'region' / 'trace',
+    as ``ChunkPredictor.evaluate`` chooses) -> ``eval_logits`` -> ``crimac_pr_histogram``; every kernel takes each
+    patch's source from the group's descriptor table.
+
+    ``seabed``: None, ``"estimate"`` or a callable ``echogram -> integer array [n_pings]``, as ``predict_echograms_memm``.
+    ``hist`` (int32 [2, 16384] on the GPU): accumulate into it and return it, no collective (as
+    ``evaluate_echogram_memm``); None: ``finish_histograms`` -- with torch.distributed initialised the *groups* are dealt
+    round-robin to the ranks, the histograms all-reduced once, and every rank returns the survey's.
+    **Models with metadata planes** (``UNet_LateMetInject``, or metadata input channels) take the per-echogram path --
+    ``evaluate_echogram_memm`` for one echogram after the other (dealt to the ranks one by one), none of the packing; an
+    echogram larger than ``group_elems`` takes it too, in its place in the order.
+    ``on_batch(centres [P, 2] numpy, labels int16 [P, H, W], logits [P, 3, H, W])`` sees every batch; a callback that
+    declares the keyword ``echograms`` also gets the echogram of every patch of the batch (a list of P).
+    ``stats`` (a dict): receives ``groups``, ``batches`` (the patches of every packed forward batch),
+    ``fallback_echograms`` (per-echogram path: metadata model) and ``solo_echograms`` (too large for the staging).
+    ``kwargs``: the other keys of the reference's ``config_args`` are accepted and ignored; a near miss of one of this
+    function's own keywords is refused as a misspelling."""
+    _refuse_near_misses("evaluate_echograms_memm", kwargs,
+                        ("group_patches", "group_elems", "seabed", "stats", "predict_fn", "meta_channels", "eval_mode",
+                         "extend_size", "hist", "on_batch"))
+    _check_survey_seabed("evaluate_echograms_memm", seabed, "evaluate_echogram_memm")
+    if eval_mode not in ("all", "region", "trace"):
+        raise ValueError(f"eval_mode={eval_mode!r}: 'all', 'region' or 'trace' (batch/transforms.py:87)")
+    dev = segpipe.device
+    model = segpipe.model.to(dev).eval()
+    eng = model.infer_engine
+    C = len(segpipe.frequencies)
+    pw, ph = (int(v) for v in patch_size)
+    overlap = int(patch_overlap)
+    step = max(int(batch_size), INTERNAL_BATCH) if predict_fn is None else int(batch_size)
+    group_patches = MEMM_GROUP_BATCHES * step if group_patches is None else int(group_patches)
+    cap = MEMM_GROUP_ELEMS if group_elems is None else int(group_elems)
+    rank, world = parallel.rank_world()
+    stats = {} if stats is None else stats
+    stats.update(groups=0, batches=[], fallback_echograms=0, solo_echograms=0)
+    own = hist is None
+    if own:
+        hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=dev)
+    tell = on_batch is not None and _takes_keyword(on_batch, "echograms")
+
+    def emit(cen, labels_t, logits, egs):
+        if tell:
+            on_batch(cen, labels_t, logits, echograms=egs())
+        elif on_batch is not None:
+            on_batch(cen, labels_t, logits)
+
+    def single(eg, sb, meta):            # the per-echogram path
+        hook = None if on_batch is None else lambda cen, lab, logits: emit(cen, lab, logits, lambda: [eg] * len(cen))
+        evaluate_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, eval_mode=eval_mode,
+                               extend_size=extend_size, predict_fn=predict_fn, meta_channels=meta, hist=hist, on_batch=hook,
+                               seabed=sb)
+
+    def done():
+        return finish_histograms(hist) if own else hist
+
+    if eng.lmi or eng.in_channels > C:        # metadata planes: one echogram per group, the per-echogram path
+        for eg in shard_memm_groups(echograms, rank, world):
+            sb = None if seabed is None or isinstance(seabed, str) else _memm_survey_seabed(eg, seabed, dev)
+            stats["fallback_echograms"] += 1
+            single(eg, seabed if sb is None else sb, meta_channels)
+        return done()
+
+    record = functools.partial(_MemmEvalRecord, eval_mode=eval_mode, extend_size=extend_size)
+    groups = iter_memm_groups(echograms, patch_size, patch_overlap, group_patches, seabed, cap, rank, world, dev,
+                              record=record)
+    first = next(groups, None)
+    if first is None:                                # nothing to do on this rank: no staging
+        return done()
+    groups = itertools.chain([first], groups)
+    W = hip.MEMM_DESC_WORDS
+    stage = _MemmGroupStage(dev, C, cap, segpipe.frequencies)
+    masked = eval_mode != "all"
+
+    def read(job, slot):
+        k, group = job
+        if group[0].elems > cap:                     # too large for the staging: evaluate_echogram_memm, nothing staged
+            return {}, (group, None, 0)
+
+        def tail(misc, at):                          # box_off [n + 1] | boxes [total][4]
+            off, rows = memm_box_table([r.boxes for r in group])
+            end = at + len(off) + rows.size
+            assert end <= stage.n_misc, "memm group staging too small (boxes)"
+            misc[at:at + len(off)] = off
+            misc[at + len(off):end] = rows.reshape(-1)
+            return end
+        uploads, offs, _, o_tail = stage.read(feed.bufs, slot(), k, group, tail=tail if masked else None)
+        return uploads, (group, offs, o_tail)
+
+    with _ChunkFeed(dev, ("memm-eval", C), stage.table, 3, enumerate(groups), read, extra=stage.extra) as feed:
+        eng.bind()
+        for k, (d, (group, offs, o_tail)) in enumerate(feed):
+            stats["groups"] += 1
+            if offs is None:                         # the per-echogram path, in its place in the order
+                feed.computed()
+                stats["solo_echograms"] += 1
+                single(group[0].echogram, group[0].seabed, None)
+                continue
+            n, P = len(group), sum(len(r.grid) for r in group)
+            stage.transpose(feed, k, d, group, offs)         # to the ping-major layout of the gather kernels
+            misc = d["misc"]
+            cen, src = misc[2 * W * n:], misc[2 * W * n + 2 * P:]
+            cen64 = cen[:2 * P].view(P, 2).long()            # the label kernels take `center_coordinates` as int64
+            box_off, boxes = misc[o_tail:], misc[o_tail + n + 1:]
+            if on_batch is not None:
+                cen_h = np.concatenate([np.asarray(r.grid, dtype=np.int32).reshape(-1, 2) for r in group])
+                egs_h = [r.echogram for r in group for _ in range(len(r.grid))]
+            for b0 in range(0, P, step):
+                Pb = min(step, P - b0)
+                stats["batches"].append(Pb)
+                raw = eng._buf("eval.raw", (Pb, C, ph, pw), torch.float32)
+                lab = eng._buf("eval.lab", (Pb, ph, pw), torch.int16)
+                call("crimac_gather_eval_crops_multi", ptr(misc), n, ptr(src, b0), C, ptr(cen, 2 * b0), Pb, ph, pw,
+                     ptr(raw), ptr(lab))
+                labels_t = torch.empty((Pb, ph, pw), dtype=torch.int16, device=dev)
+                call("crimac_labels_test_transform_multi", ptr(lab), lab.element_size(), ptr(raw), C - 1, 1e-7, 1e-4,
+                     ptr(cen64, 2 * b0), ptr(misc), n, ptr(src, b0), SEABED_PAD, overlap, ptr(labels_t), Pb, C, ph, pw)
+                x = eng._buf("tiled.x", (Pb * ph * pw, 16))
+                if masked:
+                    call("crimac_labels_extend_mask_multi", ptr(labels_t), ptr(raw), C, ptr(cen64, 2 * b0), ptr(boxes),
+                         ptr(box_off), n, ptr(src, b0), -1, Pb, ph, pw)
+                    call("crimac_gather_patches_memm_labels_multi", eng.prec, ptr(misc), n, ptr(src, b0), C,
+                         ptr(cen, 2 * b0), Pb, ph, pw, ptr(x), 16, ptr(labels_t))
+                else:
+                    call("crimac_gather_patches_memm_multi", eng.prec, ptr(misc), n, ptr(src, b0), C, ptr(cen, 2 * b0), Pb,
+                         ph, pw, ptr(x), 16)
+                logits = eval_logits(eng, x, Pb, ph, pw, predict_fn=predict_fn, split=True)
+                if on_batch is not None:
+                    emit(cen_h[b0:b0 + Pb], labels_t, logits, lambda: egs_h[b0:b0 + Pb])
+                B, nc, H, Wd = logits.shape
+                call("crimac_pr_histogram", ptr(logits), nc, ptr(labels_t), labels_t.element_size(), B, H, Wd, ptr(hist[0]),
+                     ptr(hist[1]))
+            feed.computed()
+        return done()

@@ -130,7 +130,7 @@ extern "C" {
  * points changes, and a binding must refuse a library whose version differs from the header it was written against (an
  * older build that happens to export every symbol would walk a descriptor array with the wrong stride).
  * crimac_layer_desc_size() is sizeof(crimac_layer_desc) as the library was compiled. */
-#define CRIMAC_ABI_VERSION 12
+#define CRIMAC_ABI_VERSION 13
 int crimac_version(void);
 int crimac_layer_desc_size(void);
 const char* crimac_last_error(void);
@@ -564,6 +564,23 @@ int crimac_scatter_patches_multi(const float* probs, int ncls, const crimac_memm
 int crimac_gather_eval_crops(const float* data, int C, int Wd, int H, const short* labels, const int* centres, int P,
                              int ph, int pw, int flavour, float* data_out, short* labels_out, void* stream);
 
+/* Evaluation batches packed from SEVERAL memmap echograms (tiled_inference.evaluate_echograms_memm): the evaluation chain
+ * with the per-source arguments of each patch taken from descs[src[p]] (crimac_memm_desc above; `out` is unused here), as
+ * crimac_gather_patches_memm_multi does for prediction.  Each equals its single-source entry point run per echogram, bit
+ * for bit; a patch whose src lies outside [0, n_desc) is skipped -- nothing is read, nothing is written; sources are
+ * indexed with 64-bit arithmetic.
+ *
+ * crimac_gather_eval_crops_multi: crimac_gather_eval_crops, flavour 1 (get_crop_memmap), with data, labels, Wd = n_pings and
+ *   H = n_range of the descriptor (a descriptor without data or labels is skipped); centres[p] lie in the patch's own
+ *   echogram, and the rule "centre row = H / 2 when H <= ph" goes by that echogram's H. */
+int crimac_gather_eval_crops_multi(const crimac_memm_desc* descs, int n_desc, const int* src, int C, const int* centres,
+                                   int P, int ph, int pw, float* data_out, short* labels_out, void* stream);
+/* crimac_gather_patches_memm_labels without metadata planes (flags 0, db_scaled 0), every storage type: the data crop of
+ *   patch p from descs[src[p]], the border rule by patch_labels [P][ph][pw] (the batch's transformed labels). */
+int crimac_gather_patches_memm_labels_multi(int prec, const crimac_memm_desc* descs, int n_desc, const int* src, int C,
+                                            const int* centres, int P, int ph, int pw, void* out, long ld,
+                                            const short* patch_labels, void* stream);
+
 
 /* Validation metrics (get_predictions_dataloader + compute_evaluation_metrics, pipeline.py:242-295):
  * histograms (16384 bins, indexed by the float16 bit pattern of softmax(logits)[SANDEEL]) of the valid
@@ -692,6 +709,21 @@ int crimac_labels_test_transform(const void* labels_in, int label_bytes, const f
  * data [B][C][H][W] fp32 linear sv; H * W <= 65536. */
 int crimac_labels_extend_mask(short* labels, const float* data, int C, const long long* centres, const int* boxes,
                               int n_boxes, int ignore_val, int B, int H, int W, void* stream);
+
+/* The two label kernels above for batches packed from several memmap echograms (crimac_gather_eval_crops_multi).
+ * crimac_labels_test_transform_multi: seabed rule 1 (Echogram) only, no seabed mask; the seabed vector (from ping 0,
+ *   seabed_pings = n_pings) and n_range of patch b come from descs[src[b]]; a NULL `seabed` in a descriptor means no seabed
+ *   rule for that echogram (as in crimac_scatter_patches_multi).  centres [B][2] int64 in the patch's own echogram.
+ * crimac_labels_extend_mask_multi: boxes [box_off[n_desc]][4] int32 holds the ALREADY extended boxes of all echograms of
+ *   the table, one echogram after the other; box_off int32 [n_desc + 1], ascending from 0; patch b is tested against boxes
+ *   [box_off[src[b]], box_off[src[b] + 1]) only.  An echogram without boxes leaves nothing unmasked, as n_boxes = 0 above. */
+int crimac_labels_test_transform_multi(const void* labels_in, int label_bytes, const float* data, int thr_channel,
+                                       float thr_lo, float thr_hi, const long long* centres,
+                                       const crimac_memm_desc* descs, int n_desc, const int* src, int seabed_pad,
+                                       int overlap, short* labels_out, int B, int C, int H, int W, void* stream);
+int crimac_labels_extend_mask_multi(short* labels, const float* data, int C, const long long* centres, const int* boxes,
+                                    const int* box_off, int n_desc, const int* src, int ignore_val, int B, int H, int W,
+                                    void* stream);
 
 /* ---- narrow layers (start_filts 8, 16, 32; csrc/narrow.hip) ------------------------------------------------
  * Layers below the 64-channel tiles of crimac_conv3x3 / crimac_igemm_conv.  Weights are the fp32 MASTER tensors (no packed
