@@ -5,7 +5,13 @@ Each HIP kernel is compared with the torch CPU fp32 op the reference dispatches 
   * 'f32x6' (parity mode): 2e-6 of max|ref| -- 3-plane split, ~2^-24 per product (fp32-equivalent);
   * 'f32x3': 1e-4 of max|ref| -- 2-plane split-bf16 products carry ~2^-16 relative error;
   * 'bf16' / 'fp16' (16-bit storage modes): inputs are pre-rounded on the host, so what is left is the
-    rounding of the OUTPUT (2^-9 / 2^-11 relative) and accumulation order: 1e-2 / 2e-3 of max|ref|.
+    rounding of the OUTPUT (2^-8 / 2^-11 relative) and accumulation order: 1e-2 / 2e-3 of max|ref|.
+
+The BatchNorm / ReLU / max-pool / unpool kernels (colstats, colsum_f32, sum_replicas, bn_finalize, bn_train_act_pool,
+bn_act_pool, unpool_add, bn_bwd_reduce and the four bn_bwd_apply paths) have their direct tests in
+tests/test_gpu_bn_kernels.py: a float64 reference, data on which the ReLU and arg-max decisions are exact, element-wise
+bounds, edge channel counts, strided / sliced / guarded buffers and capped grids.  The tests of those kernels below compare
+them at the workload's shapes and with one another.
 """
 import numpy as np
 import pytest
