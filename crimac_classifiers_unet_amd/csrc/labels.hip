@@ -43,20 +43,28 @@ struct TestChain {
   const unsigned char* seabed_mask;     // the reader's 2-D mask [mask_pings][n_range] (1 below the seabed)
   int mask_ping0, mask_pings;
   int n_range, seabed_pad, seabed_rule, overlap;
+  // A batch packed from several memmap echograms (tiled_inference.evaluate_echograms_memm), descs != NULL: the seabed
+  // vector (from ping 0, one entry per ping) and the range extent of patch b are taken from descs[src[b]]; a descriptor
+  // without a seabed vector gets no seabed rule.
+  const crimac_memm_desc* descs; int n_desc; const int* src;
 };
 
 // One workgroup per (patch, band of BAND rows): it scans the whole patch for the bounding box (a few reads
 // per thread, L2-resident) and then works on its rows plus the 3 + 3 halo rows the two morphology passes need.
 constexpr int BAND = 32;
 
-// The body of one workgroup, shared by the kernels that take the seabed of the whole batch as arguments and by the one
-// that takes it per patch from a descriptor (labels_test_transform_multi_kernel): one text, the same labels.
 template <bool TEST>
-__device__ __forceinline__ void refine_labels_band(
+__global__ __launch_bounds__(kThreads) void refine_labels_kernel(
     const void* __restrict__ labels_in, int label_bytes, const unsigned char* __restrict__ aux,
     const float* __restrict__ data, int thr_channel, float thr_lo, float thr_hi, int mode,
-    short* __restrict__ labels_out, int C, int H, int W, const TestChain& tc) {
+    short* __restrict__ labels_out, int C, int H, int W, TestChain tc) {
   extern __shared__ unsigned char smem[];
+  if (TEST && tc.descs) {                               // a workgroup works on one patch: uniform over it
+    const int s = tc.src[blockIdx.x];
+    if (s < 0 || s >= tc.n_desc) return;                // (nobody waits at a barrier)
+    const crimac_memm_desc d = tc.descs[s];
+    tc.seabed = d.seabed; tc.seabed_pings = (int)d.n_pings; tc.n_range = (int)d.n_range;
+  }
   const int HW = H * W;
   const int r0 = blockIdx.y * BAND;                     // first output row of this band
   const int rows = min(BAND, H - r0);
@@ -171,29 +179,6 @@ __device__ __forceinline__ void refine_labels_band(
   }
 }
 
-template <bool TEST>
-__global__ __launch_bounds__(kThreads) void refine_labels_kernel(
-    const void* __restrict__ labels_in, int label_bytes, const unsigned char* __restrict__ aux,
-    const float* __restrict__ data, int thr_channel, float thr_lo, float thr_hi, int mode,
-    short* __restrict__ labels_out, int C, int H, int W, TestChain tc) {
-  refine_labels_band<TEST>(labels_in, label_bytes, aux, data, thr_channel, thr_lo, thr_hi, mode, labels_out, C, H, W, tc);
-}
-
-// The test-time chain of a batch packed from several memmap echograms (tiled_inference.evaluate_echograms_memm): seabed
-// rule 1 (Echogram, absolute rows) with the seabed vector (from ping 0, one entry per ping) and the range extent of patch
-// b taken from descs[src[b]]; a descriptor without a seabed vector gets no seabed rule.  A workgroup works on one patch,
-// so src[b] and the descriptor are uniform over it.
-__global__ __launch_bounds__(kThreads) void labels_test_transform_multi_kernel(
-    const void* __restrict__ labels_in, int label_bytes, const float* __restrict__ data, int thr_channel, float thr_lo,
-    float thr_hi, const long long* __restrict__ centres, const crimac_memm_desc* __restrict__ descs, int n_desc,
-    const int* __restrict__ src, int seabed_pad, int overlap, short* __restrict__ labels_out, int C, int H, int W) {
-  const int s = src[blockIdx.x];
-  if (s < 0 || s >= n_desc) return;                     // (uniform over the workgroup: nobody waits at a barrier)
-  const crimac_memm_desc d = descs[s];
-  const TestChain tc{centres, d.seabed, 0, (int)d.n_pings, nullptr, 0, 0, (int)d.n_range, seabed_pad, 1, overlap};
-  refine_labels_band<true>(labels_in, label_bytes, nullptr, data, thr_channel, thr_lo, thr_hi, 2, labels_out, C, H, W, tc);
-}
-
 // get_extended_label_mask_for_crop (batch/label_transforms/extend_label_masks.py:35-98), the last link of
 // define_label_transform_test when eval_mode is 'region' / 'trace' (batch/transforms.py:87-90): a pixel keeps its label
 // only inside a (host-extended) school bounding box, everything else becomes `ignore_val`; remove_nan_inf's label rule
@@ -202,12 +187,23 @@ __global__ __launch_bounds__(kThreads) void labels_test_transform_multi_kernel(
 // share in registers.
 constexpr int kBoxRound = 1024;
 
-// (the body of one workgroup = one patch, shared with extend_mask_multi_kernel)
-__device__ __forceinline__ void extend_mask_patch(short* __restrict__ labels, const float* __restrict__ data, int C,
-                                                  const long long* __restrict__ centres, const int* __restrict__ boxes,
-                                                  int n_boxes, int ignore_val, int H, int W) {
+// box_off != NULL (a batch packed from several echograms): patch b is tested against the boxes of its own echogram
+// only, rows [box_off[src[b]], box_off[src[b] + 1]) of `boxes`, the tables of all echograms one after the other.
+__global__ __launch_bounds__(kThreads) void extend_mask_kernel(short* __restrict__ labels, const float* __restrict__ data,
+                                                               int C, const long long* __restrict__ centres,
+                                                               const int* __restrict__ boxes, int n_boxes,
+                                                               const int* __restrict__ box_off, int n_desc,
+                                                               const int* __restrict__ src, int ignore_val, int H, int W) {
   __shared__ int list[kBoxRound][4];
   __shared__ int n_list;
+  if (box_off) {
+    const int s = src[blockIdx.x];
+    if (s < 0 || s >= n_desc) return;                     // (uniform over the workgroup)
+    const int first = box_off[s];
+    n_boxes = box_off[s + 1] - first;
+    if (first < 0 || n_boxes < 0) return;                 // (not an offset table: touch nothing)
+    boxes += 4 * (long)first;
+  }
   const int b = blockIdx.x, tid = threadIdx.x, HW = H * W;
   // the reference places the crop at centre - shape // 2 (extend_label_masks.py:64), one pixel off the crop's real
   // origin (utils/np.py:378-380) -- restated as is
@@ -250,55 +246,51 @@ __device__ __forceinline__ void extend_mask_patch(short* __restrict__ labels, co
   }
 }
 
-__global__ __launch_bounds__(kThreads) void extend_mask_kernel(short* __restrict__ labels, const float* __restrict__ data,
-                                                               int C, const long long* __restrict__ centres,
-                                                               const int* __restrict__ boxes, int n_boxes, int ignore_val,
-                                                               int H, int W) {
-  extend_mask_patch(labels, data, C, centres, boxes, n_boxes, ignore_val, H, W);
-}
-
-// Patch b is tested against the boxes of its own echogram only: rows [box_off[src[b]], box_off[src[b] + 1]) of `boxes`,
-// the tables of all echograms one after the other.
-__global__ __launch_bounds__(kThreads) void extend_mask_multi_kernel(short* __restrict__ labels,
-                                                                     const float* __restrict__ data, int C,
-                                                                     const long long* __restrict__ centres,
-                                                                     const int* __restrict__ boxes,
-                                                                     const int* __restrict__ box_off, int n_desc,
-                                                                     const int* __restrict__ src, int ignore_val, int H,
-                                                                     int W) {
-  const int s = src[blockIdx.x];
-  if (s < 0 || s >= n_desc) return;                     // (uniform over the workgroup)
-  const int first = box_off[s], n = box_off[s + 1] - first;
-  if (first < 0 || n < 0) return;                       // (not an offset table: touch nothing)
-  extend_mask_patch(labels, data, C, centres, boxes + 4 * (long)first, n, ignore_val, H, W);
-}
-
 }  // namespace
+
+static int extend_mask_run(const char* name, short* labels, const float* data, int C, const long long* centres,
+                           const int* boxes, int n_boxes, const int* box_off, int n_desc, const int* src, int ignore_val,
+                           int B, int H, int W, void* stream) {
+  CRIMAC_REQUIRE(labels && data && centres && C > 0, "%s: bad arguments", name);
+  CRIMAC_REQUIRE(B > 0 && H > 0 && W > 0 && (long)H * W <= 64L * kThreads, "%s: patch of %d x %d (at most 65536 pixels)",
+                 name, H, W);
+  CRIMAC_REQUIRE(ignore_val >= -32768 && ignore_val <= 32767, "%s: ignore_val %d", name, ignore_val);
+  hipLaunchKernelGGL(extend_mask_kernel, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, labels, data, C, centres, boxes,
+                     n_boxes, box_off, n_desc, src, ignore_val, H, W);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}
 
 extern "C" int crimac_labels_extend_mask(short* labels, const float* data, int C, const long long* centres,
                                          const int* boxes, int n_boxes, int ignore_val, int B, int H, int W,
                                          void* stream) {
-  CRIMAC_REQUIRE(labels && data && centres && (boxes || n_boxes == 0) && n_boxes >= 0 && C > 0,
-                 "labels_extend_mask: bad arguments (n_boxes=%d)", n_boxes);
-  CRIMAC_REQUIRE(B > 0 && H > 0 && W > 0 && (long)H * W <= 64L * kThreads,
-                 "labels_extend_mask: patch of %d x %d (at most 65536 pixels)", H, W);
-  CRIMAC_REQUIRE(ignore_val >= -32768 && ignore_val <= 32767, "labels_extend_mask: ignore_val %d", ignore_val);
-  hipLaunchKernelGGL(extend_mask_kernel, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, labels, data, C, centres, boxes,
-                     n_boxes, ignore_val, H, W);
-  CRIMAC_LAUNCH_CHECK();
-  return CRIMAC_OK;
+  CRIMAC_REQUIRE((boxes || n_boxes == 0) && n_boxes >= 0, "labels_extend_mask: bad arguments (n_boxes=%d)", n_boxes);
+  return extend_mask_run("labels_extend_mask", labels, data, C, centres, boxes, n_boxes, nullptr, 0, nullptr, ignore_val,
+                         B, H, W, stream);
 }
 
 extern "C" int crimac_labels_extend_mask_multi(short* labels, const float* data, int C, const long long* centres,
                                                const int* boxes, const int* box_off, int n_desc, const int* src,
                                                int ignore_val, int B, int H, int W, void* stream) {
-  CRIMAC_REQUIRE(labels && data && centres && box_off && src && n_desc > 0 && C > 0,
-                 "labels_extend_mask_multi: bad arguments (n_desc=%d)", n_desc);
-  CRIMAC_REQUIRE(B > 0 && H > 0 && W > 0 && (long)H * W <= 64L * kThreads,
-                 "labels_extend_mask_multi: patch of %d x %d (at most 65536 pixels)", H, W);
-  CRIMAC_REQUIRE(ignore_val >= -32768 && ignore_val <= 32767, "labels_extend_mask_multi: ignore_val %d", ignore_val);
-  hipLaunchKernelGGL(extend_mask_multi_kernel, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, labels, data, C, centres,
-                     boxes, box_off, n_desc, src, ignore_val, H, W);
+  CRIMAC_REQUIRE(box_off && src && n_desc > 0, "labels_extend_mask_multi: bad arguments (n_desc=%d)", n_desc);
+  return extend_mask_run("labels_extend_mask_multi", labels, data, C, centres, boxes, 0, box_off, n_desc, src, ignore_val,
+                         B, H, W, stream);
+}
+
+// The launch of refine_labels_kernel<TEST>: LDS for the two mask bands of W columns + the bounding box, above the default
+// limit for wide patches -- the attribute is per kernel and per device, set on the first use of either.
+template <bool TEST>
+static int refine_launch(const void* labels_in, int label_bytes, const unsigned char* aux, const float* data,
+                         int thr_channel, float thr_lo, float thr_hi, int mode, short* labels_out, int B, int C, int H,
+                         int W, const TestChain& tc, void* stream) {
+  static unsigned long long attr_devs = 0;      // bit d: done on device d
+  if (crimac_first_use_on_device(&attr_devs)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&refine_labels_kernel<TEST>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  }
+  const size_t lds = (size_t)(((2 * BAND + 18) * W + 15) & ~15) + 16;
+  hipLaunchKernelGGL(refine_labels_kernel<TEST>, dim3(B, cdiv(H, BAND)), dim3(kThreads), lds, (hipStream_t)stream,
+                     labels_in, label_bytes, aux, data, thr_channel, thr_lo, thr_hi, mode, labels_out, C, H, W, tc);
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
 }
@@ -314,17 +306,22 @@ extern "C" int crimac_refine_labels(const void* labels_in, int label_bytes, cons
   CRIMAC_REQUIRE(aux_mask || (C > 0 && thr_channel >= 0 && thr_channel < C), "refine_labels: bad channel %d of %d",
                  thr_channel, C);
   CRIMAC_REQUIRE(mode == 0 || mode == 1, "refine_labels: bad mode %d", mode);
-  static unsigned long long attr_devs = 0;      // bit d: done on device d (the attribute is per device)
-  if (crimac_first_use_on_device(&attr_devs)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&refine_labels_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const size_t lds = (size_t)(((2 * BAND + 18) * W + 15) & ~15) + 16;
-  hipLaunchKernelGGL(refine_labels_kernel<false>, dim3(B, cdiv(H, BAND)), dim3(kThreads), lds, (hipStream_t)stream,
-                     labels_in, label_bytes, aux_mask, data, thr_channel, thr_lo, thr_hi, mode, labels_out, C, H, W,
-                     TestChain{});
-  CRIMAC_LAUNCH_CHECK();
-  return CRIMAC_OK;
+  return refine_launch<false>(labels_in, label_bytes, aux_mask, data, thr_channel, thr_lo, thr_hi, mode, labels_out, B, C,
+                              H, W, TestChain{}, stream);
+}
+
+static int test_transform_run(const char* name, const void* labels_in, int label_bytes, const float* data, int thr_channel,
+                              float thr_lo, float thr_hi, short* labels_out, int B, int C, int H, int W,
+                              const TestChain& tc, void* stream) {
+  CRIMAC_REQUIRE(labels_in && labels_out && data && tc.centres && (label_bytes == 2 || label_bytes == 4 || label_bytes == 8),
+                 "%s: bad arguments (label_bytes=%d)", name, label_bytes);
+  CRIMAC_REQUIRE(B > 0 && H > 0 && W > 0 && W <= 1024 && H % 2 == 0 && W % 2 == 0 && (long)H * W < (1L << 30),
+                 "%s: patch of %d x %d (even sizes, W <= 1024)", name, H, W);
+  CRIMAC_REQUIRE(C > 0 && thr_channel >= 0 && thr_channel < C, "%s: bad channel %d of %d", name, thr_channel, C);
+  CRIMAC_REQUIRE(tc.overlap >= 0 && 2 * tc.overlap < H && 2 * tc.overlap < W && tc.seabed_pad >= 0, "%s: overlap %d / pad %d",
+                 name, tc.overlap, tc.seabed_pad);
+  return refine_launch<true>(labels_in, label_bytes, nullptr, data, thr_channel, thr_lo, thr_hi, 2, labels_out, B, C, H, W,
+                             tc, stream);
 }
 
 extern "C" int crimac_labels_test_transform(const void* labels_in, int label_bytes, const float* data, int thr_channel,
@@ -333,53 +330,23 @@ extern "C" int crimac_labels_test_transform(const void* labels_in, int label_byt
                                             int mask_ping0, int mask_pings, int n_range, int seabed_pad,
                                             int seabed_rule, int overlap, short* labels_out, int B, int C, int H,
                                             int W, void* stream) {
-  CRIMAC_REQUIRE(labels_in && labels_out && data && centres && (label_bytes == 2 || label_bytes == 4 || label_bytes == 8),
-                 "labels_test_transform: bad arguments (label_bytes=%d)", label_bytes);
-  CRIMAC_REQUIRE(B > 0 && H > 0 && W > 0 && W <= 1024 && H % 2 == 0 && W % 2 == 0 && (long)H * W < (1L << 30),
-                 "labels_test_transform: patch of %d x %d (even sizes, W <= 1024)", H, W);
-  CRIMAC_REQUIRE(C > 0 && thr_channel >= 0 && thr_channel < C, "labels_test_transform: bad channel %d of %d", thr_channel, C);
   CRIMAC_REQUIRE(!(seabed && seabed_mask), "labels_test_transform: give the seabed vector OR the seabed mask");
   CRIMAC_REQUIRE(seabed_rule == 0 || seabed_rule == 1, "labels_test_transform: seabed_rule=%d", seabed_rule);
-  CRIMAC_REQUIRE(overlap >= 0 && 2 * overlap < H && 2 * overlap < W && n_range > 0 && seabed_pad >= 0,
-                 "labels_test_transform: overlap %d / n_range %d / pad %d", overlap, n_range, seabed_pad);
-  static unsigned long long attr_devs = 0;
-  if (crimac_first_use_on_device(&attr_devs)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&refine_labels_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const size_t lds = (size_t)(((2 * BAND + 18) * W + 15) & ~15) + 16;
-  TestChain tc{centres, seabed, seabed_ping0, seabed_pings, seabed_mask, mask_ping0, mask_pings, n_range, seabed_pad,
-               seabed_rule, overlap};
-  hipLaunchKernelGGL(refine_labels_kernel<true>, dim3(B, cdiv(H, BAND)), dim3(kThreads), lds, (hipStream_t)stream,
-                     labels_in, label_bytes, (const unsigned char*)nullptr, data, thr_channel, thr_lo, thr_hi, 2, labels_out,
-                     C, H, W, tc);
-  CRIMAC_LAUNCH_CHECK();
-  return CRIMAC_OK;
+  CRIMAC_REQUIRE(n_range > 0, "labels_test_transform: n_range %d", n_range);
+  const TestChain tc{centres, seabed, seabed_ping0, seabed_pings, seabed_mask, mask_ping0, mask_pings, n_range, seabed_pad,
+                     seabed_rule, overlap};
+  return test_transform_run("labels_test_transform", labels_in, label_bytes, data, thr_channel, thr_lo, thr_hi, labels_out,
+                            B, C, H, W, tc, stream);
 }
 
+// Seabed rule 1 (Echogram, absolute rows); the kernel fills the seabed vector and the extents in per patch.
 extern "C" int crimac_labels_test_transform_multi(const void* labels_in, int label_bytes, const float* data,
                                                   int thr_channel, float thr_lo, float thr_hi, const long long* centres,
                                                   const crimac_memm_desc* descs, int n_desc, const int* src,
                                                   int seabed_pad, int overlap, short* labels_out, int B, int C, int H,
                                                   int W, void* stream) {
-  CRIMAC_REQUIRE(labels_in && labels_out && data && centres && (label_bytes == 2 || label_bytes == 4 || label_bytes == 8),
-                 "labels_test_transform_multi: bad arguments (label_bytes=%d)", label_bytes);
   CRIMAC_REQUIRE(descs && src && n_desc > 0, "labels_test_transform_multi: needs the descriptor table (n_desc=%d)", n_desc);
-  CRIMAC_REQUIRE(B > 0 && H > 0 && W > 0 && W <= 1024 && H % 2 == 0 && W % 2 == 0 && (long)H * W < (1L << 30),
-                 "labels_test_transform_multi: patch of %d x %d (even sizes, W <= 1024)", H, W);
-  CRIMAC_REQUIRE(C > 0 && thr_channel >= 0 && thr_channel < C, "labels_test_transform_multi: bad channel %d of %d",
-                 thr_channel, C);
-  CRIMAC_REQUIRE(overlap >= 0 && 2 * overlap < H && 2 * overlap < W && seabed_pad >= 0,
-                 "labels_test_transform_multi: overlap %d / pad %d", overlap, seabed_pad);
-  static unsigned long long attr_devs = 0;
-  if (crimac_first_use_on_device(&attr_devs)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&labels_test_transform_multi_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const size_t lds = (size_t)(((2 * BAND + 18) * W + 15) & ~15) + 16;
-  hipLaunchKernelGGL(labels_test_transform_multi_kernel, dim3(B, cdiv(H, BAND)), dim3(kThreads), lds, (hipStream_t)stream,
-                     labels_in, label_bytes, data, thr_channel, thr_lo, thr_hi, centres, descs, n_desc, src, seabed_pad,
-                     overlap, labels_out, C, H, W);
-  CRIMAC_LAUNCH_CHECK();
-  return CRIMAC_OK;
+  const TestChain tc{centres, nullptr, 0, 0, nullptr, 0, 0, 0, seabed_pad, 1, overlap, descs, n_desc, src};
+  return test_transform_run("labels_test_transform_multi", labels_in, label_bytes, data, thr_channel, thr_lo, thr_hi,
+                            labels_out, B, C, H, W, tc, stream);
 }

@@ -22,10 +22,33 @@ namespace {
 
 constexpr int TS = 32;   // tile side
 
+// Where the patches of a launch are read from.  descs == NULL: ONE source for all of them, given as scalars -- data
+// [C][Wd][H] fp32, labels [Wd][H] int16 (or NULL).  Otherwise (batches that span memmap echograms,
+// tiled_inference.predict_echograms_memm / evaluate_echograms_memm) src[p] picks patch p's crimac_memm_desc from a
+// device-resident table, and data, labels and both extents are that echogram's.  A block works on one patch (blockIdx.z),
+// so src[p], the descriptor load and the early return for a src[p] that names no descriptor are uniform over the block.
+// Both forms run the same kernel, hence the same body: the same bits.
+static_assert(sizeof(crimac_memm_desc) == 48, "crimac_memm_desc: six 64-bit fields (hip.MEMM_DESC_WORDS)");
+struct PatchSrc {
+  const float* data; int Wd, H; const short* labels;
+  const crimac_memm_desc* descs; int n_desc; const int* src;
+  __device__ __forceinline__ bool resolve(int p) {
+    if (!descs) return true;
+    const int i = src[p];
+    if (i < 0 || i >= n_desc) return false;
+    const crimac_memm_desc d = descs[i];
+    data = d.data; Wd = (int)d.n_pings; H = (int)d.n_range; labels = d.labels;
+    return true;
+  }
+  bool ok() const { return descs ? src && n_desc > 0 : data && Wd > 0 && H > 0; }      // (host: the launchers' check)
+};
+struct GatherSrc { PatchSrc from; int db_scaled; MetaPlaneSrc meta; const int* meta_centres; };
+
 // data [C][Wd][H] fp32; centres [P][2] = (cy, cx_local) with cx_local relative to the chunk slice.
-// border_labels != NULL (memm flavour, save_predict.py:222-265): labels [Wd][H] int16 raw annotation ids covering the
-// same extent as `data`; a pixel outside that extent, or whose raw label the test-time label transform maps to
-// "ignore" (convert_label_indexing: negative ids), gets 0.0 AFTER the dB transform in every channel
+// border_labels != NULL (memm flavour, save_predict.py:222-265; the source's labels, a descriptor without labels gets no
+// border rule): labels [Wd][H] int16 raw annotation ids covering the same extent as `data`; a pixel outside that extent,
+// or whose raw label the test-time label transform maps to "ignore" (convert_label_indexing: negative ids), gets 0.0
+// AFTER the dB transform in every channel
 // (set_data_border_value, batch/data_transforms/set_data_border_value.py:20-23, last step of define_data_transform_test).
 // meta.flags != 0 (early metadata injection, crimac_gather_patches_memm_meta): channels C .. C+Cm-1 of every pixel get
 // the crop's metadata planes (meta_plane_values, crop centred on meta_centres[p] = (range idx, GLOBAL ping idx)), which
@@ -36,15 +59,14 @@ constexpr int TS = 32;   // tile side
 // (batch/dataset.py:229-235): a pixel whose transformed label is -100 gets 0.0, every other pixel its dB value, in or
 // outside the extent of `data`.  The labels are those of get_crop_memmap's crop (crimac_gather_eval_crops, flavour 1), so
 // the data crop takes its centre row too: H / 2 when the window covers the whole water column (dataset.py:259-261).
-// The body of one block = one 32 x 32 tile of patch blockIdx.z, shared by the single-source kernels and by the kernel that
-// takes the source of every patch from a descriptor (gather_patches_multi_kernel): one text, the same bits.
-template <typename T, bool PATCH_LABELS = false>
+// The body of one block = one 32 x 32 tile of patch blockIdx.z; gather_patches_kernel hands it the source of that patch.
+template <typename T, bool PATCH_LABELS>
 __device__ __forceinline__ void gather_patch_tile(const float* __restrict__ data, int C, int Wd, int H,
                                                   const int* __restrict__ centres, int ph, int pw,
                                                   T* __restrict__ out, int ld,
                                                   const short* __restrict__ border_labels, int db_scaled,
                                                   const MetaPlaneSrc& meta, const int* __restrict__ meta_centres,
-                                                  const short* __restrict__ patch_labels = nullptr) {
+                                                  const short* __restrict__ patch_labels) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float* tile = reinterpret_cast<float*>(smem_raw);      // [C][TS (x)][TS + 1 (y)]
   const int p = blockIdx.z;
@@ -107,25 +129,14 @@ __device__ __forceinline__ void gather_patch_tile(const float* __restrict__ data
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void gather_patches_kernel(const float* __restrict__ data, int C, int Wd,
-                                                             int H, const int* __restrict__ centres,
-                                                             int ph, int pw, T* __restrict__ out,
-                                                             int ld, const short* __restrict__ border_labels,
-                                                             int db_scaled, MetaPlaneSrc meta,
-                                                             const int* __restrict__ meta_centres) {
-  gather_patch_tile<T>(data, C, Wd, H, centres, ph, pw, out, ld, border_labels, db_scaled, meta, meta_centres);
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void gather_patches_labels_kernel(const float* __restrict__ data, int C, int Wd,
-                                                                    int H, const int* __restrict__ centres,
-                                                                    int ph, int pw, T* __restrict__ out, int ld,
-                                                                    const short* __restrict__ patch_labels,
-                                                                    int db_scaled, MetaPlaneSrc meta,
-                                                                    const int* __restrict__ meta_centres) {
-  gather_patch_tile<T, true>(data, C, Wd, H, centres, ph, pw, out, ld, nullptr, db_scaled, meta, meta_centres,
-                             patch_labels);
+template <typename T, bool PATCH_LABELS>
+__global__ __launch_bounds__(256) void gather_patches_kernel(GatherSrc g, int C, const int* __restrict__ centres, int ph,
+                                                             int pw, T* __restrict__ out, int ld,
+                                                             const short* __restrict__ patch_labels) {
+  PatchSrc& s = g.from;
+  if (!s.resolve(blockIdx.z)) return;                      // (uniform over the block: nobody waits at the barrier)
+  gather_patch_tile<T, PATCH_LABELS>(s.data, C, s.Wd, s.H, centres, ph, pw, out, ld, PATCH_LABELS ? nullptr : s.labels,
+                                     g.db_scaled, g.meta, g.meta_centres, patch_labels);
 }
 
 // probs [P][ncls][ph][pw] fp32; centres [P][2] global (cy, cx); out [2][H][n_chunk] fp32 (or fp16).
@@ -186,46 +197,9 @@ __global__ __launch_bounds__(256) void scatter_patches_kernel(ScatterParams q) {
   }
 }
 
-// ---- batches that span memmap echograms (tiled_inference.predict_echograms_memm) ---------------------------------------
-// The two kernels above read ONE source and write ONE destination, given as scalar arguments.  A forward batch packed
-// from several echograms needs both per patch: src[p] picks the patch's crimac_memm_desc from a device-resident table.
-// A block works on one patch, so the descriptor, src[p] and the centre are uniform over the block.
-
-// crimac_gather_patches_memm's kernel (border rule, no metadata planes, db_with_limits) with the source taken from
-// descs[src[p]]: gather_patch_tile on that echogram.  A descriptor without labels gets no border rule, as a NULL
-// border_labels in the single-source kernel.
-static_assert(sizeof(crimac_memm_desc) == 48, "crimac_memm_desc: six 64-bit fields (hip.MEMM_DESC_WORDS)");
-
-template <typename T>
-__global__ __launch_bounds__(256) void gather_patches_multi_kernel(const crimac_memm_desc* __restrict__ descs,
-                                                                   int n_desc, const int* __restrict__ src, int C,
-                                                                   const int* __restrict__ centres, int ph, int pw,
-                                                                   T* __restrict__ out, int ld) {
-  const int s = src[blockIdx.z];
-  if (s < 0 || s >= n_desc) return;                        // (uniform over the block: nobody waits at the barrier)
-  const crimac_memm_desc d = descs[s];
-  gather_patch_tile<T>(d.data, C, (int)d.n_pings, (int)d.n_range, centres, ph, pw, out, ld, d.labels, 0, MetaPlaneSrc{},
-                       nullptr);
-}
-
-// crimac_gather_patches_memm_labels' kernel in its flags == 0 form (border rule by the TRANSFORMED labels of the patches,
-// no metadata planes, db_with_limits) with the source taken from descs[src[p]]; patch_labels belong to the batch, not to
-// a source.  (tiled_inference.evaluate_echograms_memm, eval_mode 'region' / 'trace')
-template <typename T>
-__global__ __launch_bounds__(256) void gather_patches_labels_multi_kernel(const crimac_memm_desc* __restrict__ descs,
-                                                                          int n_desc, const int* __restrict__ src, int C,
-                                                                          const int* __restrict__ centres, int ph, int pw,
-                                                                          T* __restrict__ out, int ld,
-                                                                          const short* __restrict__ patch_labels) {
-  const int s = src[blockIdx.z];
-  if (s < 0 || s >= n_desc) return;
-  const crimac_memm_desc d = descs[s];
-  gather_patch_tile<T, true>(d.data, C, (int)d.n_pings, (int)d.n_range, centres, ph, pw, out, ld, nullptr, 0,
-                             MetaPlaneSrc{}, nullptr, patch_labels);
-}
-
-// scatter_patches_kernel with the memm rules only (labels, seabed vector from ping 0, seabed_rule 1, no data0), the
-// destination [2][n_range][n_pings], the labels, the seabed vector and the two extents taken from descs[src[p]].
+// scatter_patches_kernel for batches that span memmap echograms: the memm rules only (labels, seabed vector from ping 0,
+// seabed_rule 1, no data0), the destination [2][n_range][n_pings], the labels, the seabed vector and the two extents
+// taken from descs[src[p]] (PatchSrc's table; the grid and the rule set differ, so the kernel stays its own).
 // blockIdx.y = patch.  Interiors of different patches are disjoint, within an echogram and across echograms: plain stores.
 struct ScatterMultiParams {
   const float* probs; int ncls; const crimac_memm_desc* descs; int n_desc; const int* src; const int* centres;
@@ -303,12 +277,15 @@ __global__ __launch_bounds__(256) void pr_histogram_kernel(const float* __restri
 // 0, and a water column not deeper than the patch puts the centre row at H / 2.
 // A pure streaming transpose: one 32 x 32 tile per block and plane, lanes along range (contiguous in the chunk) when
 // reading, along ping (contiguous in the crop) when writing; `vec`: 16-byte stores (pw % 8 == 0, 16-byte aligned bases).
-// The body of one block = one 32 x 32 tile of patch blockIdx.z, shared by the single-source kernel and by the kernel that
-// takes the source of every patch from a descriptor (gather_eval_crops_multi_kernel): one text, the same bits.
-__device__ __forceinline__ void eval_crops_tile(const float* __restrict__ data, int C, int Wd, int H,
-                                                const short* __restrict__ labels, const int* __restrict__ centres,
-                                                int ph, int pw, int flavour, int vec, float* __restrict__ data_out,
-                                                short* __restrict__ labels_out) {
+// One block = one 32 x 32 tile of patch blockIdx.z.  With a descriptor table (flavour 1 only) the centre-row rule of a
+// water column not deeper than the patch is the patch's own echogram's; a descriptor without data or labels is skipped.
+__global__ __launch_bounds__(256) void gather_eval_crops_kernel(PatchSrc s, int C, const int* __restrict__ centres, int ph,
+                                                                int pw, int flavour, int vec, float* __restrict__ data_out,
+                                                                short* __restrict__ labels_out) {
+  if (!s.resolve(blockIdx.z) || !s.data || !s.labels) return;      // (uniform over the block: nobody waits at a barrier)
+  const float* __restrict__ data = s.data;
+  const short* __restrict__ labels = s.labels;
+  const int Wd = s.Wd, H = s.H;
   __shared__ float tile[TS][TS + 1];          // [x (ping)][y (range)]
   __shared__ short ltile[TS][TS + 2];
   const int p = blockIdx.z;
@@ -377,43 +354,35 @@ __device__ __forceinline__ void eval_crops_tile(const float* __restrict__ data, 
   }
 }
 
-__global__ __launch_bounds__(256) void gather_eval_crops_kernel(const float* __restrict__ data, int C, int Wd, int H,
-                                                                const short* __restrict__ labels,
-                                                                const int* __restrict__ centres, int ph, int pw,
-                                                                int flavour, int vec, float* __restrict__ data_out,
-                                                                short* __restrict__ labels_out) {
-  eval_crops_tile(data, C, Wd, H, labels, centres, ph, pw, flavour, vec, data_out, labels_out);
-}
-
-// flavour 1 (get_crop_memmap) with data, labels and both extents taken from descs[src[p]] -- the centre-row rule of a water
-// column not deeper than the patch is then the patch's own echogram's.  A descriptor without data or labels is skipped.
-__global__ __launch_bounds__(256) void gather_eval_crops_multi_kernel(const crimac_memm_desc* __restrict__ descs,
-                                                                      int n_desc, const int* __restrict__ src, int C,
-                                                                      const int* __restrict__ centres, int ph, int pw,
-                                                                      int vec, float* __restrict__ data_out,
-                                                                      short* __restrict__ labels_out) {
-  const int s = src[blockIdx.z];
-  if (s < 0 || s >= n_desc) return;                        // (uniform over the block: nobody waits at a barrier)
-  const crimac_memm_desc d = descs[s];
-  if (!d.data || !d.labels) return;
-  eval_crops_tile(d.data, C, (int)d.n_pings, (int)d.n_range, d.labels, centres, ph, pw, 1, vec, data_out, labels_out);
-}
-
 }  // namespace
+
+static int eval_crops_run(const char* name, const PatchSrc& s, int C, const int* centres, int P, int ph, int pw,
+                          int flavour, float* data_out, short* labels_out, void* stream) {
+  CRIMAC_REQUIRE(s.ok() && (s.descs || s.labels) && centres && data_out && labels_out && C > 0 && P > 0 && ph > 0 && pw > 0,
+                 "%s: bad arguments", name);
+  CRIMAC_REQUIRE(P <= 65535, "%s: at most 65535 patches per call", name);
+  const int vec = pw % 8 == 0 && ((uintptr_t)data_out & 15) == 0 && ((uintptr_t)labels_out & 15) == 0;
+  dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
+  hipLaunchKernelGGL(gather_eval_crops_kernel, grid, dim3(256), 0, (hipStream_t)stream, s, C, centres, ph, pw, flavour,
+                     vec, data_out, labels_out);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}
 
 extern "C" int crimac_gather_eval_crops(const float* data, int C, int Wd, int H, const short* labels, const int* centres,
                                         int P, int ph, int pw, int flavour, float* data_out, short* labels_out,
                                         void* stream) {
-  CRIMAC_REQUIRE(data && labels && centres && data_out && labels_out && C > 0 && Wd > 0 && H > 0 && P > 0 && ph > 0 &&
-                     pw > 0, "gather_eval_crops: bad arguments");
   CRIMAC_REQUIRE(flavour == 0 || flavour == 1, "gather_eval_crops: flavour=%d (0 zarr, 1 memm)", flavour);
-  CRIMAC_REQUIRE(P <= 65535, "gather_eval_crops: at most 65535 patches per call");
-  const int vec = pw % 8 == 0 && ((uintptr_t)data_out & 15) == 0 && ((uintptr_t)labels_out & 15) == 0;
-  dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
-  hipLaunchKernelGGL(gather_eval_crops_kernel, grid, dim3(256), 0, (hipStream_t)stream, data, C, Wd, H, labels, centres,
-                     ph, pw, flavour, vec, data_out, labels_out);
-  CRIMAC_LAUNCH_CHECK();
-  return CRIMAC_OK;
+  return eval_crops_run("gather_eval_crops", PatchSrc{data, Wd, H, labels}, C, centres, P, ph, pw, flavour, data_out,
+                        labels_out, stream);
+}
+
+extern "C" int crimac_gather_eval_crops_multi(const crimac_memm_desc* descs, int n_desc, const int* src, int C,
+                                              const int* centres, int P, int ph, int pw, float* data_out,
+                                              short* labels_out, void* stream) {
+  CRIMAC_REQUIRE(descs, "gather_eval_crops_multi: needs the descriptor table");
+  return eval_crops_run("gather_eval_crops_multi", PatchSrc{nullptr, 0, 0, nullptr, descs, n_desc, src}, C, centres, P,
+                        ph, pw, 1, data_out, labels_out, stream);
 }
 
 extern "C" int crimac_pr_histogram(const float* logits, int ncls, const void* labels, int label_bytes,
@@ -431,27 +400,31 @@ extern "C" int crimac_pr_histogram(const float* logits, int ncls, const void* la
   return CRIMAC_OK;
 }
 
-static int gather_run(int prec, const float* data, int C, int Wd, int H, const int* centres, int P, int ph, int pw,
-                      void* out, long ld, const short* border_labels, int db_scaled, const MetaPlaneSrc& meta,
-                      const int* meta_centres, void* stream, const short* patch_labels = nullptr) {
-  CRIMAC_REQUIRE(prec >= CRIMAC_PREC_BF16 && prec <= CRIMAC_PREC_MAX, "gather_patches: bad precision %d", prec);
-  CRIMAC_REQUIRE(data && centres && out && C > 0 && C <= 16 && Wd > 0 && H > 0 && P > 0 && ph > 0 && pw > 0,
-                 "gather_patches: bad arguments (C=%d must be <= 16)", C);
-  CRIMAC_REQUIRE(ld >= C && ld % 8 == 0 && ld <= 16, "gather_patches: ld=%ld must be 8 or 16 and >= C", ld);
-  CRIMAC_REQUIRE(P <= 65535, "gather_patches: at most 65535 patches per call");
-  CRIMAC_REQUIRE(!meta.flags || C + meta_plane_count(meta.flags) <= ld,
-                 "gather_patches: %d data + %d metadata channels do not fit ld=%ld", C, meta_plane_count(meta.flags), ld);
+// The one launcher of the gather family; `name`: the entry point the caller used.  patch_labels picks PATCH_LABELS.
+static int gather_run(const char* name, int prec, const GatherSrc& g, int C, const int* centres, int P, int ph, int pw,
+                      void* out, long ld, void* stream, const short* patch_labels = nullptr) {
+  const MetaPlaneSrc& m = g.meta;
+  CRIMAC_REQUIRE(prec >= CRIMAC_PREC_BF16 && prec <= CRIMAC_PREC_MAX, "%s: bad precision %d", name, prec);
+  CRIMAC_REQUIRE(g.from.ok() && centres && out && C > 0 && C <= 16 && P > 0 && ph > 0 && pw > 0,
+                 "%s: bad arguments (C=%d must be <= 16)", name, C);
+  CRIMAC_REQUIRE(ld >= C && ld % 8 == 0 && ld <= 16, "%s: ld=%ld must be 8 or 16 and >= C", name, ld);
+  CRIMAC_REQUIRE(P <= 65535, "%s: at most 65535 patches per call", name);
+  CRIMAC_REQUIRE(m.flags >= 0 && m.flags < 64, "%s: bad metadata flags %d", name, m.flags);
+  CRIMAC_REQUIRE(!m.flags || g.meta_centres, "%s: metadata planes need the global centres", name);
+  CRIMAC_REQUIRE(!(m.flags & 2) || (m.portion_day && m.n_day > 0), "%s: portion_day needs its vector", name);
+  CRIMAC_REQUIRE(!(m.flags & 4) || (m.time_diff && m.n_td > 0), "%s: time_diff needs its vector", name);
+  CRIMAC_REQUIRE(!(m.flags & 56) || (m.seabed && m.n_sb > 0), "%s: the depth planes need the seabed vector", name);
+  CRIMAC_REQUIRE(C + meta_plane_count(m.flags) <= ld, "%s: %d data + %d metadata channels do not fit ld=%ld", name, C,
+                 meta_plane_count(m.flags), ld);
   dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
   const size_t lds = (size_t)C * TS * (TS + 1) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
   if (patch_labels) {
-    CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(gather_patches_labels_kernel<T>, grid, dim3(256), lds, st, data, C,
-                                                   Wd, H, centres, ph, pw, (T*)out, (int)ld, patch_labels, db_scaled,
-                                                   meta, meta_centres));
+    CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL((gather_patches_kernel<T, true>), grid, dim3(256), lds, st, g, C,
+                                                   centres, ph, pw, (T*)out, (int)ld, patch_labels));
   } else {
-    CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(gather_patches_kernel<T>, grid, dim3(256), lds, st, data, C, Wd, H,
-                                                   centres, ph, pw, (T*)out, (int)ld, border_labels, db_scaled, meta,
-                                                   meta_centres));
+    CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL((gather_patches_kernel<T, false>), grid, dim3(256), lds, st, g, C,
+                                                   centres, ph, pw, (T*)out, (int)ld, patch_labels));
   }
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
@@ -459,14 +432,14 @@ static int gather_run(int prec, const float* data, int C, int Wd, int H, const i
 
 extern "C" int crimac_gather_patches(int prec, const float* data, int C, int Wd, int H, const int* centres,
                                      int P, int ph, int pw, void* out, long ld, void* stream) {
-  return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, nullptr, 0, MetaPlaneSrc{}, nullptr, stream);
+  return gather_run("gather_patches", prec, GatherSrc{{data, Wd, H}}, C, centres, P, ph, pw, out, ld, stream);
 }
 
 extern "C" int crimac_gather_patches_memm(int prec, const float* data, int C, int Wd, int H, const int* centres,
                                           int P, int ph, int pw, void* out, long ld, const short* border_labels,
                                           void* stream) {
   CRIMAC_REQUIRE(border_labels, "gather_patches_memm: needs the label array (border rule)");
-  return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, border_labels, 0, MetaPlaneSrc{}, nullptr,
+  return gather_run("gather_patches_memm", prec, GatherSrc{{data, Wd, H, border_labels}}, C, centres, P, ph, pw, out, ld,
                     stream);
 }
 
@@ -476,13 +449,10 @@ extern "C" int crimac_gather_patches_memm_meta(int prec, const float* data, int 
                                                int n_day, const double* time_diff, int n_td, const long long* seabed,
                                                int n_sb, const int* meta_centres, void* stream) {
   CRIMAC_REQUIRE(border_labels, "gather_patches_memm_meta: needs the label array (border rule)");
-  CRIMAC_REQUIRE(meta_centres && flags > 0 && flags < 64, "gather_patches_memm_meta: bad metadata arguments");
-  CRIMAC_REQUIRE(!(flags & 2) || (portion_day && n_day > 0), "gather_patches_memm_meta: portion_day needs its vector");
-  CRIMAC_REQUIRE(!(flags & 4) || (time_diff && n_td > 0), "gather_patches_memm_meta: time_diff needs its vector");
-  CRIMAC_REQUIRE(!(flags & 56) || (seabed && n_sb > 0), "gather_patches_memm_meta: the depth planes need the seabed vector");
+  CRIMAC_REQUIRE(flags > 0, "gather_patches_memm_meta: bad metadata arguments (flags=%d: no plane)", flags);
   const MetaPlaneSrc meta{flags, portion_year, portion_day, n_day, time_diff, n_td, seabed, n_sb};
-  return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, border_labels, db_scaled ? 1 : 0, meta,
-                    meta_centres, stream);
+  return gather_run("gather_patches_memm_meta", prec, GatherSrc{{data, Wd, H, border_labels}, db_scaled ? 1 : 0, meta,
+                    meta_centres}, C, centres, P, ph, pw, out, ld, stream);
 }
 
 extern "C" int crimac_gather_patches_memm_labels(int prec, const float* data, int C, int Wd, int H, const int* centres,
@@ -492,14 +462,28 @@ extern "C" int crimac_gather_patches_memm_labels(int prec, const float* data, in
                                                  const long long* seabed, int n_sb, const int* meta_centres,
                                                  void* stream) {
   CRIMAC_REQUIRE(patch_labels, "gather_patches_memm_labels: needs the transformed labels of the patches (border rule)");
-  CRIMAC_REQUIRE(flags >= 0 && flags < 64, "gather_patches_memm_labels: bad metadata flags %d", flags);
-  CRIMAC_REQUIRE(!flags || meta_centres, "gather_patches_memm_labels: metadata planes need the global centres");
-  CRIMAC_REQUIRE(!(flags & 2) || (portion_day && n_day > 0), "gather_patches_memm_labels: portion_day needs its vector");
-  CRIMAC_REQUIRE(!(flags & 4) || (time_diff && n_td > 0), "gather_patches_memm_labels: time_diff needs its vector");
-  CRIMAC_REQUIRE(!(flags & 56) || (seabed && n_sb > 0), "gather_patches_memm_labels: the depth planes need the seabed vector");
   const MetaPlaneSrc meta{flags, portion_year, portion_day, n_day, time_diff, n_td, seabed, n_sb};
-  return gather_run(prec, data, C, Wd, H, centres, P, ph, pw, out, ld, nullptr, db_scaled ? 1 : 0, meta, meta_centres,
-                    stream, patch_labels);
+  return gather_run("gather_patches_memm_labels", prec, GatherSrc{{data, Wd, H}, db_scaled ? 1 : 0, meta, meta_centres}, C,
+                    centres, P, ph, pw, out, ld, stream, patch_labels);
+}
+
+// The two forms for batches that span memmap echograms: border rule (by the descriptor's labels / by the TRANSFORMED
+// labels of the patches, which belong to the batch, not to a source), no metadata planes, db_with_limits.
+extern "C" int crimac_gather_patches_memm_multi(int prec, const crimac_memm_desc* descs, int n_desc, const int* src,
+                                                int C, const int* centres, int P, int ph, int pw, void* out, long ld,
+                                                void* stream) {
+  CRIMAC_REQUIRE(descs, "gather_patches_memm_multi: needs the descriptor table");
+  return gather_run("gather_patches_memm_multi", prec, GatherSrc{{nullptr, 0, 0, nullptr, descs, n_desc, src}}, C, centres,
+                    P, ph, pw, out, ld, stream);
+}
+
+extern "C" int crimac_gather_patches_memm_labels_multi(int prec, const crimac_memm_desc* descs, int n_desc, const int* src,
+                                                       int C, const int* centres, int P, int ph, int pw, void* out, long ld,
+                                                       const short* patch_labels, void* stream) {
+  CRIMAC_REQUIRE(descs, "gather_patches_memm_labels_multi: needs the descriptor table");
+  CRIMAC_REQUIRE(patch_labels, "gather_patches_memm_labels_multi: needs the transformed labels of the patches (border rule)");
+  return gather_run("gather_patches_memm_labels_multi", prec, GatherSrc{{nullptr, 0, 0, nullptr, descs, n_desc, src}}, C,
+                    centres, P, ph, pw, out, ld, stream, patch_labels);
 }
 
 extern "C" int crimac_scatter_patches_ex(const float* probs, int ncls, const int* centres, int P, int ph, int pw,
@@ -535,23 +519,6 @@ extern "C" int crimac_scatter_patches(const float* probs, int ncls, const int* c
                                    seabed_pad, 0, out, 0, stream);
 }
 
-extern "C" int crimac_gather_patches_memm_multi(int prec, const crimac_memm_desc* descs, int n_desc, const int* src,
-                                                int C, const int* centres, int P, int ph, int pw, void* out, long ld,
-                                                void* stream) {
-  CRIMAC_REQUIRE(prec >= CRIMAC_PREC_BF16 && prec <= CRIMAC_PREC_MAX, "gather_patches_memm_multi: bad precision %d", prec);
-  CRIMAC_REQUIRE(descs && src && centres && out && n_desc > 0 && C > 0 && C <= 16 && P > 0 && ph > 0 && pw > 0,
-                 "gather_patches_memm_multi: bad arguments (C=%d must be <= 16)", C);
-  CRIMAC_REQUIRE(ld >= C && ld % 8 == 0 && ld <= 16, "gather_patches_memm_multi: ld=%ld must be 8 or 16 and >= C", ld);
-  CRIMAC_REQUIRE(P <= 65535, "gather_patches_memm_multi: at most 65535 patches per call");
-  dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
-  const size_t lds = (size_t)C * TS * (TS + 1) * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
-  CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(gather_patches_multi_kernel<T>, grid, dim3(256), lds, st, descs,
-                                                 n_desc, src, C, centres, ph, pw, (T*)out, (int)ld));
-  CRIMAC_LAUNCH_CHECK();
-  return CRIMAC_OK;
-}
-
 extern "C" int crimac_scatter_patches_multi(const float* probs, int ncls, const crimac_memm_desc* descs, int n_desc,
                                             const int* src, const int* centres, int P, int ph, int pw, int overlap,
                                             int seabed_pad, int out_f16, void* stream) {
@@ -566,39 +533,6 @@ extern "C" int crimac_scatter_patches_multi(const float* probs, int ncls, const 
   if (bx > 64) bx = 64;
   ScatterMultiParams q{probs, ncls, descs, n_desc, src, centres, ph, pw, overlap, seabed_pad, out_f16};
   hipLaunchKernelGGL(scatter_patches_multi_kernel, dim3((unsigned)bx, (unsigned)P), dim3(256), 0, (hipStream_t)stream, q);
-  CRIMAC_LAUNCH_CHECK();
-  return CRIMAC_OK;
-}
-
-extern "C" int crimac_gather_eval_crops_multi(const crimac_memm_desc* descs, int n_desc, const int* src, int C,
-                                              const int* centres, int P, int ph, int pw, float* data_out,
-                                              short* labels_out, void* stream) {
-  CRIMAC_REQUIRE(descs && src && centres && data_out && labels_out && n_desc > 0 && C > 0 && P > 0 && ph > 0 && pw > 0,
-                 "gather_eval_crops_multi: bad arguments");
-  CRIMAC_REQUIRE(P <= 65535, "gather_eval_crops_multi: at most 65535 patches per call");
-  const int vec = pw % 8 == 0 && ((uintptr_t)data_out & 15) == 0 && ((uintptr_t)labels_out & 15) == 0;
-  dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
-  hipLaunchKernelGGL(gather_eval_crops_multi_kernel, grid, dim3(256), 0, (hipStream_t)stream, descs, n_desc, src, C,
-                     centres, ph, pw, vec, data_out, labels_out);
-  CRIMAC_LAUNCH_CHECK();
-  return CRIMAC_OK;
-}
-
-extern "C" int crimac_gather_patches_memm_labels_multi(int prec, const crimac_memm_desc* descs, int n_desc, const int* src,
-                                                       int C, const int* centres, int P, int ph, int pw, void* out, long ld,
-                                                       const short* patch_labels, void* stream) {
-  CRIMAC_REQUIRE(prec >= CRIMAC_PREC_BF16 && prec <= CRIMAC_PREC_MAX, "gather_patches_memm_labels_multi: bad precision %d",
-                 prec);
-  CRIMAC_REQUIRE(descs && src && centres && out && n_desc > 0 && C > 0 && C <= 16 && P > 0 && ph > 0 && pw > 0,
-                 "gather_patches_memm_labels_multi: bad arguments (C=%d must be <= 16)", C);
-  CRIMAC_REQUIRE(patch_labels, "gather_patches_memm_labels_multi: needs the transformed labels of the patches (border rule)");
-  CRIMAC_REQUIRE(ld >= C && ld % 8 == 0 && ld <= 16, "gather_patches_memm_labels_multi: ld=%ld must be 8 or 16 and >= C", ld);
-  CRIMAC_REQUIRE(P <= 65535, "gather_patches_memm_labels_multi: at most 65535 patches per call");
-  dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
-  const size_t lds = (size_t)C * TS * (TS + 1) * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
-  CRIMAC_FOR_STORAGE2(prec, TF_, T, hipLaunchKernelGGL(gather_patches_labels_multi_kernel<T>, grid, dim3(256), lds, st,
-                                                 descs, n_desc, src, C, centres, ph, pw, (T*)out, (int)ld, patch_labels));
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
 }

@@ -28,12 +28,14 @@ that a caller appends with the reference's ``create_xarray_ds_predictions`` / ``
 """
 from __future__ import annotations
 
+import contextlib
 import difflib
 import functools
 import inspect
 import itertools
 import os
 import time
+import types
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -528,9 +530,9 @@ def release_staging():
 
 
 class _ChunkFeed:
-    """The chunk pipeline of ``predict_survey``, ``evaluate_survey``, ``predict_echograms_memm`` and
-    ``evaluate_echograms_memm`` (whose chunk is a group of echograms): reader threads fill pinned host slots ahead of the GPU, a copy stream uploads each chunk into one of
-    two device slots while the chunk before it computes.  ``jobs`` is any iterable, taken from lazily.
+    """The chunk pipeline of ``predict_survey``, ``evaluate_survey`` and ``_MemmSurveyFlow`` (the memm survey flows, whose
+    chunk is a group of echograms): reader threads fill pinned host slots ahead of the GPU, a copy stream uploads each
+    chunk into one of two device slots while the chunk before it computes.  ``jobs`` is any iterable, taken from lazily.
 
     ``table`` {name: (elements, dtype)}: the flat buffers a chunk is staged in, one of each per host slot and per device
     slot.  The set (+ the caller's ``extra()`` buffers) is kept in ``_STAGING`` between surveys of the same key -- ``tag``
@@ -1095,11 +1097,11 @@ def _check_survey_seabed(name, seabed, single):
 
 
 class _MemmGroupStage:
-    """What ``predict_echograms_memm`` and ``evaluate_echograms_memm`` share of moving a group of echograms through a
-    ``_ChunkFeed``: the ``table`` of flat staging buffers (``cap`` pixels of ``C`` planes and of labels, ``n_misc`` int32
-    words), the transposed planes per device slot (``extra``), the reader thread's copy of a group into a pinned slot
-    (``read``) and the transposes on the copy stream (``transpose``).  ``misc`` holds, in this order: the descriptor table
-    int64 [n][MEMM_DESC_WORDS] | the centres int32 [P][2] | src int32 [P] | the seabed lines | the caller's tail."""
+    """What ``_MemmSurveyFlow`` needs to move a group of echograms through a ``_ChunkFeed``: the ``table`` of flat staging
+    buffers (``cap`` pixels of ``C`` planes and of labels, ``n_misc`` int32 words), the transposed planes per device slot
+    (``extra``), the reader thread's copy of a group into a pinned slot (``read``) and the transposes on the copy stream
+    (``transpose``).  ``misc`` holds, in this order: the descriptor table int64 [n][MEMM_DESC_WORDS] | the centres int32
+    [P][2] | src int32 [P] | the seabed lines | the caller's tail."""
 
     def __init__(self, dev, C, cap, frequencies):
         self.dev, self.C, self.cap, self.frequencies = dev, C, cap, frequencies
@@ -1113,8 +1115,8 @@ class _MemmGroupStage:
     def read(self, bufs, host, k, group, out=None, tail=None):
         """Group ``k`` (device slot k & 1) into the pinned slot ``host``; the descriptors point at the transposed planes,
         at the seabed lines inside the uploaded ``misc`` and -- ``out``: the flat float16 prediction buffer -- at the
-        echogram's [2, range, pings] share of it.  ``tail(misc, at) -> end``: writes the caller's words behind the seabed
-        lines.  Returns (uploads, the pixel offset of every echogram, the group's pixels, where the tail starts)."""
+        echogram's [2, range, pings] share of it.  ``tail(group, misc, at) -> end``: writes the caller's words behind the
+        seabed lines.  Returns (uploads, the pixel offset of every echogram, the group's pixels, where the tail starts)."""
         C, W = self.C, hip.MEMM_DESC_WORDS
         n, P = len(group), sum(len(r.grid) for r in group)
         misc = host["misc"].numpy()
@@ -1138,7 +1140,7 @@ class _MemmGroupStage:
             off, p0, o_sb = off + npx, p0 + Pe, o_sb + Wp
         o_tail = o_sb
         if tail is not None:
-            o_sb = tail(misc, o_sb)
+            o_sb = tail(group, misc, o_sb)
             assert o_tail <= o_sb <= self.n_misc, "memm group staging too small"
         return ({"data": host["data"][:C * off], "lab": host["lab"][:off], "misc": host["misc"][:o_sb]},
                 offs, off, o_tail)
@@ -1157,132 +1159,181 @@ class _MemmGroupStage:
         feed.main.wait_stream(feed.copy_stream)
 
 
+class _MemmSurveyFlow:
+    """What ``predict_echograms_memm`` and ``evaluate_echograms_memm`` share: a memm survey -- many small echograms --
+    moved through ONE ``_ChunkFeed``, forward batches packed across echograms.
+
+    ``echograms``: any iterable of the reference's ``Echogram`` API, consumed lazily (a few groups ahead of the group at
+    work).  Consecutive echograms form *groups* (``plan_memm_groups``): a group is closed when its patches reach
+    ``group_patches`` (default ``MEMM_GROUP_BATCHES`` forward batches) or its pixels ``group_elems`` (default
+    ``MEMM_GROUP_ELEMS``: the staging is allocated for that many).  All patches of a group form ONE patch list, cut into
+    forward batches of ``max(batch_size, INTERNAL_BATCH)`` (``batch_size`` with a ``predict_fn``, as in
+    ``ChunkPredictor.predict``): only the last batch of a group is short.  The ``_multi`` entry points take each patch's
+    source (and destination) from a descriptor table that goes up with the group's centres and seabed lines in one pinned
+    copy (``_MemmGroupStage``); reader threads copy the next groups' memmaps into pinned staging, the copy stream uploads
+    and transposes them while the current group computes.
+    ``seabed``: None (the reader's ``get_seabed``), ``"estimate"`` (``estimate_seabed_memm`` per echogram) or a callable
+    ``echogram -> integer array [n_pings]``; not an array, which belongs to one echogram.
+    **Models with metadata planes** (``UNet_LateMetInject``, or metadata input channels): the metadata sources are per
+    echogram and the metadata kernels read one source, so these models take the per-echogram path (``alone``,
+    ``each_alone``): the caller's single-echogram sibling for one echogram after the other; same interface, same results,
+    none of the packing.  An echogram larger than ``group_elems`` takes that path too, in its place in the order.
+    Multi-GPU (torch.distributed initialised): the *groups* (``alone``: the echograms) are dealt round-robin to the ranks.
+    ``skip(echogram) -> bool``: echograms to leave out; it is asked after the groups have been planned and dealt over the
+    WHOLE input (``iter_memm_groups``), so every echogram keeps its rank whatever the ranks skip.
+    ``stats`` (a dict): receives ``groups``, ``batches`` (the patches of every packed forward batch),
+    ``fallback_echograms`` (per-echogram path: metadata model) and ``solo_echograms`` (too large for the staging).
+    ``kwargs``: the other keys of the reference's ``config_args``, accepted and ignored as by the sibling calls; a near
+    miss of one of the caller's ``own`` keywords (``difflib.get_close_matches``: ``group_patch``, ``seabeds``, ``stat``
+    ...) is refused as a misspelling.  The checks come before anything is read."""
+
+    def __init__(self, name, own, kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
+                 group_patches, group_elems, stats, skip=None, eval_mode=None):
+        _refuse_near_misses(name, kwargs, own)
+        _check_survey_seabed(name, seabed, name.replace("echograms", "echogram"))
+        if eval_mode not in (None, "all", "region", "trace"):
+            raise ValueError(f"eval_mode={eval_mode!r}: 'all', 'region' or 'trace' (batch/transforms.py:87)")
+        self.echograms, self.seabed, self.skip = echograms, seabed, skip
+        self.patch_size, self.patch_overlap, self.frequencies = patch_size, patch_overlap, segpipe.frequencies
+        self.dev, self.C = segpipe.device, len(segpipe.frequencies)
+        self.eng = segpipe.model.to(self.dev).eval().infer_engine
+        (self.pw, self.ph), self.overlap = (int(v) for v in patch_size), int(patch_overlap)
+        self.step = max(int(batch_size), INTERNAL_BATCH) if predict_fn is None else int(batch_size)
+        self.group_patches = MEMM_GROUP_BATCHES * self.step if group_patches is None else int(group_patches)
+        self.cap = MEMM_GROUP_ELEMS if group_elems is None else int(group_elems)
+        self.rank, self.world = parallel.rank_world()
+        self.stats = {} if stats is None else stats
+        self.stats.update(groups=0, batches=[], fallback_echograms=0, solo_echograms=0)
+        self.alone = self.eng.lmi or self.eng.in_channels > self.C     # metadata planes: the per-echogram path
+
+    def each_alone(self):
+        """This rank's echograms, one per "group", each with the ``seabed`` argument of the single-echogram functions."""
+        given = self.seabed is None or isinstance(self.seabed, str)
+        for eg in shard_memm_groups(self.echograms, self.rank, self.world):
+            if self.skip is None or not self.skip(eg):
+                self.stats["fallback_echograms"] += 1
+                yield eg, self.seabed if given else _memm_survey_seabed(eg, self.seabed, self.dev)
+
+    def batches(self, P):
+        """``(first patch, patches)`` of every forward batch of a group of ``P`` patches."""
+        for b0 in range(0, P, self.step):
+            Pb = min(self.step, P - b0)
+            self.stats["batches"].append(Pb)
+            yield b0, Pb
+
+    @contextlib.contextmanager
+    def staged(self, tag, record=_MemmRecord, extra=None, out=None, tail=None):
+        """Plans this rank's groups; inside ``with``: an iterator that stages them one by one and yields each as a
+        namespace -- ``k``, ``group`` (the records), ``offs`` (the pixel offset of every echogram; None: ONE echogram too
+        large for the staging, nothing staged, the caller takes the per-echogram path), ``total`` (pixels), ``n`` / ``P``
+        (echograms / patches), ``misc`` (the int32 staging) with its views ``cen`` [P][2] and ``src`` [P], ``o_tail``
+        (where the caller's tail starts).  The caller enqueues the group's ``batches(P)`` and then calls
+        ``feed.computed()`` (done already for a group too large).  Nothing is allocated for an empty plan.
+        ``extra()``: the caller's buffers next to the stage's; ``out``: the name of the one the descriptors' ``out``
+        point into; ``tail(group, misc, at) -> end`` writes the caller's words behind the seabed lines."""
+        groups = iter_memm_groups(self.echograms, self.patch_size, self.patch_overlap, self.group_patches, self.seabed,
+                                  self.cap, self.rank, self.world, self.dev, self.skip, record)
+        first = next(groups, None)
+        if first is None:                                # nothing to do (an empty survey, everything skipped): no staging
+            yield iter(())
+            return
+        groups = itertools.chain([first], groups)
+        stage = _MemmGroupStage(self.dev, self.C, self.cap, self.frequencies)
+
+        def read(job, slot):
+            k, group = job
+            if group[0].elems > self.cap:                # too large for the staging: nothing staged
+                return {}, (group, None, 0, 0)
+            uploads, *staged = stage.read(feed.bufs, slot(), k, group, out=feed.bufs.get(out), tail=tail)
+            return uploads, (group, *staged)
+
+        with _ChunkFeed(self.dev, (tag, self.C), stage.table, 3, enumerate(groups), read,
+                        extra=lambda: dict(stage.extra(), **(extra() if extra else {}))) as feed:
+            self.feed = feed
+            self.eng.bind()
+            yield self._staged_groups(feed, stage)
+
+    def _staged_groups(self, feed, stage):
+        W = hip.MEMM_DESC_WORDS
+        for k, (d, (group, offs, total, o_tail)) in enumerate(feed):
+            self.stats["groups"] += 1
+            g = types.SimpleNamespace(k=k, group=group, offs=offs, total=total, o_tail=o_tail)
+            if offs is None:                         # the per-echogram path, in its place in the order
+                feed.computed()
+                self.stats["solo_echograms"] += 1
+            else:
+                g.n, g.P = len(group), sum(len(r.grid) for r in group)
+                stage.transpose(feed, k, d, group, offs)         # to the ping-major layout of the gather kernels
+                g.misc = d["misc"]
+                g.cen, g.src = g.misc[2 * W * g.n:], g.misc[2 * W * g.n + 2 * g.P:]
+            yield g
+
+
 def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn=None, meta_channels=None,
                            seabed=None, group_patches=None, stats=None, group_elems=None, skip=None, **kwargs):
     """``save_reader_predictions_memm`` (save_predict.py:222-265) for a whole memm survey -- a directory of many small
     echograms: a generator of ``(echogram, float64 [2, n_range, n_pings])`` in input order, every array equal to
-    ``predict_echogram_memm`` of that echogram (probabilities rounded to float16 on the GPU, then widened).
+    ``predict_echogram_memm`` of that echogram (probabilities rounded to float16 on the GPU, then widened); each rank
+    yields the echograms of its own groups only, no collective.
 
-    ``echograms``: any iterable of the reference's ``Echogram`` API, consumed lazily (a few groups ahead of the result
-    handed out).  Consecutive echograms form *groups* (``plan_memm_groups``): a group is closed when its patches reach
-    ``group_patches`` (default ``MEMM_GROUP_BATCHES`` forward batches) or its pixels ``group_elems`` (default
-    ``MEMM_GROUP_ELEMS``: the staging is allocated for that many).  All patches of a group form ONE patch list, cut into
-    forward batches of ``max(batch_size, INTERNAL_BATCH)`` (``batch_size`` with a ``predict_fn``, as in
-    ``ChunkPredictor.predict``): only the last batch of a group is short.  ``crimac_gather_patches_memm_multi`` /
-    ``crimac_scatter_patches_multi`` take each patch's source and destination from a descriptor table that goes up with
-    the group's centres and seabed lines in one pinned copy.  Reader threads copy the next groups' memmaps into pinned
-    staging (``_ChunkFeed``), the copy stream uploads and transposes them while the current group computes, and the
-    float16 results leave through a non-blocking download into a ring of two pinned buffers.
+    Groups, batches, ``seabed``, metadata models, ``skip`` (``save_predictions_memm``'s resume rule), ``stats`` and
+    ``kwargs``: ``_MemmSurveyFlow``.  Per batch ``crimac_gather_patches_memm_multi`` -> forward ->
+    ``crimac_scatter_patches_multi``; the float16 results of a group leave through a non-blocking download into a ring of
+    two pinned buffers."""
+    flow = _MemmSurveyFlow("predict_echograms_memm",
+                           ("group_patches", "group_elems", "seabed", "skip", "stats", "predict_fn", "meta_channels"),
+                           kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
+                           group_patches, group_elems, stats, skip=skip)
+    eng, C, ph, pw, cap = flow.eng, flow.C, flow.ph, flow.pw, flow.cap
 
-    ``seabed``: None (the reader's ``get_seabed``), ``"estimate"`` (``estimate_seabed_memm`` per echogram) or a callable
-    ``echogram -> integer array [n_pings]``; not an array, which belongs to one echogram.
-    **Models with metadata planes** (``UNet_LateMetInject``, or metadata input channels): the metadata sources are per
-    echogram and the metadata kernels read one source, so these models take the per-echogram path --
-    ``predict_echogram_memm`` for one echogram after the other, one echogram per "group"; same interface, same results,
-    none of the packing.  An echogram larger than ``group_elems`` takes that path too.
-    Multi-GPU (torch.distributed initialised): the *groups* are dealt round-robin to the ranks, no collective; each rank
-    yields the echograms of its own groups only.
-    ``skip(echogram) -> bool``: echograms to leave out (``save_predictions_memm``'s resume rule); it is asked after the
-    groups have been planned and dealt over the WHOLE input (``iter_memm_groups``), so every echogram keeps its rank
-    whatever the ranks skip.
-    ``stats`` (a dict): receives ``groups``, ``batches`` (the patches of every forward batch), ``fallback_echograms``
-    (per-echogram path: metadata model) and ``solo_echograms`` (per-echogram path: too large for the staging).
-    ``kwargs``: the other keys of the reference's ``config_args`` are accepted and ignored, as by the sibling calls; a
-    keyword that is a near miss of one of this function's own (``difflib.get_close_matches``: ``group_patch``,
-    ``group_elem``, ``seabeds``, ``stat`` ...) is refused, it is a misspelling."""
-    _refuse_near_misses("predict_echograms_memm", kwargs,
-                        ("group_patches", "group_elems", "seabed", "skip", "stats", "predict_fn", "meta_channels"))
-    _check_survey_seabed("predict_echograms_memm", seabed, "predict_echogram_memm")
-    dev = segpipe.device
-    model = segpipe.model.to(dev).eval()
-    eng = model.infer_engine
-    C = len(segpipe.frequencies)
-    pw, ph = (int(v) for v in patch_size)
-    overlap = int(patch_overlap)
-    step = max(int(batch_size), INTERNAL_BATCH) if predict_fn is None else int(batch_size)
-    group_patches = MEMM_GROUP_BATCHES * step if group_patches is None else int(group_patches)
-    cap = MEMM_GROUP_ELEMS if group_elems is None else int(group_elems)
-    rank, world = parallel.rank_world()
-    stats = {} if stats is None else stats
-    stats.update(groups=0, batches=[], fallback_echograms=0, solo_echograms=0)
+    def single(eg, sb, meta):            # the per-echogram path
+        return eg, predict_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, predict_fn=predict_fn,
+                                         meta_channels=meta, seabed=sb)
 
-    if eng.lmi or eng.in_channels > C:        # metadata planes: one echogram per group, the per-echogram path
-        for eg in shard_memm_groups(echograms, rank, world):
-            if skip is not None and skip(eg):
-                continue
-            sb = None if seabed is None or isinstance(seabed, str) else _memm_survey_seabed(eg, seabed, dev)
-            stats["fallback_echograms"] += 1
-            yield eg, predict_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, predict_fn=predict_fn,
-                                            meta_channels=meta_channels, seabed=seabed if sb is None else sb)
+    if flow.alone:
+        for eg, sb in flow.each_alone():
+            yield single(eg, sb, meta_channels)
         return
 
-    groups = iter_memm_groups(echograms, patch_size, patch_overlap, group_patches, seabed, cap, rank, world, dev, skip)
-    first = next(groups, None)
-    if first is None:                                # nothing to do (an empty survey, everything skipped): no staging
-        return
-    groups = itertools.chain([first], groups)
-    W = hip.MEMM_DESC_WORDS
-    stage = _MemmGroupStage(dev, C, cap, segpipe.frequencies)
-
-    def extra():            # transposed planes per device slot, the group's predictions, the result ring
-        return dict(stage.extra(), out=torch.empty(2 * cap, dtype=torch.float16, device=dev),
+    def extra():            # the group's predictions, the result ring
+        return dict(out=torch.empty(2 * cap, dtype=torch.float16, device=flow.dev),
                     pinned=[torch.empty(2 * cap, dtype=torch.float16).pin_memory() for _ in range(2)])
 
-    def read(job, slot):
-        k, group = job
-        if group[0].elems > cap:                     # too large for the staging: predict_echogram_memm, nothing staged
-            return {}, (group, None, 0)
-        uploads, offs, total, _ = stage.read(feed.bufs, slot(), k, group, out=feed.bufs["out"])
-        return uploads, (group, offs, total)
+    def take(group, offs, ring):            # the group whose download went into pinned[ring]
+        events[ring].synchronize()
+        for r, off in zip(group, offs):
+            res = pinned[ring][2 * off:2 * (off + r.pixels)].view(2, r.n_range, r.n_pings)
+            yield r.echogram, res.numpy().astype(np.float64)
 
-    with _ChunkFeed(dev, ("memm", C), stage.table, 3, enumerate(groups), read, extra=extra) as feed:
-        bufs = feed.bufs
-        pinned, out = bufs["pinned"], bufs["out"]
-        events = [torch.cuda.Event() for _ in range(2)]
-        eng.bind()
-
-        def take(group, offs, ring):            # the group whose download went into pinned[ring]
-            events[ring].synchronize()
-            for r, off in zip(group, offs):
-                res = pinned[ring][2 * off:2 * (off + r.pixels)].view(2, r.n_range, r.n_pings)
-                yield r.echogram, res.numpy().astype(np.float64)
-
+    with flow.staged("memm", extra=extra, out="out") as groups:
         pending = None
-        for k, (d, (group, offs, total)) in enumerate(feed):
-            stats["groups"] += 1
-            if offs is None:                         # the per-echogram path, in its place in the order
-                feed.computed()
+        for g in groups:
+            if g.k == 0:                             # (there is a group: the staging exists)
+                pinned, out = flow.feed.bufs["pinned"], flow.feed.bufs["out"]
+                events = [torch.cuda.Event() for _ in range(2)]
+            if g.offs is None:
                 if pending is not None:
                     yield from take(*pending)
                     pending = None
-                r = group[0]
-                stats["solo_echograms"] += 1
-                yield r.echogram, predict_echogram_memm(r.echogram, segpipe, patch_size, patch_overlap, batch_size,
-                                                        predict_fn=predict_fn, seabed=r.seabed)
+                yield single(g.group[0].echogram, g.group[0].seabed, None)
                 continue
-            n, P = len(group), sum(len(r.grid) for r in group)
-            stage.transpose(feed, k, d, group, offs)         # to the ping-major layout of the gather kernel
-            misc = d["misc"]
-            cen, src = misc[2 * W * n:], misc[2 * W * n + 2 * P:]
-            out[:2 * total].zero_()
-            for b0 in range(0, P, step):
-                Pb = min(step, P - b0)
-                stats["batches"].append(Pb)
+            out[:2 * g.total].zero_()
+            for b0, Pb in flow.batches(g.P):
                 x = eng._buf("tiled.x", (Pb * ph * pw, 16))
-                call("crimac_gather_patches_memm_multi", eng.prec, ptr(misc), n, ptr(src, b0), C, ptr(cen, 2 * b0), Pb, ph,
-                     pw, ptr(x), 16)
+                call("crimac_gather_patches_memm_multi", eng.prec, ptr(g.misc), g.n, ptr(g.src, b0), C, ptr(g.cen, 2 * b0),
+                     Pb, ph, pw, ptr(x), 16)
                 if predict_fn is not None:
                     probs = predict_fn(x, Pb, ph, pw)
                 else:
                     probs = eng.forward_nhwc_eval_split(x, Pb, ph, pw, softmax=True)
-                call("crimac_scatter_patches_multi", ptr(probs), probs.shape[1], ptr(misc), n, ptr(src, b0),
-                     ptr(cen, 2 * b0), Pb, ph, pw, overlap, SEABED_PAD, 1)
-            feed.computed()
-            pinned[k & 1][:2 * total].copy_(out[:2 * total], non_blocking=True)
-            events[k & 1].record()
+                call("crimac_scatter_patches_multi", ptr(probs), probs.shape[1], ptr(g.misc), g.n, ptr(g.src, b0),
+                     ptr(g.cen, 2 * b0), Pb, ph, pw, flow.overlap, SEABED_PAD, 1)
+            flow.feed.computed()
+            pinned[g.k & 1][:2 * g.total].copy_(out[:2 * g.total], non_blocking=True)
+            events[g.k & 1].record()
             if pending is not None:
                 yield from take(*pending)
-            pending = (group, offs, k & 1)
+            pending = (g.group, g.offs, g.k & 1)
         if pending is not None:
             yield from take(*pending)
 
@@ -1486,49 +1537,25 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
     """Test-set evaluation of a whole memm survey (``validate_model_survey_memm``, evaluate.py:84-117) on the tiled path:
     ``(hist_pos, hist_neg)`` int64 numpy [16384], the sum of ``evaluate_echogram_memm`` over ``echograms``.
 
-    The plan is ``predict_echograms_memm``'s: consecutive echograms form groups (``iter_memm_groups`` with every
-    echogram's own ``plan_eval_grid(..., memm=True)``; ``group_patches``, ``group_elems`` as there -- the int32 words of an
-    echogram's boxes count towards its share of the staging), all patches of a group form one patch list cut into forward
-    batches of ``max(batch_size, INTERNAL_BATCH)`` (``batch_size`` with a ``predict_fn``): only the last batch of a group
-    is short.  Reader threads copy the next groups' memmaps into pinned staging (``_ChunkFeed``), the copy stream uploads
-    and transposes them while the current group computes; nothing but the two histograms comes back.  Per batch:
+    Groups, batches, ``seabed``, metadata models, ``stats`` and ``kwargs``: ``_MemmSurveyFlow``, the plan of
+    ``predict_echograms_memm`` with every echogram's own ``plan_eval_grid(..., memm=True)`` -- the int32 words of an
+    echogram's boxes count towards its share of the staging.  Nothing but the two histograms comes back.  Per batch:
     ``crimac_gather_eval_crops_multi`` -> ``crimac_labels_test_transform_multi`` (-> ``crimac_labels_extend_mask_multi``
     with the group's box table, ``eval_boxes`` per echogram, for ``eval_mode`` 'region' / 'trace') -> network input
     (``crimac_gather_patches_memm_multi`` for 'all', ``crimac_gather_patches_memm_labels_multi`` for 'region' / 'trace',
-    as ``ChunkPredictor.evaluate`` chooses) -> ``eval_logits`` -> ``crimac_pr_histogram``; every kernel takes each
-    patch's source from the group's descriptor table.
+    as ``ChunkPredictor.evaluate`` chooses) -> ``eval_logits`` -> ``crimac_pr_histogram``.
 
-    ``seabed``: None, ``"estimate"`` or a callable ``echogram -> integer array [n_pings]``, as ``predict_echograms_memm``.
     ``hist`` (int32 [2, 16384] on the GPU): accumulate into it and return it, no collective (as
-    ``evaluate_echogram_memm``); None: ``finish_histograms`` -- with torch.distributed initialised the *groups* are dealt
-    round-robin to the ranks, the histograms all-reduced once, and every rank returns the survey's.
-    **Models with metadata planes** (``UNet_LateMetInject``, or metadata input channels) take the per-echogram path --
-    ``evaluate_echogram_memm`` for one echogram after the other (dealt to the ranks one by one), none of the packing; an
-    echogram larger than ``group_elems`` takes it too, in its place in the order.
+    ``evaluate_echogram_memm``); None: ``finish_histograms`` -- with several ranks the histograms are all-reduced once,
+    and every rank returns the survey's.
     ``on_batch(centres [P, 2] numpy, labels int16 [P, H, W], logits [P, 3, H, W])`` sees every batch; a callback that
-    declares the keyword ``echograms`` also gets the echogram of every patch of the batch (a list of P).
-    ``stats`` (a dict): receives ``groups``, ``batches`` (the patches of every packed forward batch),
-    ``fallback_echograms`` (per-echogram path: metadata model) and ``solo_echograms`` (too large for the staging).
-    ``kwargs``: the other keys of the reference's ``config_args`` are accepted and ignored; a near miss of one of this
-    function's own keywords is refused as a misspelling."""
-    _refuse_near_misses("evaluate_echograms_memm", kwargs,
-                        ("group_patches", "group_elems", "seabed", "stats", "predict_fn", "meta_channels", "eval_mode",
-                         "extend_size", "hist", "on_batch"))
-    _check_survey_seabed("evaluate_echograms_memm", seabed, "evaluate_echogram_memm")
-    if eval_mode not in ("all", "region", "trace"):
-        raise ValueError(f"eval_mode={eval_mode!r}: 'all', 'region' or 'trace' (batch/transforms.py:87)")
-    dev = segpipe.device
-    model = segpipe.model.to(dev).eval()
-    eng = model.infer_engine
-    C = len(segpipe.frequencies)
-    pw, ph = (int(v) for v in patch_size)
-    overlap = int(patch_overlap)
-    step = max(int(batch_size), INTERNAL_BATCH) if predict_fn is None else int(batch_size)
-    group_patches = MEMM_GROUP_BATCHES * step if group_patches is None else int(group_patches)
-    cap = MEMM_GROUP_ELEMS if group_elems is None else int(group_elems)
-    rank, world = parallel.rank_world()
-    stats = {} if stats is None else stats
-    stats.update(groups=0, batches=[], fallback_echograms=0, solo_echograms=0)
+    declares the keyword ``echograms`` also gets the echogram of every patch of the batch (a list of P)."""
+    flow = _MemmSurveyFlow("evaluate_echograms_memm",
+                           ("group_patches", "group_elems", "seabed", "stats", "predict_fn", "meta_channels", "eval_mode",
+                            "extend_size", "hist", "on_batch"),
+                           kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
+                           group_patches, group_elems, stats, eval_mode=eval_mode)
+    eng, dev, C, ph, pw = flow.eng, flow.dev, flow.C, flow.ph, flow.pw
     own = hist is None
     if own:
         hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=dev)
@@ -1549,67 +1576,41 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
     def done():
         return finish_histograms(hist) if own else hist
 
-    if eng.lmi or eng.in_channels > C:        # metadata planes: one echogram per group, the per-echogram path
-        for eg in shard_memm_groups(echograms, rank, world):
-            sb = None if seabed is None or isinstance(seabed, str) else _memm_survey_seabed(eg, seabed, dev)
-            stats["fallback_echograms"] += 1
-            single(eg, seabed if sb is None else sb, meta_channels)
+    if flow.alone:
+        for eg, sb in flow.each_alone():
+            single(eg, sb, meta_channels)
         return done()
 
-    record = functools.partial(_MemmEvalRecord, eval_mode=eval_mode, extend_size=extend_size)
-    groups = iter_memm_groups(echograms, patch_size, patch_overlap, group_patches, seabed, cap, rank, world, dev,
-                              record=record)
-    first = next(groups, None)
-    if first is None:                                # nothing to do on this rank: no staging
-        return done()
-    groups = itertools.chain([first], groups)
-    W = hip.MEMM_DESC_WORDS
-    stage = _MemmGroupStage(dev, C, cap, segpipe.frequencies)
     masked = eval_mode != "all"
 
-    def read(job, slot):
-        k, group = job
-        if group[0].elems > cap:                     # too large for the staging: evaluate_echogram_memm, nothing staged
-            return {}, (group, None, 0)
+    def tail(group, misc, at):                       # box_off [n + 1] | boxes [total][4]
+        off, rows = memm_box_table([r.boxes for r in group])
+        end = at + len(off) + rows.size
+        assert end <= len(misc), "memm group staging too small (boxes)"
+        misc[at:at + len(off)] = off
+        misc[at + len(off):end] = rows.reshape(-1)
+        return end
 
-        def tail(misc, at):                          # box_off [n + 1] | boxes [total][4]
-            off, rows = memm_box_table([r.boxes for r in group])
-            end = at + len(off) + rows.size
-            assert end <= stage.n_misc, "memm group staging too small (boxes)"
-            misc[at:at + len(off)] = off
-            misc[at + len(off):end] = rows.reshape(-1)
-            return end
-        uploads, offs, _, o_tail = stage.read(feed.bufs, slot(), k, group, tail=tail if masked else None)
-        return uploads, (group, offs, o_tail)
-
-    with _ChunkFeed(dev, ("memm-eval", C), stage.table, 3, enumerate(groups), read, extra=stage.extra) as feed:
-        eng.bind()
-        for k, (d, (group, offs, o_tail)) in enumerate(feed):
-            stats["groups"] += 1
-            if offs is None:                         # the per-echogram path, in its place in the order
-                feed.computed()
-                stats["solo_echograms"] += 1
-                single(group[0].echogram, group[0].seabed, None)
+    record = functools.partial(_MemmEvalRecord, eval_mode=eval_mode, extend_size=extend_size)
+    with flow.staged("memm-eval", record=record, tail=tail if masked else None) as groups:
+        for g in groups:
+            if g.offs is None:
+                single(g.group[0].echogram, g.group[0].seabed, None)
                 continue
-            n, P = len(group), sum(len(r.grid) for r in group)
-            stage.transpose(feed, k, d, group, offs)         # to the ping-major layout of the gather kernels
-            misc = d["misc"]
-            cen, src = misc[2 * W * n:], misc[2 * W * n + 2 * P:]
+            misc, n, P, cen, src = g.misc, g.n, g.P, g.cen, g.src
             cen64 = cen[:2 * P].view(P, 2).long()            # the label kernels take `center_coordinates` as int64
-            box_off, boxes = misc[o_tail:], misc[o_tail + n + 1:]
+            box_off, boxes = misc[g.o_tail:], misc[g.o_tail + n + 1:]
             if on_batch is not None:
-                cen_h = np.concatenate([np.asarray(r.grid, dtype=np.int32).reshape(-1, 2) for r in group])
-                egs_h = [r.echogram for r in group for _ in range(len(r.grid))]
-            for b0 in range(0, P, step):
-                Pb = min(step, P - b0)
-                stats["batches"].append(Pb)
+                cen_h = np.concatenate([np.asarray(r.grid, dtype=np.int32).reshape(-1, 2) for r in g.group])
+                egs_h = [r.echogram for r in g.group for _ in range(len(r.grid))]
+            for b0, Pb in flow.batches(P):
                 raw = eng._buf("eval.raw", (Pb, C, ph, pw), torch.float32)
                 lab = eng._buf("eval.lab", (Pb, ph, pw), torch.int16)
                 call("crimac_gather_eval_crops_multi", ptr(misc), n, ptr(src, b0), C, ptr(cen, 2 * b0), Pb, ph, pw,
                      ptr(raw), ptr(lab))
                 labels_t = torch.empty((Pb, ph, pw), dtype=torch.int16, device=dev)
                 call("crimac_labels_test_transform_multi", ptr(lab), lab.element_size(), ptr(raw), C - 1, 1e-7, 1e-4,
-                     ptr(cen64, 2 * b0), ptr(misc), n, ptr(src, b0), SEABED_PAD, overlap, ptr(labels_t), Pb, C, ph, pw)
+                     ptr(cen64, 2 * b0), ptr(misc), n, ptr(src, b0), SEABED_PAD, flow.overlap, ptr(labels_t), Pb, C, ph, pw)
                 x = eng._buf("tiled.x", (Pb * ph * pw, 16))
                 if masked:
                     call("crimac_labels_extend_mask_multi", ptr(labels_t), ptr(raw), C, ptr(cen64, 2 * b0), ptr(boxes),
@@ -1625,5 +1626,5 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
                 B, nc, H, Wd = logits.shape
                 call("crimac_pr_histogram", ptr(logits), nc, ptr(labels_t), labels_t.element_size(), B, H, Wd, ptr(hist[0]),
                      ptr(hist[1]))
-            feed.computed()
-        return done()
+            flow.feed.computed()
+    return done()
