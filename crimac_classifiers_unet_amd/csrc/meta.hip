@@ -244,8 +244,10 @@ __global__ __launch_bounds__(256) void meta_planes_kernel(MetaPlaneArgs a) {
     const int p = (int)(i / HW);
     const int rem = (int)(i - p * HW);
     const int y = rem / a.W, x = rem - y * a.W;
+    MetaPlaneSrc s = a.src;
+    if (!s.resolve(p)) continue;                 // (the table form: a patch without a source is skipped; no barrier here)
     float v[CRIMAC_MAX_META_PLANES];
-    meta_plane_values(a.src, a.centres[2 * p], a.centres[2 * p + 1], a.H, a.W, y, x, v);
+    meta_plane_values(s, a.centres[2 * p], a.centres[2 * p + 1], a.H, a.W, y, x, v);
     float* o = a.out + ((long)p * a.Cm) * HW + rem;
     for (int c = 0; c < a.Cm; ++c) o[c * HW] = v[c];
   }
@@ -314,19 +316,32 @@ extern "C" int crimac_meta_bwd(const float* dlogits, const float* meta, int Cm, 
 // reference's Dataset builds per patch in numpy DataLoader workers, built on the GPU from the echogram's three per-ping
 // vectors.  flags: bit 0 portion_year, 1 portion_day (two planes: sin, cos), 2 time_diff, 3 depth_rel,
 // 4 depth_abs_surface, 5 depth_abs_seabed; the planes come out in that order, out [P][Cm][H][W] fp32.
-extern "C" int crimac_meta_planes(const int* centres, int P, int H, int W, int flags, double portion_year,
-                                  const double* portion_day, int n_day, const double* time_diff, int n_td,
-                                  const long long* seabed, int n_sb, float* out, void* stream) {
-  CRIMAC_REQUIRE(centres && out && P > 0 && H > 0 && W > 0 && flags > 0 && flags < 64, "meta_planes: bad arguments");
-  CRIMAC_REQUIRE(!(flags & 2) || (portion_day && n_day > 0), "meta_planes: portion_day needs its vector");
-  CRIMAC_REQUIRE(!(flags & 4) || (time_diff && n_td > 0), "meta_planes: time_diff needs its vector");
-  CRIMAC_REQUIRE(!(flags & 56) || (seabed && n_sb > 0), "meta_planes: the depth planes need the seabed vector");
-  MetaPlaneArgs a{centres, P, H, W, MetaPlaneSrc{flags, portion_year, portion_day, n_day, time_diff, n_td, seabed, n_sb},
-                  out, meta_plane_count(flags)};
+static int meta_planes_run(const char* name, const MetaPlaneSrc& m, const int* centres, int P, int H, int W, float* out,
+                           void* stream) {
+  CRIMAC_REQUIRE(centres && out && P > 0 && H > 0 && W > 0 && m.flags > 0 && m.flags < 64, "%s: bad arguments", name);
+  CRIMAC_REQUIRE(m.metas || !(m.flags & 2) || (m.portion_day && m.n_day > 0), "%s: portion_day needs its vector", name);
+  CRIMAC_REQUIRE(m.metas || !(m.flags & 4) || (m.time_diff && m.n_td > 0), "%s: time_diff needs its vector", name);
+  CRIMAC_REQUIRE(m.metas || !(m.flags & 56) || (m.seabed && m.n_sb > 0), "%s: the depth planes need the seabed vector", name);
+  MetaPlaneArgs a{centres, P, H, W, m, out, meta_plane_count(m.flags)};
   const long total = (long)P * H * W;
   long blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(meta_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
+}
+
+extern "C" int crimac_meta_planes(const int* centres, int P, int H, int W, int flags, double portion_year,
+                                  const double* portion_day, int n_day, const double* time_diff, int n_td,
+                                  const long long* seabed, int n_sb, float* out, void* stream) {
+  return meta_planes_run("meta_planes", MetaPlaneSrc{flags, portion_year, portion_day, n_day, time_diff, n_td, seabed, n_sb},
+                         centres, P, H, W, out, stream);
+}
+
+// crimac_meta_planes for batches that span memmap echograms: the scalar and the vectors of patch p from metas[src[p]].
+extern "C" int crimac_meta_planes_multi(const crimac_memm_meta_desc* metas, int n_desc, const int* src, const int* centres,
+                                        int P, int H, int W, int flags, float* out, void* stream) {
+  CRIMAC_REQUIRE(metas && src && n_desc > 0, "meta_planes_multi: needs the metadata table and src");
+  return meta_planes_run("meta_planes_multi", MetaPlaneSrc{flags, 0.0, nullptr, 0, nullptr, 0, nullptr, 0, metas, n_desc, src},
+                         centres, P, H, W, out, stream);
 }

@@ -1,6 +1,7 @@
 // Per-pixel metadata planes of a crop (reference batch/dataset.py:288-351, get_crop_memmap), shared by
 // crimac_meta_planes (meta.hip: [P][Cm][H][W] planes for UNet_LateMetInject) and crimac_gather_patches_memm_meta
-// (tiling.hip: the planes as extra INPUT channels of the gathered NHWC crop) so that the two cannot drift apart.
+// (tiling.hip: the planes as extra INPUT channels of the gathered NHWC crop) so that the two cannot drift apart -- and by
+// their _multi forms, which take the scalar and the vectors of patch p from a table (MetaPlaneSrc::resolve).
 //
 // Seven planes at most, every one a function of the crop centre and of three per-ping vectors of the echogram:
 //   portion_year      : the echogram's scalar
@@ -11,6 +12,7 @@
 // DATA crop's grid (getGrid: c - (w + 1) // 2 + 1 ...): reproduced, not "fixed".  The reference computes in float64 and the
 // batch is cast to float32 by SegPipe.predict_batch (.float()): the same here (double arithmetic, one rounding).
 #pragma once
+#include "../../include/crimac_memm_meta.h"
 
 constexpr int CRIMAC_MAX_META_PLANES = 7;
 
@@ -20,7 +22,26 @@ struct MetaPlaneSrc {
   const double* portion_day; int n_day;
   const double* time_diff; int n_td;
   const long long* seabed; int n_sb;
+  // metas != NULL (batches that span memmap echograms): src[p] picks patch p's crimac_memm_meta_desc from a device-resident
+  // table -- the one PatchSrc's src indexes (tiling.hip) -- and the scalar and the three vectors are that echogram's.
+  const crimac_memm_meta_desc* metas; int n_desc; const int* src;
+  // false: patch p has no source -- src[p] names no descriptor, or the descriptor lacks a vector the flags need -- and is
+  // skipped, nothing of it is read.  The scalar form (metas == NULL) was checked by the host.
+  __device__ __forceinline__ bool resolve(int p) {
+    if (!metas) return true;
+    const int i = src[p];
+    if (i < 0 || i >= n_desc) return false;
+    const crimac_memm_meta_desc d = metas[(long)i];
+    portion_year = d.portion_year;
+    portion_day = d.portion_day; n_day = meta_len(d.n_day);
+    time_diff = d.time_diff; n_td = meta_len(d.n_td);
+    seabed = d.seabed; n_sb = meta_len(d.n_sb);
+    return (!(flags & 2) || (portion_day && n_day > 0)) && (!(flags & 4) || (time_diff && n_td > 0)) &&
+           (!(flags & 56) || (seabed && n_sb > 0));
+  }
+  __device__ __forceinline__ static int meta_len(long long n) { return n > 2147483647ll ? 2147483647 : (int)n; }
 };
+static_assert(sizeof(crimac_memm_meta_desc) == 56, "crimac_memm_meta_desc: seven 64-bit fields (hip.MEMM_META_WORDS)");
 
 __host__ __device__ inline int meta_plane_count(int flags) {
   return (flags & 1) + 2 * ((flags >> 1) & 1) + ((flags >> 2) & 1) + ((flags >> 3) & 1) + ((flags >> 4) & 1) +

@@ -42,6 +42,8 @@ struct PatchSrc {
   }
   bool ok() const { return descs ? src && n_desc > 0 : data && Wd > 0 && H > 0; }      // (host: the launchers' check)
 };
+// meta.metas != NULL (crimac_gather_patches_memm_meta_multi): the metadata vectors of patch p come from a second table,
+// indexed by the same src[p] and resolved where `from` is, uniformly over the block.
 struct GatherSrc { PatchSrc from; int db_scaled; MetaPlaneSrc meta; const int* meta_centres; };
 
 // data [C][Wd][H] fp32; centres [P][2] = (cy, cx_local) with cx_local relative to the chunk slice.
@@ -135,6 +137,7 @@ __global__ __launch_bounds__(256) void gather_patches_kernel(GatherSrc g, int C,
                                                              const short* __restrict__ patch_labels) {
   PatchSrc& s = g.from;
   if (!s.resolve(blockIdx.z)) return;                      // (uniform over the block: nobody waits at the barrier)
+  if (g.meta.flags && !g.meta.resolve(blockIdx.z)) return; // (so is this)
   gather_patch_tile<T, PATCH_LABELS>(s.data, C, s.Wd, s.H, centres, ph, pw, out, ld, PATCH_LABELS ? nullptr : s.labels,
                                      g.db_scaled, g.meta, g.meta_centres, patch_labels);
 }
@@ -411,9 +414,10 @@ static int gather_run(const char* name, int prec, const GatherSrc& g, int C, con
   CRIMAC_REQUIRE(P <= 65535, "%s: at most 65535 patches per call", name);
   CRIMAC_REQUIRE(m.flags >= 0 && m.flags < 64, "%s: bad metadata flags %d", name, m.flags);
   CRIMAC_REQUIRE(!m.flags || g.meta_centres, "%s: metadata planes need the global centres", name);
-  CRIMAC_REQUIRE(!(m.flags & 2) || (m.portion_day && m.n_day > 0), "%s: portion_day needs its vector", name);
-  CRIMAC_REQUIRE(!(m.flags & 4) || (m.time_diff && m.n_td > 0), "%s: time_diff needs its vector", name);
-  CRIMAC_REQUIRE(!(m.flags & 56) || (m.seabed && m.n_sb > 0), "%s: the depth planes need the seabed vector", name);
+  // (the table form: a descriptor that lacks a vector the flags need makes its patches skipped, MetaPlaneSrc::resolve)
+  CRIMAC_REQUIRE(m.metas || !(m.flags & 2) || (m.portion_day && m.n_day > 0), "%s: portion_day needs its vector", name);
+  CRIMAC_REQUIRE(m.metas || !(m.flags & 4) || (m.time_diff && m.n_td > 0), "%s: time_diff needs its vector", name);
+  CRIMAC_REQUIRE(m.metas || !(m.flags & 56) || (m.seabed && m.n_sb > 0), "%s: the depth planes need the seabed vector", name);
   CRIMAC_REQUIRE(C + meta_plane_count(m.flags) <= ld, "%s: %d data + %d metadata channels do not fit ld=%ld", name, C,
                  meta_plane_count(m.flags), ld);
   dim3 grid((pw + TS - 1) / TS, (ph + TS - 1) / TS, P);
@@ -484,6 +488,19 @@ extern "C" int crimac_gather_patches_memm_labels_multi(int prec, const crimac_me
   CRIMAC_REQUIRE(patch_labels, "gather_patches_memm_labels_multi: needs the transformed labels of the patches (border rule)");
   return gather_run("gather_patches_memm_labels_multi", prec, GatherSrc{{nullptr, 0, 0, nullptr, descs, n_desc, src}}, C,
                     centres, P, ph, pw, out, ld, stream, patch_labels);
+}
+
+// crimac_gather_patches_memm_meta / _labels (patch_labels given) for batches that span memmap echograms: the metadata
+// sources in a second table, parallel to the first; an echogram is its own chunk, so meta_centres are the centres.
+extern "C" int crimac_gather_patches_memm_meta_multi(int prec, const crimac_memm_desc* descs,
+                                                     const crimac_memm_meta_desc* metas, int n_desc, const int* src, int C,
+                                                     const int* centres, int P, int ph, int pw, void* out, long ld,
+                                                     const short* patch_labels, int db_scaled, int flags, void* stream) {
+  CRIMAC_REQUIRE(descs && metas, "gather_patches_memm_meta_multi: needs the descriptor table and the metadata table");
+  CRIMAC_REQUIRE(flags > 0, "gather_patches_memm_meta_multi: bad metadata arguments (flags=%d: no plane)", flags);
+  const MetaPlaneSrc meta{flags, 0.0, nullptr, 0, nullptr, 0, nullptr, 0, metas, n_desc, src};
+  return gather_run("gather_patches_memm_meta_multi", prec, GatherSrc{{nullptr, 0, 0, nullptr, descs, n_desc, src},
+                    db_scaled ? 1 : 0, meta, centres}, C, centres, P, ph, pw, out, ld, stream, patch_labels);
 }
 
 extern "C" int crimac_scatter_patches_ex(const float* probs, int ncls, const int* centres, int P, int ph, int pw,

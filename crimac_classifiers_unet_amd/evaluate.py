@@ -98,13 +98,15 @@ def validate_model_survey_memm(readers, segpipe, meta_channels, patch_size, patc
     """evaluate.py:84-117: one gridded Dataset per echogram, concatenated -> PR curve / F1 of the survey.
     ``tiled=True``: the whole survey on the tiled GPU path (``tiled_inference.evaluate_echograms_memm``: forward batches
     packed across the echograms, one feed; with several ranks the groups of echograms are dealt to the ranks and the
-    histograms all-reduced once; a model with metadata planes goes echogram by echogram); no factory is needed."""
+    histograms all-reduced once; a model with metadata planes goes echogram by echogram unless ``pack_metadata=True`` is
+    among ``kwargs``); no factory is needed."""
     if tiled:
         from .tiled_inference import evaluate_echograms_memm
         if not segpipe.model_is_loaded:
             segpipe.load_model_params()
         hp, hn = evaluate_echograms_memm(readers, segpipe, patch_size, patch_overlap, batch_size, eval_mode=eval_mode,
-                                         meta_channels=meta_channels or None)
+                                         meta_channels=meta_channels or None,
+                                         **{k: kwargs[k] for k in ("pack_metadata",) if k in kwargs})
         return _tiled_metrics(segpipe, hp, hn, save_path_metrics, save_path_plot, survey)
     dataset_cls, dtf, ltf = _reference_factories(dataset_cls, data_transform_factory, label_transform_factory, True)
     frequencies = segpipe.frequencies

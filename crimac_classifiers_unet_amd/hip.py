@@ -78,7 +78,8 @@ def parse_header(text: str):
     """The C ABI as include/crimac_unet_hip.h states it: (prototypes, structs, defines).
     prototypes: name -> (restype, argtypes, takes_stream), takes_stream = the last parameter is ``void* stream``;
     structs: tag -> [(field, ctype)] in declaration order; defines: every ``#define CRIMAC_<NAME> <integer expression>``,
-    evaluated in order.  A declaration this does not recognise raises HipLibraryError naming it: it never guesses."""
+    evaluated in order (``typedef struct crimac_x crimac_x;`` only names a struct that another header lays out: nothing
+    to record).  A declaration this does not recognise raises HipLibraryError naming it: it never guesses."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S).replace("\\\n", " ")
     protos, structs, defines = {}, {}, {}
     for line in re.findall(r"^[ \t]*(#.*?)\s*$", text, flags=re.M):
@@ -110,6 +111,8 @@ def parse_header(text: str):
     if not body:
         raise HipLibraryError('the declarations are not one `extern "C" { ... }` block')
     for stmt in filter(None, map(str.strip, body.group(1).split(";"))):
+        if re.fullmatch(r"typedef\s+struct\s+(crimac_\w+)\s+\1", stmt):      # names a struct that another header lays out
+            continue
         m = re.fullmatch(r"(int|const\s+char\s*\*)\s*(crimac_\w+)\s*\((.*)\)", stmt, flags=re.S)
         if not m:
             raise HipLibraryError(f"cannot parse the declaration `{' '.join(stmt.split())}`")
@@ -123,8 +126,10 @@ def parse_header(text: str):
 try:
     with open(_build.HEADER) as _header:
         PROTOTYPES, STRUCTS, DEFINES = parse_header(_header.read())
+    with open(_build.MEMM_META_HEADER) as _header:          # (crimac_unet_hip.h names its struct, this one lays it out)
+        MEMM_META_STRUCTS = parse_header(_header.read())[1]
 except OSError as e:
-    raise HipLibraryError(f"cannot read the C-ABI header {_build.HEADER} ({e}): the binding is derived from it, so the "
+    raise HipLibraryError(f"cannot read the C-ABI header {e.filename} ({e.strerror}): the binding is derived from it, so the "
                           "package needs include/ next to it (also with a CRIMAC_LIB override)") from None
 del _header
 
@@ -152,6 +157,17 @@ class MemmDesc(C.Structure):
 if any(C.sizeof(t) != 8 for _, t in MemmDesc._fields_):
     raise HipLibraryError("crimac_memm_desc has a field that is not 64 bits wide: the host writes the table as int64 words")
 MEMM_DESC_WORDS = C.sizeof(MemmDesc) // 8      # data, labels, seabed, out (device addresses), n_pings, n_range
+
+
+class MemmMetaDesc(C.Structure):
+    """crimac_memm_meta_desc (include/crimac_memm_meta.h): the metadata source of one echogram of a multi-source launch."""
+    _fields_ = MEMM_META_STRUCTS["crimac_memm_meta_desc"]
+
+
+if any(C.sizeof(t) != 8 for _, t in MemmMetaDesc._fields_):
+    raise HipLibraryError("crimac_memm_meta_desc has a field that is not 64 bits wide: the host writes the table as 64-bit "
+                          "words")
+MEMM_META_WORDS = C.sizeof(MemmMetaDesc) // 8      # portion_year (float64), then (device address, length) of three vectors
 
 WGRAD_GROUP_MAX_LAYERS = 16      # CRIMAC_WGRAD_GROUP_MAX_LAYERS
 MASK_PER_PATCH = -2147483648      # CRIMAC_MASK_PER_PATCH

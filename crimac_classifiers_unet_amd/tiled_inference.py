@@ -73,18 +73,23 @@ META_FLAGS = {"portion_year": 1, "portion_day": 2, "time_diff": 4, "depth_rel": 
               "depth_abs_seabed": 32}          # planes come out in this order (batch/dataset.py:288-351)
 
 
+def meta_flags(meta_channels):
+    """The yaml's ``meta_channels`` dict -> (the `flags` of the metadata kernels, the number of planes they build)."""
+    if set(meta_channels) != set(META_FLAGS) or not all(isinstance(v, bool) for v in meta_channels.values()):
+        raise ValueError(f"meta_channels must be a dict of booleans with the keys {sorted(META_FLAGS)}")    # dataset.py:60-66
+    flags = sum(f for k, f in META_FLAGS.items() if meta_channels[k])
+    if flags == 0:
+        raise ValueError("no metadata channel is switched on")
+    return flags, sum((2 if k == "portion_day" else 1) for k in META_FLAGS if meta_channels[k])
+
+
 class MetaSource:
     """The per-ping vectors the metadata planes of an echogram are built from (data_reader.py:98-100), resident on the
     GPU: ``crimac_meta_planes`` turns them into the ``[P, Cm, H, W]`` planes of a batch of crops -- what the reference's
     ``get_crop_memmap`` builds per patch in numpy DataLoader workers (batch/dataset.py:288-351)."""
 
     def __init__(self, meta_channels, portion_year, portion_day_vector, time_vector_diff, seabed, device):
-        if set(meta_channels) != set(META_FLAGS) or not all(isinstance(v, bool) for v in meta_channels.values()):
-            raise ValueError(f"meta_channels must be a dict of booleans with the keys {sorted(META_FLAGS)}")    # dataset.py:60-66
-        self.flags = sum(f for k, f in META_FLAGS.items() if meta_channels[k])
-        if self.flags == 0:
-            raise ValueError("no metadata channel is switched on")
-        self.n_planes = sum((2 if k == "portion_day" else 1) for k in META_FLAGS if meta_channels[k])
+        self.flags, self.n_planes = meta_flags(meta_channels)
         self.portion_year = float(portion_year)
 
         def dev(a, dt):
@@ -986,6 +991,7 @@ def predict_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_si
 MEMM_GROUP_BATCHES = 4            # default ``group_patches``: this many forward batches per group
 MEMM_GROUP_ELEMS = 1 << 24        # pixels (range x pings) a group stages at most: 268 MB of fp32 planes at 4 frequencies
 MEMM_MISC_SHARE = 8               # the int32 staging (descriptors, centres, src, seabed lines) is 1 / 8 of the pixels
+MEMM_META_SHARE = 4               # the 64-bit staging of packed metadata (table, three vectors per echogram): 1 / 4 of them
 
 
 def plan_memm_groups(items, group_patches, max_elems=None, key=None):
@@ -1020,9 +1026,13 @@ def shard_memm_groups(groups, rank, world):
 
 
 class _MemmRecord:
-    """One echogram of a memm survey as the planner sees it: extents, seabed line, patch grid."""
+    """One echogram of a memm survey as the planner sees it: extents, seabed line, patch grid.  ``meta`` (the flow packs
+    metadata): + its metadata source as ``_MemmGroupStage`` stages it, ``(portion_of_year_scalar, portion_of_day_vector
+    float64, time_vector_diff float64, seabed int64)`` -- the seabed vector being the one ``_load_echogram_memm`` hands to
+    ``MetaSource.from_echogram``: the reader's ``_seabed`` when the survey's ``seabed`` argument is None (``own_seabed``),
+    else the line estimated / called, ``seabed``.  Its 64-bit words count towards the echogram's share of the staging."""
 
-    def __init__(self, echogram, seabed, patch_size, patch_overlap):
+    def __init__(self, echogram, seabed, patch_size, patch_overlap, meta=False, own_seabed=True):
         self.echogram = echogram
         self.n_range, self.n_pings = (int(v) for v in echogram.shape)
         self.seabed = seabed
@@ -1030,6 +1040,14 @@ class _MemmRecord:
         self.pixels = self.n_range * self.n_pings
         # what the echogram takes of a group's staging: its pixels, or -- a sliver with many pings -- its int32 words
         self.elems = max(self.pixels, MEMM_MISC_SHARE * (2 * hip.MEMM_DESC_WORDS + 3 * len(self.grid) + self.n_pings))
+        self.meta, self.meta_words = None, 0
+        if meta:
+            def vec(a, dt):
+                return np.ascontiguousarray(np.asarray(a)).astype(dt).reshape(-1)
+            self.meta = (float(echogram.portion_of_year_scalar), vec(echogram.portion_of_day_vector, np.float64),
+                         vec(echogram.time_vector_diff, np.float64), vec(echogram._seabed if own_seabed else seabed, np.int64))
+            self.meta_words = hip.MEMM_META_WORDS + sum(len(v) for v in self.meta[1:])
+            self.elems = max(self.elems, MEMM_META_SHARE * self.meta_words)
 
     def key(self):
         return len(self.grid), self.elems
@@ -1070,7 +1088,8 @@ def iter_memm_groups(echograms, patch_size, patch_overlap, group_patches, seabed
     this rank's own groups only: the groups and their owners are planned over the whole input, which is the same on every
     rank, so what one rank skips -- files another rank is writing meanwhile -- cannot move an echogram to another rank or
     to none.  A group of which nothing is left is dropped.
-    ``record``: the record class (``evaluate_echograms_memm`` plans with ``_MemmEvalRecord``, which carries the boxes)."""
+    ``record``: the record class (``evaluate_echograms_memm`` plans with ``_MemmEvalRecord``, which carries the boxes; a flow
+    that packs metadata binds ``meta`` / ``own_seabed`` to it)."""
     records = (record(eg, _memm_survey_seabed(eg, seabed, device), patch_size, patch_overlap) for eg in echograms)
     mine = shard_memm_groups(plan_memm_groups(records, group_patches, max_elems, key=_MemmRecord.key), rank, world)
     if skip is None:
@@ -1101,12 +1120,18 @@ class _MemmGroupStage:
     buffers (``cap`` pixels of ``C`` planes and of labels, ``n_misc`` int32 words), the transposed planes per device slot
     (``extra``), the reader thread's copy of a group into a pinned slot (``read``) and the transposes on the copy stream
     (``transpose``).  ``misc`` holds, in this order: the descriptor table int64 [n][MEMM_DESC_WORDS] | the centres int32
-    [P][2] | src int32 [P] | the seabed lines | the caller's tail."""
+    [P][2] | src int32 [P] | the seabed lines | the caller's tail.
+    ``meta`` (the flow packs metadata; the records carry ``.meta``): + the buffer ``meta`` of ``n_meta`` 64-bit words, held
+    as float64 and written through int64 / float64 views: the table [n][MEMM_META_WORDS] (crimac_memm_meta_desc) | per
+    echogram portion_of_day_vector | time_vector_diff | the int64 seabed vector.  It travels in the group's pinned upload."""
 
-    def __init__(self, dev, C, cap, frequencies):
-        self.dev, self.C, self.cap, self.frequencies = dev, C, cap, frequencies
+    def __init__(self, dev, C, cap, frequencies, meta=False):
+        self.dev, self.C, self.cap, self.frequencies, self.meta = dev, C, cap, frequencies, bool(meta)
         self.n_misc = cap // MEMM_MISC_SHARE + 2 * hip.MEMM_DESC_WORDS
         self.table = {"data": (C * cap, torch.float32), "lab": (cap, torch.int16), "misc": (self.n_misc, torch.int32)}
+        if self.meta:
+            self.n_meta = cap // MEMM_META_SHARE + hip.MEMM_META_WORDS
+            self.table["meta"] = (self.n_meta, torch.float64)
 
     def extra(self):
         return {"data_t": [torch.empty(self.C * self.cap, dtype=torch.float32, device=self.dev) for _ in range(2)],
@@ -1142,8 +1167,26 @@ class _MemmGroupStage:
         if tail is not None:
             o_sb = tail(group, misc, o_sb)
             assert o_tail <= o_sb <= self.n_misc, "memm group staging too small"
-        return ({"data": host["data"][:C * off], "lab": host["lab"][:off], "misc": host["misc"][:o_sb]},
-                offs, off, o_tail)
+        uploads = {"data": host["data"][:C * off], "lab": host["lab"][:off], "misc": host["misc"][:o_sb]}
+        if self.meta:
+            uploads["meta"] = host["meta"][:self._read_meta(host["meta"].numpy(), bufs["dev"][k & 1]["meta"].data_ptr(),
+                                                            group)]
+        return uploads, offs, off, o_tail
+
+    def _read_meta(self, words, base, group):
+        """The metadata table and vectors of ``group`` into ``words`` (float64 view of the pinned slot); the descriptors
+        point into the device copy at ``base``, as the seabed lines of ``misc`` do.  Returns the words written."""
+        M, n = hip.MEMM_META_WORDS, len(group)
+        ints = words.view(np.int64)
+        at = M * n
+        for i, r in enumerate(group):
+            assert at + r.meta_words - M <= self.n_meta, "memm group staging too small (metadata)"
+            words[M * i] = r.meta[0]
+            for j, v in enumerate(r.meta[1:]):
+                ints[M * i + 1 + 2 * j:M * i + 3 + 2 * j] = (base + 8 * at, len(v))
+                (ints if v.dtype == np.int64 else words)[at:at + len(v)] = v
+                at += len(v)
+        return at
 
     def transpose(self, feed, k, d, group, offs):
         """The uploaded planes of group ``k`` to the ping-major layout of the gather kernels, on the copy stream; the
@@ -1175,9 +1218,13 @@ class _MemmSurveyFlow:
     ``seabed``: None (the reader's ``get_seabed``), ``"estimate"`` (``estimate_seabed_memm`` per echogram) or a callable
     ``echogram -> integer array [n_pings]``; not an array, which belongs to one echogram.
     **Models with metadata planes** (``UNet_LateMetInject``, or metadata input channels): the metadata sources are per
-    echogram and the metadata kernels read one source, so these models take the per-echogram path (``alone``,
-    ``each_alone``): the caller's single-echogram sibling for one echogram after the other; same interface, same results,
-    none of the packing.  An echogram larger than ``group_elems`` takes that path too, in its place in the order.
+    echogram.  By default these models take the per-echogram path (``alone``, ``each_alone``): the caller's
+    single-echogram sibling for one echogram after the other; same interface, same results, none of the packing.
+    ``pack_metadata=True`` (opt-in; no effect on a model without metadata) packs them like any other model: the group's
+    metadata table and vectors go up with it (``_MemmGroupStage``), and ``crimac_gather_patches_memm_meta_multi`` (input
+    channels) / ``crimac_meta_planes_multi`` (late injection) take each patch's scalar and vectors from that table.  It
+    needs ``meta_channels``, whose planes must be the model's.
+    An echogram larger than ``group_elems`` takes the per-echogram path, in its place in the order.
     Multi-GPU (torch.distributed initialised): the *groups* (``alone``: the echograms) are dealt round-robin to the ranks.
     ``skip(echogram) -> bool``: echograms to leave out; it is asked after the groups have been planned and dealt over the
     WHOLE input (``iter_memm_groups``), so every echogram keeps its rank whatever the ranks skip.
@@ -1188,7 +1235,7 @@ class _MemmSurveyFlow:
     ...) is refused as a misspelling.  The checks come before anything is read."""
 
     def __init__(self, name, own, kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
-                 group_patches, group_elems, stats, skip=None, eval_mode=None):
+                 group_patches, group_elems, stats, skip=None, eval_mode=None, meta_channels=None, pack_metadata=False):
         _refuse_near_misses(name, kwargs, own)
         _check_survey_seabed(name, seabed, name.replace("echograms", "echogram"))
         if eval_mode not in (None, "all", "region", "trace"):
@@ -1204,7 +1251,37 @@ class _MemmSurveyFlow:
         self.rank, self.world = parallel.rank_world()
         self.stats = {} if stats is None else stats
         self.stats.update(groups=0, batches=[], fallback_echograms=0, solo_echograms=0)
-        self.alone = self.eng.lmi or self.eng.in_channels > self.C     # metadata planes: the per-echogram path
+        eng = self.eng
+        self.early = not eng.lmi and eng.in_channels > self.C            # metadata planes as extra input channels
+        self.pack = (eng.lmi or self.early) and bool(pack_metadata)     # ... packed across echograms
+        self.alone = (eng.lmi or self.early) and not self.pack          # ... or the per-echogram path
+        self.meta_channels, self.flags = meta_channels, 0
+        if self.pack:
+            if not meta_channels and self.early:
+                raise ValueError(f"the model takes {eng.in_channels} input channels for {self.C} frequencies "
+                                 "(metadata planes as input channels): pass meta_channels")
+            if not meta_channels:
+                raise ValueError("a UNet_LateMetInject model needs the metadata planes: pass meta_channels")
+            self.flags, n_planes = meta_flags(meta_channels)
+            takes = eng.meta_channels if eng.lmi else eng.in_channels - self.C
+            if n_planes != takes:
+                raise ValueError(f"the model takes {takes} metadata {'planes' if eng.lmi else 'input channels'}, "
+                                 f"meta_channels builds {n_planes}")
+
+    def solo(self, r):
+        """``(seabed, meta_channels)`` of the single-echogram call for record ``r``, an echogram too large for the staging.
+        With packed metadata the call must build the ``MetaSource`` a direct call would: the caller's None stays None (the
+        depth planes then go by the reader's ``_seabed``), an estimated / called line is given as the array it is."""
+        if self.pack:
+            return (None if self.seabed is None else r.seabed), self.meta_channels
+        return r.seabed, None
+
+    def meta_planes(self, g, b0, Pb):
+        """Late injection: the metadata planes float32 [Pb, Cm, ph, pw] of the batch at ``b0`` of staged group ``g``."""
+        out = torch.empty((Pb, self.eng.meta_channels, self.ph, self.pw), dtype=torch.float32, device=self.dev)
+        call("crimac_meta_planes_multi", ptr(g.meta), g.n, ptr(g.src, b0), ptr(g.cen, 2 * b0), Pb, self.ph, self.pw,
+             self.flags, ptr(out))
+        return out
 
     def each_alone(self):
         """This rank's echograms, one per "group", each with the ``seabed`` argument of the single-echogram functions."""
@@ -1227,10 +1304,12 @@ class _MemmSurveyFlow:
         namespace -- ``k``, ``group`` (the records), ``offs`` (the pixel offset of every echogram; None: ONE echogram too
         large for the staging, nothing staged, the caller takes the per-echogram path), ``total`` (pixels), ``n`` / ``P``
         (echograms / patches), ``misc`` (the int32 staging) with its views ``cen`` [P][2] and ``src`` [P], ``o_tail``
-        (where the caller's tail starts).  The caller enqueues the group's ``batches(P)`` and then calls
+        (where the caller's tail starts), ``meta`` (packed metadata: the 64-bit staging, the table first).  The caller enqueues the group's ``batches(P)`` and then calls
         ``feed.computed()`` (done already for a group too large).  Nothing is allocated for an empty plan.
         ``extra()``: the caller's buffers next to the stage's; ``out``: the name of the one the descriptors' ``out``
         point into; ``tail(group, misc, at) -> end`` writes the caller's words behind the seabed lines."""
+        if self.pack:
+            record = functools.partial(record, meta=True, own_seabed=self.seabed is None)
         groups = iter_memm_groups(self.echograms, self.patch_size, self.patch_overlap, self.group_patches, self.seabed,
                                   self.cap, self.rank, self.world, self.dev, self.skip, record)
         first = next(groups, None)
@@ -1238,7 +1317,7 @@ class _MemmSurveyFlow:
             yield iter(())
             return
         groups = itertools.chain([first], groups)
-        stage = _MemmGroupStage(self.dev, self.C, self.cap, self.frequencies)
+        stage = _MemmGroupStage(self.dev, self.C, self.cap, self.frequencies, meta=self.pack)
 
         def read(job, slot):
             k, group = job
@@ -1264,26 +1343,30 @@ class _MemmSurveyFlow:
             else:
                 g.n, g.P = len(group), sum(len(r.grid) for r in group)
                 stage.transpose(feed, k, d, group, offs)         # to the ping-major layout of the gather kernels
-                g.misc = d["misc"]
+                g.misc, g.meta = d["misc"], d.get("meta")
                 g.cen, g.src = g.misc[2 * W * g.n:], g.misc[2 * W * g.n + 2 * g.P:]
             yield g
 
 
 def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn=None, meta_channels=None,
-                           seabed=None, group_patches=None, stats=None, group_elems=None, skip=None, **kwargs):
+                           seabed=None, group_patches=None, stats=None, group_elems=None, skip=None, pack_metadata=False,
+                           **kwargs):
     """``save_reader_predictions_memm`` (save_predict.py:222-265) for a whole memm survey -- a directory of many small
     echograms: a generator of ``(echogram, float64 [2, n_range, n_pings])`` in input order, every array equal to
     ``predict_echogram_memm`` of that echogram (probabilities rounded to float16 on the GPU, then widened); each rank
     yields the echograms of its own groups only, no collective.
 
-    Groups, batches, ``seabed``, metadata models, ``skip`` (``save_predictions_memm``'s resume rule), ``stats`` and
-    ``kwargs``: ``_MemmSurveyFlow``.  Per batch ``crimac_gather_patches_memm_multi`` -> forward ->
-    ``crimac_scatter_patches_multi``; the float16 results of a group leave through a non-blocking download into a ring of
+    Groups, batches, ``seabed``, metadata models and ``pack_metadata``, ``skip`` (``save_predictions_memm``'s resume rule),
+    ``stats`` and ``kwargs``: ``_MemmSurveyFlow``.  Per batch ``crimac_gather_patches_memm_multi`` (packed metadata input
+    channels: ``crimac_gather_patches_memm_meta_multi``) -> forward (packed late injection: with the planes of
+    ``crimac_meta_planes_multi``) -> ``crimac_scatter_patches_multi``; the float16 results of a group leave through a non-blocking download into a ring of
     two pinned buffers."""
     flow = _MemmSurveyFlow("predict_echograms_memm",
-                           ("group_patches", "group_elems", "seabed", "skip", "stats", "predict_fn", "meta_channels"),
+                           ("group_patches", "group_elems", "seabed", "skip", "stats", "predict_fn", "meta_channels",
+                            "pack_metadata"),
                            kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
-                           group_patches, group_elems, stats, skip=skip)
+                           group_patches, group_elems, stats, skip=skip, meta_channels=meta_channels,
+                           pack_metadata=pack_metadata)
     eng, C, ph, pw, cap = flow.eng, flow.C, flow.ph, flow.pw, flow.cap
 
     def single(eg, sb, meta):            # the per-echogram path
@@ -1315,15 +1398,21 @@ def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_
                 if pending is not None:
                     yield from take(*pending)
                     pending = None
-                yield single(g.group[0].echogram, g.group[0].seabed, None)
+                yield single(g.group[0].echogram, *flow.solo(g.group[0]))
                 continue
             out[:2 * g.total].zero_()
             for b0, Pb in flow.batches(g.P):
                 x = eng._buf("tiled.x", (Pb * ph * pw, 16))
-                call("crimac_gather_patches_memm_multi", eng.prec, ptr(g.misc), g.n, ptr(g.src, b0), C, ptr(g.cen, 2 * b0),
-                     Pb, ph, pw, ptr(x), 16)
+                if flow.pack and flow.early:
+                    call("crimac_gather_patches_memm_meta_multi", eng.prec, ptr(g.misc), ptr(g.meta), g.n, ptr(g.src, b0), C,
+                         ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16, None, 1, flow.flags)
+                else:
+                    call("crimac_gather_patches_memm_multi", eng.prec, ptr(g.misc), g.n, ptr(g.src, b0), C,
+                         ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16)
                 if predict_fn is not None:
                     probs = predict_fn(x, Pb, ph, pw)
+                elif eng.lmi:
+                    probs = eng.forward_nhwc(x, Pb, ph, pw, False, softmax=True, meta=flow.meta_planes(g, b0, Pb))
                 else:
                     probs = eng.forward_nhwc_eval_split(x, Pb, ph, pw, softmax=True)
                 call("crimac_scatter_patches_multi", ptr(probs), probs.shape[1], ptr(g.misc), g.n, ptr(g.src, b0),
@@ -1513,8 +1602,8 @@ class _MemmEvalRecord(_MemmRecord):
     """``_MemmRecord`` + the echogram's extended school boxes (None for eval_mode 'all'); the int32 words of the boxes and
     of the echogram's entry in the offset table count towards what the echogram takes of a group's staging."""
 
-    def __init__(self, echogram, seabed, patch_size, patch_overlap, eval_mode="all", extend_size=20):
-        super().__init__(echogram, seabed, patch_size, patch_overlap)
+    def __init__(self, echogram, seabed, patch_size, patch_overlap, eval_mode="all", extend_size=20, **meta):
+        super().__init__(echogram, seabed, patch_size, patch_overlap, **meta)
         self.boxes = eval_boxes(echogram, eval_mode, extend_size)
         words = 2 * hip.MEMM_DESC_WORDS + 3 * len(self.grid) + self.n_pings + 2 + \
             (0 if self.boxes is None else 4 * len(self.boxes))
@@ -1533,17 +1622,19 @@ def _takes_keyword(fn, name):
 
 def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, eval_mode="all", extend_size=20,
                             predict_fn=None, meta_channels=None, seabed=None, hist=None, on_batch=None, group_patches=None,
-                            group_elems=None, stats=None, **kwargs):
+                            group_elems=None, stats=None, pack_metadata=False, **kwargs):
     """Test-set evaluation of a whole memm survey (``validate_model_survey_memm``, evaluate.py:84-117) on the tiled path:
     ``(hist_pos, hist_neg)`` int64 numpy [16384], the sum of ``evaluate_echogram_memm`` over ``echograms``.
 
-    Groups, batches, ``seabed``, metadata models, ``stats`` and ``kwargs``: ``_MemmSurveyFlow``, the plan of
+    Groups, batches, ``seabed``, metadata models and ``pack_metadata``, ``stats`` and ``kwargs``: ``_MemmSurveyFlow``, the plan of
     ``predict_echograms_memm`` with every echogram's own ``plan_eval_grid(..., memm=True)`` -- the int32 words of an
     echogram's boxes count towards its share of the staging.  Nothing but the two histograms comes back.  Per batch:
     ``crimac_gather_eval_crops_multi`` -> ``crimac_labels_test_transform_multi`` (-> ``crimac_labels_extend_mask_multi``
     with the group's box table, ``eval_boxes`` per echogram, for ``eval_mode`` 'region' / 'trace') -> network input
     (``crimac_gather_patches_memm_multi`` for 'all', ``crimac_gather_patches_memm_labels_multi`` for 'region' / 'trace',
-    as ``ChunkPredictor.evaluate`` chooses) -> ``eval_logits`` -> ``crimac_pr_histogram``.
+    as ``ChunkPredictor.evaluate`` chooses; packed metadata input channels: ``crimac_gather_patches_memm_meta_multi``, without
+    / with the transformed labels) -> ``eval_logits`` (packed late injection: with the planes of
+    ``crimac_meta_planes_multi``) -> ``crimac_pr_histogram``.
 
     ``hist`` (int32 [2, 16384] on the GPU): accumulate into it and return it, no collective (as
     ``evaluate_echogram_memm``); None: ``finish_histograms`` -- with several ranks the histograms are all-reduced once,
@@ -1552,9 +1643,10 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
     declares the keyword ``echograms`` also gets the echogram of every patch of the batch (a list of P)."""
     flow = _MemmSurveyFlow("evaluate_echograms_memm",
                            ("group_patches", "group_elems", "seabed", "stats", "predict_fn", "meta_channels", "eval_mode",
-                            "extend_size", "hist", "on_batch"),
+                            "extend_size", "hist", "on_batch", "pack_metadata"),
                            kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
-                           group_patches, group_elems, stats, eval_mode=eval_mode)
+                           group_patches, group_elems, stats, eval_mode=eval_mode, meta_channels=meta_channels,
+                           pack_metadata=pack_metadata)
     eng, dev, C, ph, pw = flow.eng, flow.dev, flow.C, flow.ph, flow.pw
     own = hist is None
     if own:
@@ -1595,7 +1687,7 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
     with flow.staged("memm-eval", record=record, tail=tail if masked else None) as groups:
         for g in groups:
             if g.offs is None:
-                single(g.group[0].echogram, g.group[0].seabed, None)
+                single(g.group[0].echogram, *flow.solo(g.group[0]))
                 continue
             misc, n, P, cen, src = g.misc, g.n, g.P, g.cen, g.src
             cen64 = cen[:2 * P].view(P, 2).long()            # the label kernels take `center_coordinates` as int64
@@ -1615,12 +1707,17 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
                 if masked:
                     call("crimac_labels_extend_mask_multi", ptr(labels_t), ptr(raw), C, ptr(cen64, 2 * b0), ptr(boxes),
                          ptr(box_off), n, ptr(src, b0), -1, Pb, ph, pw)
+                if flow.pack and flow.early:
+                    call("crimac_gather_patches_memm_meta_multi", eng.prec, ptr(misc), ptr(g.meta), n, ptr(src, b0), C,
+                         ptr(cen, 2 * b0), Pb, ph, pw, ptr(x), 16, ptr(labels_t) if masked else None, 1, flow.flags)
+                elif masked:
                     call("crimac_gather_patches_memm_labels_multi", eng.prec, ptr(misc), n, ptr(src, b0), C,
                          ptr(cen, 2 * b0), Pb, ph, pw, ptr(x), 16, ptr(labels_t))
                 else:
                     call("crimac_gather_patches_memm_multi", eng.prec, ptr(misc), n, ptr(src, b0), C, ptr(cen, 2 * b0), Pb,
                          ph, pw, ptr(x), 16)
-                logits = eval_logits(eng, x, Pb, ph, pw, predict_fn=predict_fn, split=True)
+                meta = flow.meta_planes(g, b0, Pb) if eng.lmi and predict_fn is None else None
+                logits = eval_logits(eng, x, Pb, ph, pw, meta=meta, predict_fn=predict_fn, split=True)
                 if on_batch is not None:
                     emit(cen_h[b0:b0 + Pb], labels_t, logits, lambda: egs_h[b0:b0 + Pb])
                 B, nc, H, Wd = logits.shape

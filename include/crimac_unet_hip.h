@@ -130,7 +130,7 @@ extern "C" {
  * points changes, and a binding must refuse a library whose version differs from the header it was written against (an
  * older build that happens to export every symbol would walk a descriptor array with the wrong stride).
  * crimac_layer_desc_size() is sizeof(crimac_layer_desc) as the library was compiled. */
-#define CRIMAC_ABI_VERSION 13
+#define CRIMAC_ABI_VERSION 14
 int crimac_version(void);
 int crimac_layer_desc_size(void);
 const char* crimac_last_error(void);
@@ -581,6 +581,24 @@ int crimac_gather_patches_memm_labels_multi(int prec, const crimac_memm_desc* de
                                             const int* centres, int P, int ph, int pw, void* out, long ld,
                                             const short* patch_labels, void* stream);
 
+/* The same batches for a model with metadata planes (tiled_inference, pack_metadata=True): the metadata sources of the
+ * echograms in a second table, parallel to the first and indexed by the same src[p]: crimac_memm_meta_desc, seven 64-bit
+ * fields, laid out in include/crimac_memm_meta.h (this header names the type only: the structs defined HERE are the ones
+ * crimac_*_size() and the binding's mirrors account for one by one).  `flags` is common to a launch, as C is. */
+typedef struct crimac_memm_meta_desc crimac_memm_meta_desc;   /* defined in include/crimac_memm_meta.h */
+/* crimac_gather_patches_memm_meta (patch_labels == NULL: border rule by the descriptor's labels) and
+ * crimac_gather_patches_memm_labels with metadata (patch_labels [P][ph][pw]: border rule by the batch's transformed labels,
+ * centre row H / 2 when that echogram's H <= ph), with data, labels and extents from descs[src[p]] and the scalar and the
+ * vectors of the planes from metas[src[p]]; meta_centres are the centres themselves -- an echogram is its own chunk, ping 0
+ * is global ping 0.  flags in 1..63, C + planes <= ld.  Each equals its single-source entry point run per echogram, bit
+ * for bit (the same kernel).  A patch whose src lies outside [0, n_desc), or whose metadata descriptor lacks a vector the
+ * flags need (NULL or n <= 0), is skipped -- nothing is read, nothing is written; sources are indexed with 64-bit
+ * arithmetic. */
+int crimac_gather_patches_memm_meta_multi(int prec, const crimac_memm_desc* descs, const crimac_memm_meta_desc* metas,
+                                          int n_desc, const int* src, int C, const int* centres, int P, int ph, int pw,
+                                          void* out, long ld, const short* patch_labels, int db_scaled, int flags,
+                                          void* stream);
+
 
 /* Validation metrics (get_predictions_dataloader + compute_evaluation_metrics, pipeline.py:242-295):
  * histograms (16384 bins, indexed by the float16 bit pattern of softmax(logits)[SANDEEL]) of the valid
@@ -605,6 +623,11 @@ int crimac_pr_histogram(const float* logits, int ncls, const void* labels, int l
 int crimac_meta_planes(const int* centres, int P, int H, int W, int flags, double portion_year,
                        const double* portion_day, int n_day, const double* time_diff, int n_td,
                        const long long* seabed, int n_sb, float* out, void* stream);
+/* crimac_meta_planes for batches packed from several memmap echograms: the scalar and the vectors of patch p from
+ * metas[src[p]] (crimac_memm_meta_desc), everything else -- flags, centres, plane order, out [P][Cm][H][W] -- as
+ * there, bit for bit (the same kernel).  Skipped patches as in crimac_gather_patches_memm_meta_multi. */
+int crimac_meta_planes_multi(const crimac_memm_meta_desc* metas, int n_desc, const int* src, const int* centres, int P,
+                             int H, int W, int flags, float* out, void* stream);
 
 /* ---- late metadata injection (UNet_LateMetInject, unet.py:346-391; MetaPostProcessing, unet.py:140-166) ---- */
 

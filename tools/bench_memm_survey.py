@@ -14,7 +14,11 @@ Both legs: one warm-up pass over the survey, then ``--passes`` (3) timed passes,
 the host); host clock around a whole pass, which ends with the last result on the host.  Reported: patches/s (median
 pass) of both legs, the ratio, the share of forward batches below 16 patches (where the eval forward loses its two-stream
 form) in both, and the largest difference between the two legs' outputs over the whole survey (the bound is one float16
-step, 2**-11: batches of another size)."""
+step, 2**-11: batches of another size).
+
+``--meta early|late``: the same survey with metadata vectors (``add_metadata``) and a model that takes them -- all seven
+planes as extra input channels (``UNet_Baseline(3, 11)``) or by late injection (``UNet_LateMetInject(3, 4, 7)``); the packed
+leg then runs with ``pack_metadata=True``, the loop is what such a model gets without it."""
 import argparse
 import json
 import os
@@ -58,6 +62,32 @@ def synth_memm_survey(n, seed, pings=(500, 6000), rows=(200, 700)):
     return egs
 
 
+def add_metadata(egs, seed):
+    """The per-ping vectors and the scalar the metadata planes are built from (data_reader.py:98-100), seeded."""
+    rng = np.random.Generator(np.random.PCG64(seed + 1))
+    for i, eg in enumerate(egs):
+        tv = 737000.5 + i + np.cumsum(rng.uniform(5e-6, 9e-6, size=eg.shape[1]))
+        eg.portion_of_day_vector = tv % 1
+        eg.portion_of_year_scalar = float(rng.uniform(0.3, 0.7))
+        eg.time_vector_diff = np.concatenate((np.diff(tv), [tv[-1] - tv[-2]])) / 6e-6 - 1
+
+
+def make_model(meta, precision):
+    """``--meta`` none / early / late -> (the model with synthetic weights, the keywords of both legs, those of the packed)."""
+    mc = {k: True for k in ti.META_FLAGS}
+    if meta == "early":
+        model = pkg.UNet_Baseline(3, len(FREQS) + 7, infer_precision=precision)
+        model.load_state_dict(synth.synth_state_dict(seed=0, in_channels=len(FREQS) + 7))
+    elif meta == "late":
+        model = pkg.UNet_LateMetInject(3, len(FREQS), 7, infer_precision=precision)
+        model.load_state_dict(synth.synth_state_dict(seed=0, meta_in_channels=7))
+    else:
+        model = pkg.UNet_Baseline(3, len(FREQS), infer_precision=precision)
+        model.load_state_dict(synth.synth_state_dict(seed=0))
+        return model, {}, {}
+    return model, dict(meta_channels=mc), dict(pack_metadata=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--echograms", type=int, default=200)
@@ -65,14 +95,16 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seed", type=int, default=11)
     ap.add_argument("--precision", default=None, help="inference precision (default: the package's, 'h3p')")
+    ap.add_argument("--meta", default="none", choices=["none", "early", "late"], help="metadata model (module docstring)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_memm_survey: needs a GPU")
     t0 = time.perf_counter()
     egs = synth_memm_survey(args.echograms, args.seed)
+    if args.meta != "none":
+        add_metadata(egs, args.seed)
     synth_s = time.perf_counter() - t0
-    model = pkg.UNet_Baseline(3, len(FREQS), infer_precision=args.precision)
-    model.load_state_dict(synth.synth_state_dict(seed=0))
+    model, kw, kw_packed = make_model(args.meta, args.precision)
 
     class Pipe:
         frequencies = FREQS
@@ -86,14 +118,15 @@ def main():
 
     def loop(keep=None):
         for eg in egs:
-            out = ti.predict_echogram_memm(eg, pipe, PATCH, OVERLAP, args.batch)
+            out = ti.predict_echogram_memm(eg, pipe, PATCH, OVERLAP, args.batch, **kw)
             if keep is not None:
                 keep.append(out.astype(np.float16))
 
     stats = {}
 
     def packed(keep=None):
-        for eg, out in ti.predict_echograms_memm(iter(egs), pipe, PATCH, OVERLAP, args.batch, stats=stats):
+        for eg, out in ti.predict_echograms_memm(iter(egs), pipe, PATCH, OVERLAP, args.batch, stats=stats, **kw,
+                                                 **kw_packed):
             if keep is not None:
                 keep.append(out.astype(np.float16))
 
@@ -119,13 +152,14 @@ def main():
     small = lambda bs: round(sum(1 for p in bs if p < 16) / max(1, len(bs)), 4)                  # noqa: E731
     print(json.dumps({
         "echograms": len(egs), "patches": patches, "pixels": int(sum(eg.shape[0] * eg.shape[1] for eg in egs)),
-        "precision": model.infer_precision,
+        "precision": model.infer_precision, "meta": args.meta,
         "loop_patches_per_s": round(patches / med["loop"], 1), "packed_patches_per_s": round(patches / med["packed"], 1),
         "packed_over_loop": round(med["loop"] / med["packed"], 3),
         "loop_pass_s": [round(t, 4) for t in times["loop"]], "packed_pass_s": [round(t, 4) for t in times["packed"]],
         "loop_batches": len(loop_batches), "loop_batches_below_16": small(loop_batches),
         "packed_groups": stats["groups"], "packed_batches": len(stats["batches"]),
         "packed_batches_below_16": small(stats["batches"]), "packed_solo_echograms": stats["solo_echograms"],
+        "packed_fallback_echograms": stats["fallback_echograms"],
         "max_abs_difference": worst, "differing_pixel_share": round(differing / max(1, total), 8),
         "synth_s": round(synth_s, 1), "device": torch.cuda.get_device_name(0)}))
 
