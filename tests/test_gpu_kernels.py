@@ -12,6 +12,12 @@ bn_act_pool, unpool_add, bn_bwd_reduce and the four bn_bwd_apply paths) have the
 tests/test_gpu_bn_kernels.py: a float64 reference, data on which the ReLU and arg-max decisions are exact, element-wise
 bounds, edge channel counts, strided / sliced / guarded buffers and capped grids.  The tests of those kernels below compare
 them at the workload's shapes and with one another.
+
+The MFMA contraction kernels (conv3x3, its pool / cols / input-gradient uses, the transposed convolution, the weight
+gradients) have their exact tests in tests/test_gpu_conv_exact.py: ternary operands on which every kernel form and
+precision must equal a float64 reference bit for bit, images smaller than a tile (down to 1x1), guarded and sliced
+buffers.  The tests of those kernels below compare them norm-wise on Gaussian data, which a single wrong product at
+K = 9 * Cin >= 576 passes in the 16-bit modes.
 """
 import numpy as np
 import pytest
