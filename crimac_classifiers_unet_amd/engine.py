@@ -17,6 +17,7 @@ PyTorch supplies memory and streams only; there is no CPU or eager fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -507,13 +508,16 @@ class UNetEngine:
             self._ltab16 = arr16
         return self._ltab
 
-    def _pack_group(self, gi):
-        arr, bounds = self._layer_table()
-        first, n = bounds[gi]
+    def _pack_layers(self, first, n):
+        """Operand planes of layers [first, first + n) of the layer table (h3f: and their fp16 twins)."""
         if n:
+            arr, _ = self._layer_table()
             call("crimac_pack_layers", C.byref(arr, first * C.sizeof(hip.LayerDesc)), n, self._fwd_planes_arg())
             if self.bwd16:
                 call("crimac_pack_layers", C.byref(self._ltab16, first * C.sizeof(hip.LayerDesc)), n, hip.PLANES_FP16)
+
+    def _pack_group(self, gi):
+        self._pack_layers(*self._layer_table()[1][gi])
 
     def _pk_bwd(self, key):
         """Operand planes the backward pass's contractions read (h3f: the fp16 input-gradient planes)."""
@@ -532,10 +536,8 @@ class UNetEngine:
             for gi in range(len(bounds)):
                 if gi not in done:
                     self._pack_group(gi)
-        elif len(arr):
-            call("crimac_pack_layers", C.byref(arr), len(arr), self._fwd_planes_arg())
-            if self.bwd16:
-                call("crimac_pack_layers", C.byref(self._ltab16), len(arr), hip.PLANES_FP16)
+        else:
+            self._pack_layers(0, len(arr))
         self._packed_groups = set()
         self._train_pack_dirty = False
 
@@ -643,13 +645,20 @@ class UNetEngine:
             self._side = [torch.cuda.Stream(device=self.device) for _ in range(self.wgrad_side_streams)]
             self._side_events = [torch.cuda.Event() for _ in range(32)]
             self._side_i = 0
+        with self._fork_side(self._side[self._side_i % len(self._side)]):
+            fn()
+
+    def _fork_side(self, side):
+        """Context in which ``side`` is the current stream, ordered after everything queued on the caller's stream so far."""
         ev = self._side_events[self._side_i % len(self._side_events)]
-        side = self._side[self._side_i % len(self._side)]
         self._side_i += 1
         ev.record()                                   # everything the launch reads has been queued on this stream
-        with torch.cuda.stream(side):
-            side.wait_event(ev)
-            fn()
+        side.wait_event(ev)
+        return torch.cuda.stream(side)
+
+    def _single_side(self):
+        """The side stream when there is exactly one (follow-up work is then queued on it behind the weight gradients)."""
+        return self._side[0] if (self._side is not None and len(self._side) == 1) else None
 
     def _wgrad(self, prec, mode, f, f_ld, cf, s_, s_ld, cs, B, h, w, key, flops=None):
         dwt, sp, stride = self._dw(key)
@@ -680,31 +689,29 @@ class UNetEngine:
         self._flush_wgrad_group()                     # the group's conv3x3 weight gradients: one persistent launch
         arr, bounds = self._layer_table()
         first, n = bounds[gi]
-        side = self._side[0] if (self._side is not None and len(self._side) == 1) else None
-        if side is not None:
-            # bias / BatchNorm gradients of the range are written on the caller's stream: order them first
-            ev = self._side_events[self._side_i % len(self._side_events)]
-            self._side_i += 1
-            ev.record()
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                if n:
-                    call("crimac_unpack_wgrad_layers", C.byref(arr, first * C.sizeof(hip.LayerDesc)), n)
-                self._unpack_narrow(gi)
-                if on_ready is not None and self.exchange_on_side:
-                    on_ready(*rng)
-                done = torch.cuda.Event()
-                done.record()
-                self._unpacked[gi] = done             # (gradient range gi is final on the side stream from here)
-            if on_ready is not None and not self.exchange_on_side:
-                torch.cuda.current_stream().wait_stream(side)       # the collective is queued on the caller's stream
+
+        def unpack():
+            if n:
+                call("crimac_unpack_wgrad_layers", C.byref(arr, first * C.sizeof(hip.LayerDesc)), n)
+            self._unpack_narrow(gi)
+
+        side = self._single_side()
+        if side is None:
+            self._join_wgrad()
+            unpack()
+            if on_ready is not None:
                 on_ready(*rng)
             return
-        self._join_wgrad()
-        if n:
-            call("crimac_unpack_wgrad_layers", C.byref(arr, first * C.sizeof(hip.LayerDesc)), n)
-        self._unpack_narrow(gi)
-        if on_ready is not None:
+        # bias / BatchNorm gradients of the range are written on the caller's stream: order them first
+        with self._fork_side(side):
+            unpack()
+            if on_ready is not None and self.exchange_on_side:
+                on_ready(*rng)
+            done = torch.cuda.Event()
+            done.record()
+            self._unpacked[gi] = done                 # (gradient range gi is final on the side stream from here)
+        if on_ready is not None and not self.exchange_on_side:
+            torch.cuda.current_stream().wait_stream(side)           # the collective is queued on the caller's stream
             on_ready(*rng)
 
     def _unpack_narrow(self, gi):
@@ -972,19 +979,15 @@ class UNetEngine:
     def _bn_train(self, b, y: Act, M):
         """Batch statistics were accumulated by the conv epilogue; finish them."""
         world = self._sync_world()
+        src = (ptr(self._stat(b, 0)), ptr(self._stat(b, 1)), self._nrep(b.cout), M, b.cout)
         if world > 1:
             import torch.distributed as dist
             tmp = self._buf("syncbn.fwd", (2, self.cmax), torch.float64)   # (the backward slots must stay zero)
             call("crimac_sum_replicas", ptr(self._stat(b, 0)), self._nrep(b.cout), b.cout, b.cout,
                  ptr(tmp[0]), None, ptr(self._stat(b, 1)), ptr(tmp[1]))
             dist.all_reduce(tmp, group=UNetEngine._bn_group)
-            call("crimac_bn_finalize", ptr(tmp[0]), ptr(tmp[1]), 1, M * world, b.cout,
-                 ptr(self.P[b.bn_key + ".weight"]), ptr(self.P[b.bn_key + ".bias"]), BN_EPS, BN_MOMENTUM,
-                 ptr(self.Bf[b.bn_key + ".running_mean"]), ptr(self.Bf[b.bn_key + ".running_var"]),
-                 ptr(self.Bf[b.bn_key + ".num_batches_tracked"]), ptr(self._bnf(b, 0)),
-                 ptr(self._bnf(b, 1)), ptr(self._bnf(b, 2)), ptr(self._bnf(b, 3)))
-            return
-        call("crimac_bn_finalize", ptr(self._stat(b, 0)), ptr(self._stat(b, 1)), self._nrep(b.cout), M, b.cout,
+            src = (ptr(tmp[0]), ptr(tmp[1]), 1, M * world, b.cout)
+        call("crimac_bn_finalize", *src,
              ptr(self.P[b.bn_key + ".weight"]), ptr(self.P[b.bn_key + ".bias"]), BN_EPS, BN_MOMENTUM,
              ptr(self.Bf[b.bn_key + ".running_mean"]), ptr(self.Bf[b.bn_key + ".running_var"]),
              ptr(self.Bf[b.bn_key + ".num_batches_tracked"]), ptr(self._bnf(b, 0)),
@@ -1008,6 +1011,21 @@ class UNetEngine:
              ptr(self._bnf(b, 2)) if train else None, ptr(self._bnf(b, 3)) if train else None,
              1 if train else 0, out.p if out is not None else None, out.ld if out is not None else 0,
              pool.p if pool is not None else None, pool.ld if pool is not None else 0, B, H, W, b.cout)
+
+    def _conv_stats(self, b, x: Act, y: Act, B, h, w, cin, cin_real=None):
+        """Train mode: y = conv3x3(x) of block b, its BatchNorm statistics taken in the conv epilogue."""
+        self._conv3x3(x, self.pk[b.conv_key], self.P[b.conv_key + ".bias"], y, B, h, w, cin, b.cout, relu=False,
+                      cin_real=cin_real, stats=(self._stat(b, 0), self._stat(b, 1)))
+
+    def _conv_bn(self, b, x: Act, y: Act, out: Act, pool: Act, B, h, w, M, cin, cin_real=None):
+        """Train-mode step of block b: conv3x3 with statistics, then BatchNorm + ReLU (+ max-pool)."""
+        self._conv_stats(b, x, y, B, h, w, cin, cin_real)
+        self._bn_act(b, y, out, pool, B, h, w, M)
+
+    def _conv_folded(self, b, x: Act, out: Act, B, h, w, cin, cin_real=None):
+        """Eval-mode step of block b: conv3x3 with BatchNorm folded into its planes and bias, + ReLU."""
+        pe = self.pk_eval[b.conv_key]
+        self._conv3x3(x, pe, pe["bias"], out, B, h, w, cin, b.cout, relu=True, cin_real=cin_real, out_planes=True)
 
     # ------------------------------------------------------------------------------------------
     # forward
@@ -1158,27 +1176,21 @@ class UNetEngine:
             if training:
                 y1 = Act(self._buf(f"e{i}.y1", (M, c)), c)
                 y2 = Act(self._buf(f"e{i}.y2", (M, c)), c)
-                self._conv3x3(cur, self.pk[b1.conv_key], self.P[b1.conv_key + ".bias"], y1, B, h, w,
-                              b1.cin_pad, c, relu=False, cin_real=b1.cin,
-                              stats=(self._stat(b1, 0), self._stat(b1, 1)))
-                self._bn_act(b1, y1, a1, None, B, h, w, M)
-                self._conv3x3(a1, self.pk[b2.conv_key], self.P[b2.conv_key + ".bias"], y2, B, h, w, c, c,
-                              relu=False, stats=(self._stat(b2, 0), self._stat(b2, 1)))
-                self._bn_act(b2, y2, a2, pool, B, h, w, M)
+                self._conv_bn(b1, cur, y1, a1, None, B, h, w, M, b1.cin_pad, cin_real=b1.cin)
+                self._conv_bn(b2, a1, y2, a2, pool, B, h, w, M, c)
                 saved[f"e{i}"] = (cur, y1, a1, y2, a2)
             else:
-                pe1, pe2 = self.pk_eval[b1.conv_key], self.pk_eval[b2.conv_key]
-                self._conv3x3(cur, pe1, pe1["bias"], a1, B, h, w, b1.cin_pad, c, relu=True, cin_real=b1.cin,
-                              out_planes=True)
+                self._conv_folded(b1, cur, a1, B, h, w, b1.cin_pad, cin_real=b1.cin)
                 if pool is not None and not b2.narrow:
                     # the max-pool comes out of the conv epilogue (the tile is still in LDS)
+                    pe2 = self.pk_eval[b2.conv_key]
                     call("crimac_conv3x3_pool", self.prec, a1.p, a1.ld, B, h, w, c, c, ptr(pe2["fwd_hi"]),
                          ptr(pe2["fwd_lo"]), ptr(pe2["bias"]), a2.p, a2.ld,
                          hip.EPI_RELU | (hip.EPI_OUT_PLANES if self.is_hp else 0)
                          | (hip.EPI_WFRAG if pe2.get("fwd_frag") else 0), pool.p, pool.ld,
                          flops=2.0 * 9 * c * c * B * h * w, mfmas=hip.MFMAS_PER_PRODUCT[self.prec])
                 else:
-                    self._conv3x3(a1, pe2, pe2["bias"], a2, B, h, w, c, c, relu=True, out_planes=True)
+                    self._conv_folded(b2, a1, a2, B, h, w, c)
                     if pool is not None:
                         self._act(b2, a2, None, pool, B, h, w, train=False)
             cur = pool if pool is not None else a2
@@ -1198,44 +1210,37 @@ class UNetEngine:
             if training:
                 y1 = Act(self._buf(f"d{j}.y1", (M, c)), c)
                 y2 = Act(self._buf(f"d{j}.y2", (M, c)), c)
-                self._conv3x3(catA, self.pk[b1.conv_key], self.P[b1.conv_key + ".bias"], y1, B, h, w,
-                              2 * c, c, relu=False, stats=(self._stat(b1, 0), self._stat(b1, 1)))
-                self._bn_act(b1, y1, a1, None, B, h, w, M)
-                self._conv3x3(a1, self.pk[b2.conv_key], self.P[b2.conv_key + ".bias"], y2, B, h, w, c, c,
-                              relu=False, stats=(self._stat(b2, 0), self._stat(b2, 1)))
+                self._conv_bn(b1, catA, y1, a1, None, B, h, w, M, 2 * c)
                 if j == D - 2 and self.fuse_head_bn and self.fuse_bn_bwd:
                     # the last block's activation only feeds the 1x1 head: formed on the fly there (forward and
                     # backward) from y2 -- one read + one write of the largest activation saved, twice
+                    self._conv_stats(b2, a1, y2, B, h, w, c)
                     self._bn_train(b2, y2, M)
                     head_bn = b2
                     a2 = y2
                 else:
-                    self._bn_act(b2, y2, a2, None, B, h, w, M)
+                    self._conv_bn(b2, a1, y2, a2, None, B, h, w, M, c)
                 saved[f"d{j}"] = (cur, catA, y1, a1, y2, a2)
             else:
-                pe1, pe2 = self.pk_eval[b1.conv_key], self.pk_eval[b2.conv_key]
-                self._conv3x3(catA, pe1, pe1["bias"], a1, B, h, w, 2 * c, c, relu=True, out_planes=True)
-                self._conv3x3(a1, pe2, pe2["bias"], a2, B, h, w, c, c, relu=True, out_planes=True)
+                self._conv_folded(b1, catA, a1, B, h, w, 2 * c)
+                self._conv_folded(b2, a1, a2, B, h, w, c)
             cur = a2
         logits = out if out is not None else torch.empty((B, self.n_classes, H, W), dtype=torch.float32,
                                                          device=self.device)
+        w_head, head_softmax = ptr(self.P["conv_final.weight"]), 1 if softmax else 0
         if self.lmi:
             if meta is None:
                 raise ValueError("UNet_LateMetInject needs the metadata tensor")
             w64, wm = self._lmi_weights()
-            call("crimac_head_fwd", self.prec, cur.p, cur.ld, self.sf, ptr(w64), ptr(self.P["conv_final.bias"]),
-                 ptr(logits), B, H, W, self.n_classes, 0,
-                 ptr(self._bnf(head_bn, 2)) if head_bn is not None else None,
-                 ptr(self._bnf(head_bn, 3)) if head_bn is not None else None)
+            w_head, head_softmax = ptr(w64), 0        # (the softmax follows the injection)
+        bn_scale, bn_shift = (ptr(self._bnf(head_bn, 2)), ptr(self._bnf(head_bn, 3))) if head_bn is not None else (None, None)
+        call("crimac_head_fwd", self.prec, cur.p, cur.ld, self.sf, w_head, ptr(self.P["conv_final.bias"]), ptr(logits),
+             B, H, W, self.n_classes, head_softmax, bn_scale, bn_shift)
+        if self.lmi:
             m = self._buf("lmi.m", (B * H * W,), torch.float32)
             call("crimac_meta_mlp_fwd", ptr(meta), self.meta_channels, B, H, W, *self._mlp(), ptr(m))
             call("crimac_meta_inject_fwd", ptr(m), ptr(wm), ptr(logits), B, H, W, self.n_classes, 1 if softmax else 0)
             saved["meta"] = meta
-        else:
-            call("crimac_head_fwd", self.prec, cur.p, cur.ld, self.sf, ptr(self.P["conv_final.weight"]),
-                 ptr(self.P["conv_final.bias"]), ptr(logits), B, H, W, self.n_classes, 1 if softmax else 0,
-                 ptr(self._bnf(head_bn, 2)) if head_bn is not None else None,
-                 ptr(self._bnf(head_bn, 3)) if head_bn is not None else None)
         saved["head_in"] = cur if head_bn is None else None
         self.saved = saved if training else None
         if training:
@@ -1256,6 +1261,16 @@ class UNetEngine:
         gradient) from the dgrad epilogue.  unpool_src=(dp, ds): ``da`` was NOT stored -- it is ds + unpool(dp), whose
         BatchNorm-backward sums crimac_unpool_add took (sums-only call); the apply kernel rebuilds it.
         Returns whether next_bn's sums were fused."""
+        dy = self._bn_bwd(tag, b, da, y, B, h, w, M, reduce_done, unpool_src)
+        self._wgrad(self.prec_bwd, 0, dy.p, dy.ld, b.cout, x_in.p, x_in.ld, b.cin_pad, B, h, w, b.conv_key,
+                    flops=2.0 * 9 * b.cin * b.cout * B * h * w)
+        if dx_out is None:
+            return False
+        return self._dgrad(tag, b, dy, dx_out, B, h, w, M, next_bn, bias_from_stats) and next_bn is not None
+
+    def _bn_bwd(self, tag, b, da: Act, y: Act, B, h, w, M, reduce_done, unpool_src):
+        """BatchNorm + ReLU backward of block b: the two per-channel sums (unless the producer of ``da`` took them), the
+        SyncBN exchange, then dy = d(conv output) into the buffer ``{tag}.dy`` and the gamma / beta gradients."""
         world = self._sync_world()
         folded = reduce_done and self.fold_bn_finalize and world == 1     # the replicas are added up by the apply kernel
         if folded:
@@ -1297,103 +1312,70 @@ class UNetEngine:
             call("crimac_bn_bwd_apply", prec_apply, da.p, da.ld, y.p, y.ld, ptr(self._bnf(b, 2)),
                  ptr(self._bnf(b, 3)), ptr(self._bnf(b, 0)), ptr(self._bnf(b, 1)), ptr(self._stat(b, 2)),
                  ptr(self._stat(b, 3)), M, M * world, b.cout, dy.p, dy.ld, ptr(dgamma), ptr(dbeta), None)
-        self._wgrad(self.prec_bwd, 0, dy.p, dy.ld, b.cout, x_in.p, x_in.ld, b.cin_pad, B, h, w, b.conv_key,
-                    flops=2.0 * 9 * b.cin * b.cout * B * h * w)
-        fused = False
-        if dx_out is not None:
-            stats = None
-            if bias_from_stats is not None:
-                per = 2 * STAT_REPLICAS * 2 * self.cmax                  # this level's slice (zeroed in backward())
-                lvl = bias_from_stats[2]
-                scr = self.bias_scr[lvl * per:(lvl + 1) * per]
-                stats = (scr[:per // 2], scr[per // 2:])
-            C_up = bias_from_stats[1] if bias_from_stats is not None else 0
-            side = self._side[0] if (self._side is not None and len(self._side) == 1) else None
-            side_ok = side is not None and not self._gloo_ranks()      # skip half of decoder dgrads on the side stream
-            if b.narrow and bias_from_stats is not None:
-                # narrow decoder conv1: the up half of d(concat) (plane pairs in h3p: it feeds two contractions) with its
-                # column sums, then the skip half -- on the side stream when there is one, as below
-                self._conv3x3(dy, self.pk[b.conv_key], None, dx_out, B, h, w, b.cout, b.cin, relu=False, dgrad=True,
-                              stats=stats, cols=(0, C_up), out_planes=True)
-                if side_ok:
-                    ev = self._side_events[self._side_i % len(self._side_events)]
-                    self._side_i += 1
-                    ev.record()
-                    with torch.cuda.stream(side):
-                        side.wait_event(ev)
-                        self._conv3x3(dy, self.pk[b.conv_key], None, dx_out, B, h, w, b.cout, b.cin, relu=False,
-                                      dgrad=True, cols=(C_up, C_up))
-                        done = torch.cuda.Event()
-                        done.record()
-                    self._skip_done[bias_from_stats[2]] = done
-                else:
-                    self._conv3x3(dy, self.pk[b.conv_key], None, dx_out, B, h, w, b.cout, b.cin, relu=False,
-                                  dgrad=True, cols=(C_up, C_up))
-                fused = stats is not None
-            elif self.is_hp and bias_from_stats is not None:
-                # plane pairs: the up half of d(concat) feeds two contractions (transposed-conv input and weight
-                # gradients) -> plane pairs; the skip half is read by unpool_add -> fp32: always two launches
-                if stats is None or b.cin != 2 * C_up or C_up % 64 != 0:
-                    raise NotImplementedError("h3p: decoder convolution shape outside the plane-pair kernels")
-                dx_up = dx_out
-                if self.bwd16:
-                    # h3f: the up half is an fp16 operand (2-byte elements) -- a buffer of its own, not a slice of the
-                    # 4-byte-addressed d(concat) buffer
-                    dx_up = Act(self._buf(f"{tag}.dup16", (M, C_up), torch.float16), C_up)
-                    self._dup16[bias_from_stats[2]] = dx_up
-                self._conv3x3(dy, self._pk_bwd(b.conv_key), None, dx_up, B, h, w, b.cout, b.cin, relu=False,
-                              dgrad=True, stats=stats, cols=(0, C_up), out_planes=True)
-                if side_ok:
-                    ev = self._side_events[self._side_i % len(self._side_events)]
-                    self._side_i += 1
-                    ev.record()
-                    with torch.cuda.stream(side):
-                        side.wait_event(ev)
-                        self._conv3x3(dy, self._pk_bwd(b.conv_key), None, dx_out, B, h, w, b.cout, b.cin, relu=False,
-                                      dgrad=True, cols=(C_up, C_up))
-                        done = torch.cuda.Event()
-                        done.record()
-                    self._skip_done[bias_from_stats[2]] = done
-                else:
-                    self._conv3x3(dy, self._pk_bwd(b.conv_key), None, dx_out, B, h, w, b.cout, b.cin, relu=False,
-                                  dgrad=True, cols=(C_up, C_up))
-                fused = True
-            elif (stats is not None and b.cin == 2 * C_up and b.cout % 64 == 0 and self.is16
-                    and ((side_ok and C_up % 128 == 0)
-                         or (C_up == 64 and b.cout == 64 and B * ((h + 15) // 16) * ((w + 15) // 16) >= 512))):
-                # decoder conv1: dx_out = d(concat [up | skip]).  The up half (and its column sums = the transposed
-                # convolution's bias gradient) is needed at once; the skip half only when the encoder level is
-                # reached -> side stream, off the critical path.  (The last decoder level -- two 64-channel halves of a
-                # 64-channel dy at 256 x 256 -- takes the two launches of the persistent 64 -> 64 kernel with or without a
-                # side stream: 2 x ~150 us against 330-344 us for the one-chunk launch of the channel-split kernel, and the
-                # serialized roofline pass then times the kernels the overlapped step runs.)
-                self._conv3x3(dy, self._pk_bwd(b.conv_key), None, dx_out, B, h, w, b.cout, b.cin, relu=False,
-                              dgrad=True, stats=stats, cols=(0, C_up))
-                if side_ok:
-                    ev = self._side_events[self._side_i % len(self._side_events)]
-                    self._side_i += 1
-                    ev.record()
-                    with torch.cuda.stream(side):
-                        side.wait_event(ev)
-                        self._conv3x3(dy, self._pk_bwd(b.conv_key), None, dx_out, B, h, w, b.cout, b.cin, relu=False,
-                                      dgrad=True, cols=(C_up, C_up))
-                        done = torch.cuda.Event()
-                        done.record()
-                    self._skip_done[bias_from_stats[2]] = done
-                else:
-                    self._conv3x3(dy, self._pk_bwd(b.conv_key), None, dx_out, B, h, w, b.cout, b.cin, relu=False,
-                                  dgrad=True, cols=(C_up, C_up))
-                fused = True
-            else:
-                fused = self._conv3x3(dy, self._pk_bwd(b.conv_key), None, dx_out, B, h, w, b.cout, b.cin, relu=False,
-                                      dgrad=True, stats=stats, bnb=next_bn if stats is None else None)
-            if stats is not None:
-                grad, C = bias_from_stats[:2]
-                call("crimac_sum_replicas", ptr(stats[0]), STAT_REPLICAS, b.cin, C, None, ptr(grad), None, None)
-            elif bias_from_stats is not None:
-                grad, C = bias_from_stats[:2]
-                call("crimac_colsum_f32", self.prec, dx_out.p, dx_out.ld, M, C, ptr(grad))
-        return fused and next_bn is not None
+        return dy
+
+    def _dgrad_concat(self, b, dy: Act, pk, dx_up: Act, dx_out: Act, B, h, w, stats, C_up, level, side):
+        """Decoder conv1: dx_out = d(concat [up | skip]) in two launches.  The up half (into ``dx_up``; plane pairs in h3p,
+        where it feeds two contractions) and its column sums = the transposed convolution's bias gradient are needed at
+        once; the skip half only when the encoder level is reached -> on ``side`` (the one side stream; None: inline),
+        off the critical path, with the event that says it is there in ``_skip_done[level]``."""
+        self._conv3x3(dy, pk, None, dx_up, B, h, w, b.cout, b.cin, relu=False, dgrad=True, stats=stats, cols=(0, C_up),
+                      out_planes=True)
+        with self._fork_side(side) if side is not None else contextlib.nullcontext():
+            self._conv3x3(dy, pk, None, dx_out, B, h, w, b.cout, b.cin, relu=False, dgrad=True, cols=(C_up, C_up))
+            if side is not None:
+                self._skip_done[level] = done = torch.cuda.Event()
+                done.record()
+
+    def _dgrad(self, tag, b, dy: Act, dx_out: Act, B, h, w, M, next_bn, bias_from_stats):
+        """dx_out = input gradient of block b's convolution; ``next_bn`` / ``bias_from_stats`` as in _block_bwd.  Returns
+        whether the dgrad epilogue took sums (next_bn's BatchNorm-backward sums, or the bias column sums)."""
+        stats, C_up, level = None, 0, None
+        if bias_from_stats is not None:
+            C_up, level = bias_from_stats[1:]
+            per = 2 * STAT_REPLICAS * 2 * self.cmax                      # this level's slice (zeroed in backward())
+            scr = self.bias_scr[level * per:(level + 1) * per]
+            stats = (scr[:per // 2], scr[per // 2:])
+        side = self._single_side()
+        if side is not None and self._gloo_ranks():
+            side = None                                   # (the skip half of decoder dgrads goes on the side stream)
+        pk = self._pk_bwd(b.conv_key)
+        if b.narrow and bias_from_stats is not None:
+            # narrow decoder conv1: two launches, the skip half on the side stream when there is one, as below
+            self._dgrad_concat(b, dy, self.pk[b.conv_key], dx_out, dx_out, B, h, w, stats, C_up, level, side)
+            fused = stats is not None
+        elif self.is_hp and bias_from_stats is not None:
+            # plane pairs: the up half of d(concat) feeds two contractions (transposed-conv input and weight
+            # gradients) -> plane pairs; the skip half is read by unpool_add -> fp32: always two launches
+            if stats is None or b.cin != 2 * C_up or C_up % 64 != 0:
+                raise NotImplementedError("h3p: decoder convolution shape outside the plane-pair kernels")
+            dx_up = dx_out
+            if self.bwd16:
+                # h3f: the up half is an fp16 operand (2-byte elements) -- a buffer of its own, not a slice of the
+                # 4-byte-addressed d(concat) buffer
+                dx_up = Act(self._buf(f"{tag}.dup16", (M, C_up), torch.float16), C_up)
+                self._dup16[level] = dx_up
+            self._dgrad_concat(b, dy, pk, dx_up, dx_out, B, h, w, stats, C_up, level, side)
+            fused = True
+        elif (stats is not None and b.cin == 2 * C_up and b.cout % 64 == 0 and self.is16
+                and ((side is not None and C_up % 128 == 0)
+                     or (C_up == 64 and b.cout == 64 and B * ((h + 15) // 16) * ((w + 15) // 16) >= 512))):
+            # 16-bit decoder conv1: two launches where the skip half can leave the critical path.  (The last decoder
+            # level -- two 64-channel halves of a 64-channel dy at 256 x 256 -- takes the two launches of the persistent
+            # 64 -> 64 kernel with or without a side stream: 2 x ~150 us against 330-344 us for the one-chunk launch of the
+            # channel-split kernel, and the serialized roofline pass then times the kernels the overlapped step runs.)
+            self._dgrad_concat(b, dy, pk, dx_out, dx_out, B, h, w, stats, C_up, level, side)
+            fused = True
+        else:
+            fused = self._conv3x3(dy, pk, None, dx_out, B, h, w, b.cout, b.cin, relu=False, dgrad=True, stats=stats,
+                                  bnb=next_bn if stats is None else None)
+        if stats is not None:
+            grad, C = bias_from_stats[:2]
+            call("crimac_sum_replicas", ptr(stats[0]), STAT_REPLICAS, b.cin, C, None, ptr(grad), None, None)
+        elif bias_from_stats is not None:
+            grad, C = bias_from_stats[:2]
+            call("crimac_colsum_f32", self.prec, dx_out.p, dx_out.ld, M, C, ptr(grad))
+        return fused
 
     wgrad_target_blocks = 0      # 0 = let the library pick the pixel-range split
 
@@ -1552,11 +1534,8 @@ class UNetEngine:
             fused = self._block_bwd(f"g.e{i}.2", b2, da2, y2, a1, B, h, w, M, da1, next_bn=(b1, y1),
                                     reduce_done=(self.fuse_bn_bwd and i != D - 1) or (i == D - 1 and cur_done),
                                     unpool_src=unpool_src)
-            if i > 0:
-                d_pool = Act(self._buf(f"g.e{i}.xin", (M, b1.cin)), b1.cin)
-                self._block_bwd(f"g.e{i}.1", b1, da1, y1, x_in, B, h, w, M, d_pool, reduce_done=fused)
-            else:
-                self._block_bwd(f"g.e{i}.1", b1, da1, y1, x_in, B, h, w, M, None, reduce_done=fused)
+            d_pool = Act(self._buf(f"g.e{i}.xin", (M, b1.cin)), b1.cin) if i > 0 else None     # (the network input has no gradient)
+            self._block_bwd(f"g.e{i}.1", b1, da1, y1, x_in, B, h, w, M, d_pool, reduce_done=fused)
             g = self._enc_group(i)
             if i == 0 or self._enc_group(i - 1) != g:        # last (shallowest) block of its group
                 self._unpack_group(g, on_ready, ranges[g] if ranges else None)
@@ -1704,7 +1683,7 @@ class UNetEngine:
                     scale = grad_sync(self.flat_g)
             self.sgd_step(lr, momentum, grad_scale=scale / ls, guarded=True)
             return (sums[0] / sums[1]).float()
-        if single and self.early_sgd and self._side is not None and len(self._side) == 1:
+        if single and self.early_sgd and self._single_side() is not None:
             self._sgd_left = None
             self.mark_dirty()                         # (before the early re-packs register themselves)
             self.backward(dl, before_join=lambda: self._early_sgd(lr, momentum))
