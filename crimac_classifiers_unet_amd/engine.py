@@ -160,8 +160,8 @@ class UNetEngine:
         self.meta_channels = int(getattr(module, "meta_in_channels", 0)) if self.lmi else 0
         if self.lmi and not 1 <= self.meta_channels <= 8:
             raise ValueError(f"late metadata injection supports 1..8 metadata channels, got {self.meta_channels}")
-        if self.lmi and self.bwd16:
-            raise NotImplementedError("precision 'h3f' with late metadata injection (use 'h3p')")
+        # (h3f covers it: the head writes the fp32 `da` of the last decoder block in every precision and the metadata
+        # kernels are fp32 throughout, so the fp16 backward starts at the same tensor as for UNet_Baseline)
         if self.bwd16:
             # h3f's fp16 backward pass exists on the fused kernels only: checked HERE, not in the first backward pass
             # (ADVICE r4): every transposed convolution inside crimac_upconv2x2_dgrad_bnb_prec's shapes, the fused
@@ -1069,15 +1069,6 @@ class UNetEngine:
             raise ValueError(f"expected metadata [B,{self.meta_channels},H,W] matching the data, got {tuple(meta.shape)}")
         return meta.contiguous().float()
 
-    def _lmi_weights(self):
-        """conv_final.weight [nc, 65, 1, 1] -> (first 64 columns packed [nc, 64], metadata column [nc])"""
-        w = self.P["conv_final.weight"].detach().view(self.n_classes, self.sf + 1)
-        w64 = self._buf("lmi.w64", (self.n_classes, self.sf), torch.float32)
-        wm = self._buf("lmi.wm", (self.n_classes,), torch.float32)
-        w64.copy_(w[:, :self.sf])
-        wm.copy_(w[:, self.sf])
-        return w64, wm
-
     def _mlp(self):
         pre = "post_processing_weights.main."
         return [ptr(self.P[pre + k]) for k in ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias")]
@@ -1227,20 +1218,19 @@ class UNetEngine:
             cur = a2
         logits = out if out is not None else torch.empty((B, self.n_classes, H, W), dtype=torch.float32,
                                                          device=self.device)
-        w_head, head_softmax = ptr(self.P["conv_final.weight"]), 1 if softmax else 0
+        bn_scale, bn_shift = (ptr(self._bnf(head_bn, 2)), ptr(self._bnf(head_bn, 3))) if head_bn is not None else (None, None)
         if self.lmi:
+            # head + perceptron + metadata column (+ softmax) in one launch on conv_final.weight [nc, 65] as it stands: the
+            # logits of crimac_head_fwd / crimac_meta_mlp_fwd / crimac_meta_inject_fwd bit for bit, written once
             if meta is None:
                 raise ValueError("UNet_LateMetInject needs the metadata tensor")
-            w64, wm = self._lmi_weights()
-            w_head, head_softmax = ptr(w64), 0        # (the softmax follows the injection)
-        bn_scale, bn_shift = (ptr(self._bnf(head_bn, 2)), ptr(self._bnf(head_bn, 3))) if head_bn is not None else (None, None)
-        call("crimac_head_fwd", self.prec, cur.p, cur.ld, self.sf, w_head, ptr(self.P["conv_final.bias"]), ptr(logits),
-             B, H, W, self.n_classes, head_softmax, bn_scale, bn_shift)
-        if self.lmi:
-            m = self._buf("lmi.m", (B * H * W,), torch.float32)
-            call("crimac_meta_mlp_fwd", ptr(meta), self.meta_channels, B, H, W, *self._mlp(), ptr(m))
-            call("crimac_meta_inject_fwd", ptr(m), ptr(wm), ptr(logits), B, H, W, self.n_classes, 1 if softmax else 0)
+            call("crimac_head_meta_fwd", self.prec, cur.p, cur.ld, ptr(self.P["conv_final.weight"]),
+                 ptr(self.P["conv_final.bias"]), ptr(meta), self.meta_channels, *self._mlp(), ptr(logits), B, H, W,
+                 self.n_classes, 1 if softmax else 0, bn_scale, bn_shift)
             saved["meta"] = meta
+        else:
+            call("crimac_head_fwd", self.prec, cur.p, cur.ld, self.sf, ptr(self.P["conv_final.weight"]),
+                 ptr(self.P["conv_final.bias"]), ptr(logits), B, H, W, self.n_classes, 1 if softmax else 0, bn_scale, bn_shift)
         saved["head_in"] = cur if head_bn is None else None
         self.saved = saved if training else None
         if training:
@@ -1451,28 +1441,20 @@ class UNetEngine:
         head_fused = self.fuse_bn_bwd and D >= 2
         if head_in is None and not head_fused:
             raise RuntimeError("head input was not materialised (fuse_head_bn) but the fused BatchNorm sums are off")
-        w_head, g_head = ptr(self.P["conv_final.weight"]), self.G["conv_final.weight"]
+        bnb = self._bnb_args(self.dec[D - 2][1], s[f"d{D - 2}"][4] if head_fused else None)
+        x_args = (head_in.p if head_in is not None else None, head_in.ld if head_in is not None else 0)
         if self.lmi:
-            # metadata column + perceptron first (they only need dlogits), then the 64-channel head on the packed columns
-            w64, wm = self._lmi_weights()
-            g64 = self._buf("lmi.g64", (self.n_classes, self.sf), torch.float32)
-            gwm = self._buf("lmi.gwm", (self.n_classes,), torch.float32)
-            g64.zero_()
-            gwm.zero_()
+            # one pass over dlogits: da, conv_final's gradients in place ([nc, 65]: column 64 the metadata column) and the
+            # perceptron's (all accumulated into the zeroed flat gradient buffer)
             pre = "post_processing_weights.main."
-            call("crimac_meta_bwd", ptr(dlogits), ptr(s["meta"]), self.meta_channels, B, H, W, self.n_classes, ptr(wm),
-                 *self._mlp(), ptr(gwm), *[ptr(self.G[pre + k]) for k in
-                                          ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias")])
-            w_head, g_head = ptr(w64), g64
-        call("crimac_head_bwd", self.prec, ptr(dlogits), head_in.p if head_in is not None else None,
-             head_in.ld if head_in is not None else 0, self.sf,
-             w_head, d_cur.p, d_cur.ld, ptr(g_head),
-             ptr(self.G["conv_final.bias"]), B, H, W, self.n_classes,
-             *self._bnb_args(self.dec[D - 2][1], s[f"d{D - 2}"][4] if head_fused else None))
-        if self.lmi:
-            gw = self.G["conv_final.weight"].view(self.n_classes, self.sf + 1)
-            gw[:, :self.sf].copy_(g64)
-            gw[:, self.sf].copy_(gwm)
+            call("crimac_head_meta_bwd", self.prec, ptr(dlogits), *x_args, ptr(self.P["conv_final.weight"]), d_cur.p,
+                 d_cur.ld, ptr(self.G["conv_final.weight"]), ptr(self.G["conv_final.bias"]), ptr(s["meta"]),
+                 self.meta_channels, *self._mlp(),
+                 *[ptr(self.G[pre + k]) for k in ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias")],
+                 B, H, W, self.n_classes, *bnb)
+        else:
+            call("crimac_head_bwd", self.prec, ptr(dlogits), *x_args, self.sf, ptr(self.P["conv_final.weight"]), d_cur.p,
+                 d_cur.ld, ptr(self.G["conv_final.weight"]), ptr(self.G["conv_final.bias"]), B, H, W, self.n_classes, *bnb)
         skip_grad = {}
         cur_done = head_fused            # BatchNorm-backward sums of d_cur's block already taken by its producer
         for j in reversed(range(D - 1)):

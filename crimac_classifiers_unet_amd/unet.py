@@ -129,7 +129,8 @@ class UNet_Baseline(nn.Module):
                             output gradients, the up-half of d(concat) and the input-gradient weight planes in plain
                             fp16, conv outputs and activation gradients in fp32 (ReLU / max-pool decisions as in 'h3p'),
                             weight gradients on the hi plane of the saved activations; every gradient tensor inside the
-                            tolerance 'h3p' is held to (worst 0.76 of it); 1.39x the training rate of 'h3p'
+                            tolerance 'h3p' is held to (worst 0.76 of it); 1.39x the training rate of 'h3p'.  Covers
+                            UNet_LateMetInject too (not the narrow nets and up_mode='upsample': 'h3p' there)
                  'fp16'  -- fp16 activations / MFMA, fp32 accumulate, loss-scaled gradients with overflow skip
                             (BASELINE configs[4]); same kernels and rate as 'bf16'
       infer_precision: precision of EVAL-mode forwards (``model.eval()``; ``predict_softmax``; tiled inference).

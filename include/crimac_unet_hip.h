@@ -130,7 +130,7 @@ extern "C" {
  * points changes, and a binding must refuse a library whose version differs from the header it was written against (an
  * older build that happens to export every symbol would walk a descriptor array with the wrong stride).
  * crimac_layer_desc_size() is sizeof(crimac_layer_desc) as the library was compiled. */
-#define CRIMAC_ABI_VERSION 14
+#define CRIMAC_ABI_VERSION 15
 int crimac_version(void);
 int crimac_layer_desc_size(void);
 const char* crimac_last_error(void);
@@ -647,6 +647,28 @@ int crimac_meta_bwd(const float* dlogits, const float* meta, int Cm, int B, int 
                     const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
                     const float* b3, float* dwm, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3,
                     void* stream);
+/* The late-injection head in one launch each way.  Forward (UNet_LateMetInject.forward's tail, unet.py:346-391; the training and
+ * prediction call sites pipeline.py:170-174 and pipeline.py:210-216).  x, x_ld, bn_scale / bn_shift and prec as for
+ * crimac_head_fwd with Cin = 64; w = conv_final.weight [ncls][65] as torch stores it (columns 0..63 the head, column 64
+ * the metadata column), b its bias; meta [B][Cm][H][W] fp32, Cm in 1..8, the perceptron's tensors as for
+ * crimac_meta_mlp_fwd.  logits = softmax?(w[:, :64] . act(x) + b + w[:, 64] * m): per pixel the fp32 operations of
+ * crimac_head_fwd, crimac_meta_mlp_fwd and crimac_meta_inject_fwd in that order, hence their logits bit for bit; m is never
+ * stored, the logits are written once, and a pixel's result does not depend on the batch around it. */
+int crimac_head_meta_fwd(int prec, const void* x, long x_ld, const float* w, const float* b, const float* meta, int Cm,
+                         const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                         const float* b3, float* logits, int B, int H, int W, int ncls, int softmax,
+                         const float* bn_scale, const float* bn_shift, void* stream);
+/* Its backward in ONE pass over dlogits: dx = the `da` of the last decoder activation (+ the fused BatchNorm-backward
+ * sums; x, dx, bnb_* and prec as for crimac_head_bwd with Cin = 64), dw = conv_final.weight's gradient [ncls][65] written
+ * in place at row stride 65 (columns 0..63 from the head, column 64 = sum dlogits * m), db [ncls], and the six perceptron
+ * gradients as crimac_meta_bwd's.  Every gradient output is ACCUMULATED (caller zeroes), as crimac_head_bwd's and
+ * crimac_meta_bwd's are. */
+int crimac_head_meta_bwd(int prec, const float* dlogits, const void* x, long x_ld, const float* w, void* dx, long dx_ld,
+                         float* dw, float* db, const float* meta, int Cm, const float* w1, const float* b1,
+                         const float* w2, const float* b2, const float* w3, const float* b3, float* gw1, float* gb1,
+                         float* gw2, float* gb2, float* gw3, float* gb3, int B, int H, int W, int ncls, const void* bnb_y,
+                         long bnb_y_ld, const float* bnb_vec, long bnb_stride, double* stat_sum, double* stat_sumsq,
+                         int stat_replicas, void* stream);
 
 /* ---- on-GPU training augmentation + data transform (BASELINE configs[4]) -------------------------- */
 
