@@ -443,7 +443,8 @@ int crimac_sgd_momentum(float* p, float* g, float* v, long n, float lr, float mo
  * the n gradients is inf / NaN (caller zeroes state[0] before every step); crimac_sgd_momentum_guarded then leaves
  * p and v untouched for that step and counts it in state[1].  No host synchronisation is involved: the caller
  * reads state[1] whenever it flushes its loss log and adapts the scale it passes as crimac_wce_bwd's `upstream`
- * (and divides out again through `grad_scale`). */
+ * (and divides out again through `grad_scale`).  A skipped step leaves g as it is, also with zero_grad = 1: the caller
+ * clears its gradient buffer itself before the next backward pass. */
 int crimac_grad_overflow_flag(const float* g, long n, int* state, void* stream);
 int crimac_sgd_momentum_guarded(float* p, float* g, float* v, long n, float lr, float momentum,
                                 float grad_scale, int zero_grad, int* state, void* stream);
