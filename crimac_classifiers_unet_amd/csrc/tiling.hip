@@ -271,6 +271,71 @@ __global__ __launch_bounds__(256) void pr_histogram_kernel(const float* __restri
   }
 }
 
+// The same histograms for every foreground class selected by `mask` (bit c = class c), hist [ncls][2][CRIMAC_PR_BINS]:
+// one softmax per pixel -- max, expf, the order of the sum and the division as above, so row 1 is that kernel's result.
+// Evaluation data is skewed: every below-seabed pixel is bin 0 of `neg` of every class, and a probability under 2^-14 is
+// a float16 subnormal, 6e-8 wide bins where most background pixels of a trained network collect.  So the counters of
+// bins [0, PR_LDS_BINS) live in LDS, [selected class][pos, neg][bin]: a wave first adds the lanes that share the first
+// active lane's counter as ONE LDS atomic (a run of seabed or background pixels is the whole wave), the other lanes add
+// their own; the workgroup adds its non-zero counters to global memory once, at the end.  From 2^-14 up a float16 bin is
+// no wider than 2^-10 of its value, pixels spread over many bins, and each takes one global atomic as above.
+// Exact: 32-bit counters everywhere (a workgroup sees at most npix / gridDim.x + 256 pixels).
+constexpr int PR_LDS_BINS = 1024;
+__global__ __launch_bounds__(256) void pr_histogram_classes_kernel(const float* __restrict__ logits, int ncls,
+                                                                   const void* __restrict__ labels, int lbytes,
+                                                                   long npix, long HW, unsigned int mask,
+                                                                   unsigned int* __restrict__ hist) {
+  extern __shared__ unsigned int pr_low[];   // [popc(mask)][2][PR_LDS_BINS]
+  const int n_low = __popc(mask) * 2 * PR_LDS_BINS;
+  for (int i = threadIdx.x; i < n_low; i += 256) pr_low[i] = 0u;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < npix; p += (long)gridDim.x * blockDim.x) {
+    long l = lbytes == 8 ? ((const long long*)labels)[p] : lbytes == 4 ? ((const int*)labels)[p]
+                                                                       : ((const short*)labels)[p];
+    if (l == -70 || l == -30 || l == -100 || l == -10) continue;
+    const bool seabed = l == -50;
+    float z[8], den = 0.f;
+    if (!seabed) {
+      const long b = p / HW, hw = p % HW;
+      float mx = -INFINITY;
+#pragma unroll
+      for (int o = 0; o < 8; ++o)
+        if (o < ncls) { z[o] = logits[(b * ncls + o) * HW + hw]; mx = fmaxf(mx, z[o]); }
+#pragma unroll
+      for (int o = 0; o < 8; ++o)
+        if (o < ncls) { z[o] = expf(z[o] - mx); den += z[o]; }
+    }
+#pragma unroll
+    for (int c = 1; c < 8; ++c) {
+      if (!((mask >> c) & 1u)) continue;       // (uniform; the entry point admits bits 1 .. ncls-1 only)
+      const float prob = seabed ? 0.f : z[c] / den;
+      const _Float16 h = (_Float16)prob;
+      unsigned short bits = *reinterpret_cast<const unsigned short*>(&h);
+      if (bits > 0x3C00) bits = CRIMAC_PR_NAN_BIN;
+      const int side = (!seabed && l == c) ? 0 : 1;
+      if (bits < PR_LDS_BINS) {
+        const int key = ((__popc(mask & ((1u << c) - 1u)) * 2) + side) * PR_LDS_BINS + bits;
+        const int first = __builtin_amdgcn_readfirstlane(key);
+        const unsigned long long same = __ballot(key == first);
+        if (key != first) atomicAdd(&pr_low[key], 1u);
+        else if (lane == __ffsll(same) - 1) atomicAdd(&pr_low[key], (unsigned int)__popcll(same));
+      } else {
+        atomicAdd(&hist[((long)c * 2 + side) * CRIMAC_PR_BINS + bits], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n_low; i += 256) {
+    const unsigned int v = pr_low[i];
+    if (!v) continue;
+    unsigned int m = mask;                     // class of slot i / (2 * PR_LDS_BINS): that many set bits of the mask down
+    for (int k = i / (2 * PR_LDS_BINS); k > 0; --k) m &= m - 1u;
+    const int c = __ffs(m) - 1;
+    atomicAdd(&hist[(long)c * 2 * CRIMAC_PR_BINS + (i / PR_LDS_BINS % 2) * CRIMAC_PR_BINS + i % PR_LDS_BINS], v);
+  }
+}
+
 // RAW evaluation crops (the per-patch crop of the reference's gridded test Dataset, before any transform): for patch p
 //   data_out [P][C][ph][pw] fp32 linear sv, labels_out [P][ph][pw] int16 raw annotation ids
 // from the resident chunk data [C][Wd][H] / labels [Wd][H].  flavour 0 = get_crop_zarr (dataset.py:358-407): the patch
@@ -399,6 +464,24 @@ extern "C" int crimac_pr_histogram(const float* logits, int ncls, const void* la
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(pr_histogram_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, ncls,
                      labels, label_bytes, npix, HW, hist_pos, hist_neg);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}
+
+extern "C" int crimac_pr_histogram_classes(const float* logits, int ncls, const void* labels, int label_bytes, int B,
+                                           int H, int W, unsigned int class_mask, unsigned int* hist, void* stream) {
+  CRIMAC_REQUIRE(logits && labels && hist && B > 0 && H > 0 && W > 0 && ncls >= 2 && ncls <= 8,
+                 "pr_histogram_classes: bad arguments");
+  CRIMAC_REQUIRE(label_bytes == 2 || label_bytes == 4 || label_bytes == 8, "pr_histogram_classes: label_bytes=%d",
+                 label_bytes);
+  CRIMAC_REQUIRE(class_mask != 0u && !(class_mask & 1u) && !(class_mask >> ncls),
+                 "pr_histogram_classes: class_mask=0x%x must select foreground classes 1 .. %d only", class_mask, ncls - 1);
+  const long HW = (long)H * W, npix = B * HW;
+  long blocks = (npix + 1023) / 1024;          // four pixels or more per thread: fewer workgroups flush their LDS counters
+  if (blocks > 1024) blocks = 1024;
+  const size_t lds = (size_t)__builtin_popcount(class_mask) * 2 * PR_LDS_BINS * sizeof(unsigned int);   // <= 56 KiB
+  hipLaunchKernelGGL(pr_histogram_classes_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits,
+                     ncls, labels, label_bytes, npix, HW, class_mask, hist);
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
 }

@@ -59,18 +59,22 @@ def _is_use_metadata(meta_channels):
 def validate_model_survey_zarr(readers, segpipe, meta_channels, patch_size, patch_overlap, eval_mode, batch_size,
                                num_workers, save_path_metrics, save_path_plot, preload_n_pings=0, survey="survey",
                                dataset_cls=None, data_transform_factory=None, label_transform_factory=None,
-                               worker_init_fn=None, tiled=False, **kwargs):
+                               worker_init_fn=None, tiled=False, eval_classes=None, **kwargs):
     """evaluate.py:39-81: one zarr file = one survey; gridded patches of the whole survey -> PR curve / F1.
     ``tiled=True``: on the tiled GPU path (``tiled_inference.evaluate_survey``); ``preload_n_pings`` > 0 is then the
-    chunk size (0: the default of ``predict_survey``), and no factory is needed."""
+    chunk size (0: the default of ``predict_survey``), and no factory is needed.
+    ``eval_classes`` (foreground class indices, e.g. ``(1, 2)``; ``tiled`` or the segpipe's ``gpu_metrics``): the PR
+    curve / F1 of each class from the one pass -- ``{class: metrics}``, files ``{survey}_test_sandeel.csv``,
+    ``{survey}_test_other.csv``, ``{survey}_pr_sandeel.png`` ..."""
+    eval_classes = _eval_classes(eval_classes, tiled, segpipe)
     if tiled:
         from .tiled_inference import evaluate_survey
         if not segpipe.model_is_loaded:
             segpipe.load_model_params()
         assert len(readers) == 1, "Current evaluation code assumes one zarr file contains an entire survey"
         hp, hn = evaluate_survey(readers[0], segpipe, patch_size, patch_overlap, batch_size, preload_n_pings,
-                                 eval_mode=eval_mode)
-        return _tiled_metrics(segpipe, hp, hn, save_path_metrics, save_path_plot, survey)
+                                 eval_mode=eval_mode, classes=eval_classes)
+        return _tiled_metrics(segpipe, hp, hn, save_path_metrics, save_path_plot, survey, eval_classes)
     dataset_cls, dtf, ltf = _reference_factories(dataset_cls, data_transform_factory, label_transform_factory, False)
     assert len(readers) == 1, "Current evaluation code assumes one zarr file contains an entire survey"
     assert preload_n_pings == 0, "Current evaluation code for zarr only works when 'preloading_n_pings' = 0"
@@ -87,27 +91,28 @@ def validate_model_survey_zarr(readers, segpipe, meta_channels, patch_size, patc
                                 worker_init_fn=worker_init_fn)
         metrics = segpipe.validate_model_testing(
             dataloader, save_path_metrics=os.path.join(save_path_metrics, f"{survey}_test.csv"),
-            save_path_plot=os.path.join(save_path_plot, f"{survey}_pr.png"))
+            save_path_plot=os.path.join(save_path_plot, f"{survey}_pr.png"), **_classes_kw(eval_classes))
     return metrics
 
 
 def validate_model_survey_memm(readers, segpipe, meta_channels, patch_size, patch_overlap, eval_mode, batch_size,
                                num_workers, save_path_metrics, save_path_plot, survey="survey", dataset_cls=None,
                                data_transform_factory=None, label_transform_factory=None, worker_init_fn=None,
-                               tiled=False, **kwargs):
+                               tiled=False, eval_classes=None, **kwargs):
     """evaluate.py:84-117: one gridded Dataset per echogram, concatenated -> PR curve / F1 of the survey.
     ``tiled=True``: the whole survey on the tiled GPU path (``tiled_inference.evaluate_echograms_memm``: forward batches
     packed across the echograms, one feed; with several ranks the groups of echograms are dealt to the ranks and the
     histograms all-reduced once; a model with metadata planes goes echogram by echogram unless ``pack_metadata=True`` is
-    among ``kwargs``); no factory is needed."""
+    among ``kwargs``); no factory is needed.  ``eval_classes``: as ``validate_model_survey_zarr``."""
+    eval_classes = _eval_classes(eval_classes, tiled, segpipe)
     if tiled:
         from .tiled_inference import evaluate_echograms_memm
         if not segpipe.model_is_loaded:
             segpipe.load_model_params()
         hp, hn = evaluate_echograms_memm(readers, segpipe, patch_size, patch_overlap, batch_size, eval_mode=eval_mode,
-                                         meta_channels=meta_channels or None,
+                                         meta_channels=meta_channels or None, classes=eval_classes,
                                          **{k: kwargs[k] for k in ("pack_metadata",) if k in kwargs})
-        return _tiled_metrics(segpipe, hp, hn, save_path_metrics, save_path_plot, survey)
+        return _tiled_metrics(segpipe, hp, hn, save_path_metrics, save_path_plot, survey, eval_classes)
     dataset_cls, dtf, ltf = _reference_factories(dataset_cls, data_transform_factory, label_transform_factory, True)
     frequencies = segpipe.frequencies
     data_transform = dtf(_is_use_metadata(meta_channels))
@@ -120,14 +125,46 @@ def validate_model_survey_memm(readers, segpipe, meta_channels, patch_size, patc
                             worker_init_fn=worker_init_fn)
     return segpipe.validate_model_testing(
         dataloader, save_path_metrics=os.path.join(save_path_metrics, f"{survey}_test.csv"),
-        save_path_plot=os.path.join(save_path_plot, f"{survey}_pr.png"))
+        save_path_plot=os.path.join(save_path_plot, f"{survey}_pr.png"), **_classes_kw(eval_classes))
 
 
-def _tiled_metrics(segpipe, hist_pos, hist_neg, save_path_metrics, save_path_plot, survey):
+def _eval_classes(eval_classes, tiled, segpipe):
+    """``eval_classes`` of the two functions above -> None or a checked tuple; refused before anything is read where no
+    per-class form exists: the sklearn path (neither ``tiled`` nor ``gpu_metrics``) scores the sandeel class only."""
+    if eval_classes is None:
+        return None
+    if not (tiled or getattr(segpipe, "gpu_metrics", False)):
+        raise ValueError(f"eval_classes={eval_classes!r} (--classes) needs tiled=True (--tiled) or gpu_metrics: the "
+                         "per-class PR curves come from the GPU histograms, the sklearn path scores the sandeel class only")
+    from .tiled_inference import check_classes
+    return check_classes(eval_classes, segpipe.model.n_classes)
+
+
+def _classes_kw(eval_classes):
+    return {} if eval_classes is None else {"classes": eval_classes}
+
+
+def parse_classes(text, n_classes=None):
+    """``--classes``: ``"1,2"`` -> (1, 2); ``"all"`` -> every foreground class of an ``n_classes`` model (None: the string
+    'all' is handed back for the caller to resolve once the model exists)."""
+    if text is None:
+        return None
+    if isinstance(text, str):
+        if text.strip().lower() == "all":
+            return "all" if n_classes is None else tuple(range(1, n_classes))
+        try:
+            return tuple(int(t) for t in text.split(","))
+        except ValueError:
+            raise ValueError(f"--classes {text!r}: comma-separated class indices such as 1,2, or 'all'") from None
+    return tuple(text)
+
+
+def _tiled_metrics(segpipe, hist_pos, hist_neg, save_path_metrics, save_path_plot, survey, eval_classes=None):
     return segpipe.validate_model_testing_from_histograms(
         hist_pos, hist_neg,
         save_path_metrics=None if save_path_metrics is None else os.path.join(save_path_metrics, f"{survey}_test.csv"),
-        save_path_plot=None if save_path_plot is None else os.path.join(save_path_plot, f"{survey}_pr.png"))
+        save_path_plot=None if save_path_plot is None else os.path.join(save_path_plot, f"{survey}_pr.png"),
+        **_classes_kw(eval_classes))
 
 
 def main(argv=None, data_partition_factory=None, factories=None):
@@ -159,6 +196,9 @@ def main(argv=None, data_partition_factory=None, factories=None):
     ap.add_argument("--tiled", action="store_true", default=None,
                     help="evaluate on the tiled GPU path: chunk, crops, transforms and PR histograms stay on the GPU; "
                          "no Dataset / transform factories, no DataLoader workers")
+    ap.add_argument("--classes", dest="eval_classes", default=None,
+                    help="foreground classes to score from the one pass, e.g. 1,2 ('all': every foreground class): one "
+                         "csv / plot / F1 line per class (_sandeel, _other, _class{k}); needs --tiled or gpu_metrics")
     args = ap.parse_args(argv)
     config = yaml.safe_load(open(args.yaml_path))
     for k, v in vars(args).items():                     # command line takes precedence (utils/general.py:128-136)
@@ -170,6 +210,10 @@ def main(argv=None, data_partition_factory=None, factories=None):
     if config["data_mode"] not in ("zarr", "memm"):
         raise ValueError('data_mode not in ["zarr", "memm"]')
     tiled = bool(config.pop("tiled", False))
+    eval_classes = parse_classes(config.pop("eval_classes", None))
+    if eval_classes is not None and not (tiled or config.get("gpu_metrics")):
+        raise ValueError("--classes needs --tiled or gpu_metrics: the per-class PR curves come from the GPU histograms, the "
+                         "sklearn path scores the sandeel class only")
     if tiled:
         factories = factories or (None, None, None)
     if factories is None:
@@ -192,6 +236,9 @@ def main(argv=None, data_partition_factory=None, factories=None):
     np.random.seed(seed); random.seed(seed); torch.manual_seed(seed)
     segpipe = SegPipeUNet(**config, experiment_name=experiment_name)
     segpipe.load_model_params(checkpoint_path=config["checkpoint_path"])
+    if eval_classes == "all":
+        eval_classes = parse_classes("all", segpipe.model.n_classes)
+    config["eval_classes"] = eval_classes
     print(f'\nLoading {config["data_mode"]} data partition object...')
     t0 = time.time()
     partition = data_partition_factory(**config)

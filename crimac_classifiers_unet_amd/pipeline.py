@@ -15,6 +15,7 @@ identical argmax masks), ``loss_flush`` (how often queued train losses are hande
 """
 from __future__ import annotations
 
+import os
 from pathlib import Path
 
 import numpy as np
@@ -52,7 +53,7 @@ class SegPipe:
                  save_model_params, meta_channels, late_meta_inject, eval_mode, experiment_name,
                  precision="bf16", infer_precision="h3p", loss_flush=50, gpu_augment=False, random_seed=0,
                  gpu_metrics=False, gpu_label_transform=False, sync_bn=False, pin_batches=True,
-                 release_batch_pages=True, collate_float32=True, gpu_meta_input=False, **kwargs):
+                 release_batch_pages=True, collate_float32=True, gpu_meta_input=False, eval_classes=None, **kwargs):
         assert not (save_model_params and (checkpoint_dir is None))
         self.model = None
         self.model_is_loaded = False
@@ -132,6 +133,14 @@ class SegPipe:
         # gpu_metrics: in-training validation builds the PR curve / F1 from GPU histograms instead of
         # shipping every pixel's probability to sklearn (same numbers; the logger gets no pr_curve)
         self.gpu_metrics = bool(gpu_metrics)
+        # eval_classes (with gpu_metrics; e.g. [1, 2]): in-training validation builds the histograms of these foreground
+        # classes in the same pass and also logs test/F1_score_{name}, test/precision_{name}, test/recall_{name} for the
+        # classes other than sandeel; best.pt and the returned metrics stay the sandeel class's (checked against the
+        # model's classes at the first validation)
+        self.eval_classes = None if eval_classes is None else tuple(eval_classes)
+        if self.eval_classes is not None and not self.gpu_metrics:
+            raise ValueError("eval_classes needs gpu_metrics: the per-class PR curves come from the GPU histograms, the "
+                             "sklearn path scores the sandeel class only")
 
     # ------------------------------------------------------------------------------------------
     def _warn_infer_precision(self):
@@ -434,13 +443,17 @@ class SegPipe:
     # -- histogram form of the same metrics: no per-pixel vectors leave the GPU --------------------
     PR_BINS = hip.PR_BINS      # CRIMAC_PR_BINS: float16 bit patterns of [0, 1] are 0 .. 0x3C00
 
-    def get_pr_histograms_dataloader(self, dataloader, criterion=None, disable_tqdm=True):
+    def get_pr_histograms_dataloader(self, dataloader, criterion=None, disable_tqdm=True, classes=None):
         """GPU form of get_predictions_dataloader + the masking of validate_model_training
         (pipeline.py:242-282, :317-320): returns (hist_pos, hist_neg, mean_loss) where hist_*[k] counts
-        the valid pixels whose float16 sandeel probability has bit pattern k."""
-        from .hip import call, ptr
+        the valid pixels whose float16 sandeel probability has bit pattern k.
+        ``classes`` (foreground class indices, e.g. ``(1, 2)``): hist_pos / hist_neg are [K, 16384], row i of class
+        ``classes[i]`` (``crimac_pr_histogram_classes``: one pass over the logits for all of them; a below-seabed pixel
+        counts in hist_neg of every class with probability 0)."""
+        from .tiled_inference import add_pr_histograms, model_classes, new_histograms, split_histograms
         dev = self.device
-        hist = torch.zeros(2, self.PR_BINS, dtype=torch.int32, device=dev)
+        classes = model_classes(classes, self.model)
+        hist = new_histograms(dev, classes, self.model)
         sum_loss = None
         world, rank, _ = parallel.env_world()
         if not (torch.distributed.is_available() and torch.distributed.is_initialized()):
@@ -462,19 +475,15 @@ class SegPipe:
                 if criterion is not None:
                     loss = criterion(logits, self.set_label_ignore_val(labels.clone().long()))
                     sum_loss = loss if sum_loss is None else sum_loss + loss
-                B, nc, H, W = logits.shape
-                call("crimac_pr_histogram", ptr(logits), nc, ptr(labels), labels.element_size(), B, H, W,
-                     ptr(hist[0]), ptr(hist[1]))
-        if world > 1:                          # the histograms ARE the metric's sufficient statistic: 128 KB all-reduce
+                add_pr_histograms(logits, labels, hist, classes)
+        if world > 1:                         # the histograms ARE the metric's sufficient statistic: 128 KB all-reduce
             torch.distributed.all_reduce(hist)
             sl = torch.zeros(1, dtype=torch.float64, device=dev) if sum_loss is None else sum_loss.double().reshape(1)
             torch.distributed.all_reduce(sl)
             sum_loss = sl[0]
-        h = hist.cpu().numpy().astype(np.int64)
-        if h[:, self.PR_BINS - 1].any():      # CRIMAC_PR_NAN_BIN: sklearn raises on NaN scores as well
-            raise ValueError("Input contains NaN (sandeel probabilities of the validation set)")
+        hp, hn = split_histograms(hist.cpu().numpy(), classes)      # (raises on CRIMAC_PR_NAN_BIN, as sklearn on NaN scores)
         mean_loss = (float(sum_loss) if sum_loss is not None else 0.0) / len(dataloader)
-        return h[0], h[1], mean_loss
+        return hp, hn, mean_loss
 
     @staticmethod
     def compute_evaluation_metrics_from_histograms(hist_pos, hist_neg):
@@ -512,7 +521,17 @@ class SegPipe:
         """Reference pipeline.py:305-341."""
         multi = torch.distributed.is_available() and torch.distributed.is_initialized() \
             and torch.distributed.get_world_size() > 1
-        if self.gpu_metrics or multi:
+        others = {}
+        if self.eval_classes is not None:
+            # one pass for every class: sandeel (always, it chooses best.pt) + the classes asked for
+            from .tiled_inference import class_name
+            cls = (SANDEEL,) + tuple(c for c in self.eval_classes if c != SANDEEL)
+            hp, hn, loss_test = self.get_pr_histograms_dataloader(dataloader_test, criterion=criterion, classes=cls)
+            metrics = self.compute_evaluation_metrics_from_histograms(hp[0], hn[0])
+            others = {class_name(c): self.compute_evaluation_metrics_from_histograms(hp[i], hn[i])
+                      for i, c in enumerate(cls) if i}
+            labels = preds = None
+        elif self.gpu_metrics or multi:
             # N > 1: validation is sharded over the ranks; only the histogram form has a small sufficient statistic
             # to exchange (the per-pixel vectors of the sklearn form would have to be gathered on one rank)
             hp, hn, loss_test = self.get_pr_histograms_dataloader(dataloader_test, criterion=criterion)
@@ -533,6 +552,11 @@ class SegPipe:
             logger.add_scalar(tag="test/recall", scalar_value=metrics["recall"][argmax_F1],
                               global_step=iter_step)
             logger.add_scalar(tag="test/loss", scalar_value=loss_test, global_step=iter_step)
+            for name, m in others.items():
+                best = np.argmax(m["F1"])
+                for tag in ("F1_score", "precision", "recall"):
+                    logger.add_scalar(tag=f"test/{tag}_{name}", scalar_value=m["F1" if tag == "F1_score" else tag][best],
+                                      global_step=iter_step)
             if hasattr(logger, "add_pr_curve") and labels is not None:
                 logger.add_pr_curve(tag="test/pr_curve", labels=labels, predictions=preds,
                                     global_step=iter_step)
@@ -543,12 +567,19 @@ class SegPipe:
                 torch.save(self.model.state_dict(), Path(self.checkpoint_dir) / "best.pt")
         return metrics
 
-    def validate_model_testing(self, dataloader, save_path_metrics, save_path_plot):
+    def validate_model_testing(self, dataloader, save_path_metrics, save_path_plot, classes=None):
         """Test-set evaluation (reference pipeline.py:343-376): PR curve / F1 of the SANDEEL probability over the
         valid pixels of ``dataloader``; the curve is written as csv (columns as the reference's DataFrame:
-        precision, recall, thresholds, F1; the last threshold is NaN) and, if asked for, drawn."""
+        precision, recall, thresholds, F1; the last threshold is NaN) and, if asked for, drawn.
+        ``classes`` (``gpu_metrics`` only): as ``validate_model_testing_from_histograms``."""
+        if classes is not None and not self.gpu_metrics:
+            raise ValueError("validate_model_testing(classes=...) needs gpu_metrics: the per-class PR curves come from the "
+                             "GPU histograms, the sklearn path scores the sandeel class only")
         if not self.model_is_loaded:
             self.load_model_params()
+        if classes is not None:
+            hp, hn, _ = self.get_pr_histograms_dataloader(dataloader, disable_tqdm=False, classes=classes)
+            return self.validate_model_testing_from_histograms(hp, hn, save_path_metrics, save_path_plot, classes=classes)
         if self.gpu_metrics:
             hp, hn, _ = self.get_pr_histograms_dataloader(dataloader, disable_tqdm=False)
             metrics = self.compute_evaluation_metrics_from_histograms(hp, hn)
@@ -559,13 +590,29 @@ class SegPipe:
             metrics = self.compute_evaluation_metrics(labels=labels, preds=preds)
         return self._finish_testing(metrics, save_path_metrics, save_path_plot)
 
-    def validate_model_testing_from_histograms(self, hist_pos, hist_neg, save_path_metrics, save_path_plot):
+    def validate_model_testing_from_histograms(self, hist_pos, hist_neg, save_path_metrics, save_path_plot, classes=None):
         """The tail of ``validate_model_testing`` for a caller that already holds the PR histograms of the test set
-        (``tiled_inference.evaluate_survey`` / ``evaluate_echogram_memm``): metrics, csv, plot, the printed F1."""
-        metrics = self.compute_evaluation_metrics_from_histograms(np.asarray(hist_pos), np.asarray(hist_neg))
-        return self._finish_testing(metrics, save_path_metrics, save_path_plot)
+        (``tiled_inference.evaluate_survey`` / ``evaluate_echogram_memm``): metrics, csv, plot, the printed F1.
+        ``classes``: hist_pos / hist_neg are [K, 16384], row i of class ``classes[i]`` (what those flows return with
+        ``classes``) -> ``{class: metrics}``; one csv and one plot per class, the class's name in front of the extension
+        (``per_class_path``), and one ``F1 score (name): ...`` line per class."""
+        from .tiled_inference import check_classes, class_name
+        hist_pos, hist_neg = np.asarray(hist_pos), np.asarray(hist_neg)
+        if classes is None:
+            metrics = self.compute_evaluation_metrics_from_histograms(hist_pos, hist_neg)
+            return self._finish_testing(metrics, save_path_metrics, save_path_plot)
+        classes = check_classes(classes, self.model.n_classes)
+        if hist_pos.shape != (len(classes), self.PR_BINS) or hist_neg.shape != hist_pos.shape:
+            raise ValueError(f"hist_pos {hist_pos.shape} / hist_neg {hist_neg.shape}: classes={classes} takes "
+                             f"{(len(classes), self.PR_BINS)} each")
+        out = {}
+        for c, hp, hn in zip(classes, hist_pos, hist_neg):
+            metrics = self.compute_evaluation_metrics_from_histograms(hp, hn)
+            out[c] = self._finish_testing(metrics, per_class_path(save_path_metrics, c), per_class_path(save_path_plot, c),
+                                          name=class_name(c))
+        return out
 
-    def _finish_testing(self, metrics, save_path_metrics, save_path_plot):
+    def _finish_testing(self, metrics, save_path_metrics, save_path_plot, name=None):
         metrics["thresholds"] = np.append(np.asarray(metrics["thresholds"], dtype=np.float64), np.nan)
         if parallel.env_world()[1] == 0:
             if save_path_metrics is not None:
@@ -573,8 +620,17 @@ class SegPipe:
             if save_path_plot is not None:
                 plot_pr_curve(metrics, save_path_plot)
         F1 = metrics["F1"]
-        print(f"F1 score: {F1[np.argmax(F1)]}")
+        print(f"F1 score{'' if name is None else f' ({name})'}: {F1[np.argmax(F1)]}")
         return metrics
+
+
+def per_class_path(path, c):
+    """``survey_test.csv`` -> ``survey_test_sandeel.csv`` (class 1) / ``_other`` (2) / ``_class{k}``; None stays None."""
+    if path is None:
+        return None
+    from .tiled_inference import class_name
+    root, ext = os.path.splitext(str(path))
+    return f"{root}_{class_name(c)}{ext}"
 
 
 def write_pr_csv(metrics, path):

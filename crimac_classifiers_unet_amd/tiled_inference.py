@@ -283,7 +283,7 @@ class ChunkPredictor:
                  ptr(x), 16)
         return x
 
-    def evaluate(self, grid, hist, eval_mode="all", boxes=None, predict_fn=None, on_batch=None):
+    def evaluate(self, grid, hist, eval_mode="all", boxes=None, predict_fn=None, on_batch=None, classes=None):
         """Test-set evaluation of the patches of ``grid`` ([P, 2] global centres) on a ``wide`` chunk: what the reference's
         gridded test Dataset + ``get_predictions_dataloader`` + the masking of ``validate_model_testing`` do per patch
         (batch/dataset.py:207-242; pipeline.py:242-282, :347-353), accumulated into ``hist`` (int32 [2, 16384] on the GPU:
@@ -302,7 +302,11 @@ class ChunkPredictor:
         with or without metadata planes.
         ``predict_fn(x_nhwc, P, H, W) -> logits [P, 3, H, W]`` replaces the network; ``on_batch(centres [P, 2] numpy,
         labels int16 [P, H, W], logits [P, 3, H, W])`` sees the transformed labels and the logits of every batch, on the
-        GPU (tests)."""
+        GPU (tests).
+        ``classes`` (a tuple of foreground class indices, ``check_classes``): ``hist`` is int32 [n_classes, 2, 16384] and
+        row c takes the float16 probability of class c, by label == c / the rest, for every c of ``classes`` in one
+        ``crimac_pr_histogram_classes`` pass per batch; a below-seabed pixel counts in ``neg`` of each with probability 0."""
+        classes = model_classes(classes, self.engine, hist)
         if not self.wide:
             raise ValueError("ChunkPredictor.evaluate needs a chunk loaded with wide=True (labels and seabed for every "
                              "ping a patch can touch)")
@@ -350,9 +354,7 @@ class ChunkPredictor:
                 logits, labels_t = raw_crops_to_logits(eng, raw, lab, cen64, predict_fn=predict_fn, split=True, **chain)
             if on_batch is not None:
                 on_batch(cen, labels_t, logits)
-            B, nc, H, W = logits.shape
-            call("crimac_pr_histogram", ptr(logits), nc, ptr(labels_t), labels_t.element_size(), B, H, W, ptr(hist[0]),
-                 ptr(hist[1]))
+            add_pr_histograms(logits, labels_t, hist, classes)
         return hist
 
 
@@ -1482,19 +1484,93 @@ def plan_eval_chunks(grid, n_pings, patch_size, preload_n_pings):
     return out
 
 
-def finish_histograms(hist, all_reduce=True):
+CLASS_NAMES = {1: "sandeel", 2: "other"}      # crimac_unet/constants.py:20-22; further foreground classes: class{k}
+
+
+def class_name(c):
+    return CLASS_NAMES.get(int(c), f"class{int(c)}")
+
+
+def check_classes(classes, n_classes, hist=None):
+    """``classes`` of the evaluation flows: None (the sandeel histograms, [2, 16384]) or foreground class indices in
+    1 .. n_classes - 1 without duplicates -> None / a tuple of ints; anything else: ValueError.  ``hist``: the histogram
+    tensor a caller handed in must have the form that goes with it, [2, 16384] / [n_classes, 2, 16384]."""
+    if classes is not None:
+        if isinstance(classes, (str, bytes)) or not hasattr(classes, "__iter__"):
+            raise ValueError(f"classes={classes!r}: a tuple of foreground class indices, e.g. (1, 2)")
+        got = tuple(classes)
+        if not got or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) for c in got):
+            raise ValueError(f"classes={classes!r}: a non-empty tuple of integer class indices")
+        got = tuple(int(c) for c in got)
+        bad = [c for c in got if not 1 <= c < n_classes]
+        if bad:
+            raise ValueError(f"classes={got}: {bad} outside the foreground classes 1 .. {n_classes - 1} of a "
+                             f"{n_classes}-class model (0 is the background)")
+        if len(set(got)) != len(got):
+            raise ValueError(f"classes={got}: a class is named twice")
+        classes = got
+    if hist is not None:
+        want = (2, PR_BINS) if classes is None else (n_classes, 2, PR_BINS)
+        if tuple(hist.shape) != want or hist.dtype != torch.int32 or not hist.is_contiguous():
+            raise ValueError(f"hist {tuple(hist.shape)} {hist.dtype}: classes={classes} takes contiguous int32 {want}")
+    return classes
+
+
+def model_classes(classes, model, hist=None):
+    """``check_classes`` against ``model.n_classes`` (a model or its engine); None asks nothing of the model."""
+    return None if classes is None else check_classes(classes, model.n_classes, hist)
+
+
+def new_histograms(dev, classes=None, model=None):
+    """Zeroed PR histograms on ``dev``: int32 [2, 16384], with ``classes`` [model.n_classes, 2, 16384]."""
+    shape = (2, PR_BINS) if classes is None else (model.n_classes, 2, PR_BINS)
+    return torch.zeros(*shape, dtype=torch.int32, device=dev)
+
+
+def add_pr_histograms(logits, labels, hist, classes=None):
+    """One batch into ``hist``: ``crimac_pr_histogram`` (sandeel, [2, 16384]) or, with ``classes``,
+    ``crimac_pr_histogram_classes`` (rows ``classes`` of [n_classes, 2, 16384])."""
+    B, nc, H, W = logits.shape
+    if classes is None:
+        call("crimac_pr_histogram", ptr(logits), nc, ptr(labels), labels.element_size(), B, H, W, ptr(hist[0]),
+             ptr(hist[1]))
+    else:
+        call("crimac_pr_histogram_classes", ptr(logits), nc, ptr(labels), labels.element_size(), B, H, W,
+             sum(1 << c for c in classes), ptr(hist))
+
+
+def finish_histograms(hist, all_reduce=True, classes=None):
     """int32 [2, 16384] on the GPU -> (hist_pos, hist_neg) int64 numpy; with several ranks the ONE collective of the flow
-    (the histograms are the metric's sufficient statistic, as in ``SegPipe.get_pr_histograms_dataloader``)."""
+    (the histograms are the metric's sufficient statistic, as in ``SegPipe.get_pr_histograms_dataloader``).
+    ``classes``: int32 [n_classes, 2, 16384] -> (hist_pos [K, 16384], hist_neg [K, 16384]), rows in the order of
+    ``classes``; still one collective."""
+    if hist.dim() == 3 or classes is not None:
+        if classes is None:
+            raise ValueError(f"hist {tuple(hist.shape)} holds one row per class: name the rows to return with classes=")
+        classes = check_classes(classes, hist.shape[0], hist)
     if all_reduce and parallel.rank_world()[1] > 1:
         torch.distributed.all_reduce(hist)
-    h = hist.cpu().numpy().astype(np.int64)
+    return split_histograms(hist.cpu().numpy(), classes)
+
+
+def split_histograms(h, classes=None):
+    """The histograms on the host, [2, 16384] / with ``classes`` [n_classes, 2, 16384] -> (hist_pos, hist_neg) int64
+    ([K, 16384] each, rows in the order of ``classes``); a count in CRIMAC_PR_NAN_BIN raises, as sklearn's
+    precision_recall_curve does on a NaN score."""
+    h = np.asarray(h).astype(np.int64)
+    if classes is not None:
+        h = h[list(classes)]
+        for c, row in zip(classes, h):
+            if row[:, PR_BINS - 1].any():
+                raise ValueError(f"Input contains NaN ({class_name(c)} probabilities of the validation set, class {c})")
+        return np.ascontiguousarray(h[:, 0]), np.ascontiguousarray(h[:, 1])
     if h[:, PR_BINS - 1].any():           # CRIMAC_PR_NAN_BIN: sklearn raises on NaN scores as well
         raise ValueError("Input contains NaN (sandeel probabilities of the validation set)")
     return h[0], h[1]
 
 
 def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, eval_mode="all",
-                    extend_size=20, predict_fn=None, on_batch=None, stats=None, **kwargs):
+                    extend_size=20, predict_fn=None, on_batch=None, stats=None, classes=None, **kwargs):
     """Test-set evaluation of one zarr survey (``validate_model_survey_zarr``, evaluate.py:39-81) on the tiled path:
     returns ``(hist_pos, hist_neg)`` int64 numpy [16384] -- what ``SegPipe.get_pr_histograms_dataloader`` returns for the
     reference's gridded test DataLoader over the same survey; ``SegPipe.validate_model_testing_from_histograms`` turns
@@ -1507,7 +1583,12 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
     back.  With torch.distributed initialised the chunks are dealt to the ranks (``parallel.shard_indices``) and the
     histograms all-reduced once at the end; every rank returns the survey's histograms.
     ``reader``: the reference's zarr reader API (shape, get_data_slice, get_label_slice, get_seabed, get_seabed_mask;
-    get_object_bounding_boxes for ``eval_mode`` 'region' / 'trace')."""
+    get_object_bounding_boxes for ``eval_mode`` 'region' / 'trace').
+    ``classes`` (e.g. ``(1, 2)``, ``check_classes``): the histograms of each named foreground class from the same pass --
+    ``(hist_pos [K, 16384], hist_neg [K, 16384])``, rows in the order of ``classes``; row ``classes.index(1)`` is what
+    the call without ``classes`` returns."""
+    if classes is not None:
+        classes = check_classes(classes, segpipe.model.n_classes)
     n_pings, n_range = (int(v) for v in reader.shape)
     dev = segpipe.device
     model = segpipe.model.to(dev).eval()
@@ -1524,12 +1605,12 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
     chunks = plan_eval_chunks(grid, n_pings, patch_size, preload_n_pings)
     rank, world = parallel.rank_world()
     mine = [chunks[i] for i in parallel.shard_indices(len(chunks), rank, world)]
-    hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=dev)
+    hist = new_histograms(dev, classes, cp.engine)
     if stats is not None:
         stats["patches"] = int(sum(len(c[0]) for c in mine))
         stats["chunks"] = len(mine)
     if not mine:
-        return finish_histograms(hist)
+        return finish_histograms(hist, classes=classes)
     widest = max(hi - lo for _, lo, hi in mine)
 
     def fetch(job, slot):
@@ -1555,16 +1636,17 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
     with _ChunkFeed(dev, "eval", table, 2, mine, fetch) as feed:      # 2 host slots: one chunk is read while one is uploaded
         for (idx, lo, hi), (d, mask) in zip(mine, feed):
             _load_staged(cp, d["data"], lo, d["lab"], lo, hi, d["sb"], mask, wide=True)
-            cp.evaluate(grid[idx], hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch)
+            cp.evaluate(grid[idx], hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch, classes=classes)
             feed.computed()
-        out = finish_histograms(hist)
+        out = finish_histograms(hist, classes=classes)
     if stats is not None:
         stats["seconds"] = time.perf_counter() - t_start
     return out
 
 
 def evaluate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, eval_mode="all", extend_size=20,
-                           predict_fn=None, meta_channels=None, hist=None, on_batch=None, seabed=None, **kwargs):
+                           predict_fn=None, meta_channels=None, hist=None, on_batch=None, seabed=None, classes=None,
+                           **kwargs):
     """Test-set evaluation of one memmap echogram (one Dataset of ``validate_model_survey_memm``, evaluate.py:84-117) on
     the tiled path.  The echogram is one resident chunk, its grid the echogram's (``plan_eval_grid``); metadata models
     (late injection and metadata input channels) take ``meta_channels`` and ``seabed`` (None / "estimate" / an integer
@@ -1572,7 +1654,10 @@ def evaluate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_s
 
     ``hist`` (int32 [2, 16384] on the GPU): accumulate into it and return it -- a survey of several echograms, whose caller
     finishes with ``finish_histograms``; None: returns this echogram's ``(hist_pos, hist_neg)`` int64 numpy (no
-    collective: every rank that calls it evaluates the echogram it passes)."""
+    collective: every rank that calls it evaluates the echogram it passes).
+    ``classes``: per-class histograms as ``evaluate_survey`` returns them; ``hist`` is then int32 [n_classes, 2, 16384]."""
+    if classes is not None:            # (the default path asks nothing new of its arguments)
+        classes = check_classes(classes, segpipe.model.n_classes, hist)
     cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
                                      out_f16=False, wide=True, seabed=seabed)
     dev = segpipe.device
@@ -1582,9 +1667,9 @@ def evaluate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_s
     grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
     own = hist is None
     if own:
-        hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=dev)
-    cp.evaluate(grid, hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch)
-    return finish_histograms(hist, all_reduce=False) if own else hist
+        hist = new_histograms(dev, classes, cp.engine)
+    cp.evaluate(grid, hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch, classes=classes)
+    return finish_histograms(hist, all_reduce=False, classes=classes) if own else hist
 
 
 # ---- a memm survey: many small echograms in one evaluation feed ------------------------------------------------------------
@@ -1622,7 +1707,7 @@ def _takes_keyword(fn, name):
 
 def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, eval_mode="all", extend_size=20,
                             predict_fn=None, meta_channels=None, seabed=None, hist=None, on_batch=None, group_patches=None,
-                            group_elems=None, stats=None, pack_metadata=False, **kwargs):
+                            group_elems=None, stats=None, pack_metadata=False, classes=None, **kwargs):
     """Test-set evaluation of a whole memm survey (``validate_model_survey_memm``, evaluate.py:84-117) on the tiled path:
     ``(hist_pos, hist_neg)`` int64 numpy [16384], the sum of ``evaluate_echogram_memm`` over ``echograms``.
 
@@ -1640,17 +1725,21 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
     ``evaluate_echogram_memm``); None: ``finish_histograms`` -- with several ranks the histograms are all-reduced once,
     and every rank returns the survey's.
     ``on_batch(centres [P, 2] numpy, labels int16 [P, H, W], logits [P, 3, H, W])`` sees every batch; a callback that
-    declares the keyword ``echograms`` also gets the echogram of every patch of the batch (a list of P)."""
+    declares the keyword ``echograms`` also gets the echogram of every patch of the batch (a list of P).
+    ``classes``: per-class histograms as ``evaluate_survey`` returns them, from ``crimac_pr_histogram_classes`` on the
+    packed and on the per-echogram leg alike; ``hist`` is then int32 [n_classes, 2, 16384]."""
+    if classes is not None:            # (the default path asks nothing new of its arguments)
+        classes = check_classes(classes, segpipe.model.n_classes, hist)
     flow = _MemmSurveyFlow("evaluate_echograms_memm",
                            ("group_patches", "group_elems", "seabed", "stats", "predict_fn", "meta_channels", "eval_mode",
-                            "extend_size", "hist", "on_batch", "pack_metadata"),
+                            "extend_size", "hist", "on_batch", "pack_metadata", "classes"),
                            kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
                            group_patches, group_elems, stats, eval_mode=eval_mode, meta_channels=meta_channels,
                            pack_metadata=pack_metadata)
     eng, dev, C, ph, pw = flow.eng, flow.dev, flow.C, flow.ph, flow.pw
     own = hist is None
     if own:
-        hist = torch.zeros(2, PR_BINS, dtype=torch.int32, device=dev)
+        hist = new_histograms(dev, classes, eng)
     tell = on_batch is not None and _takes_keyword(on_batch, "echograms")
 
     def emit(cen, labels_t, logits, egs):
@@ -1663,10 +1752,10 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
         hook = None if on_batch is None else lambda cen, lab, logits: emit(cen, lab, logits, lambda: [eg] * len(cen))
         evaluate_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, eval_mode=eval_mode,
                                extend_size=extend_size, predict_fn=predict_fn, meta_channels=meta, hist=hist, on_batch=hook,
-                               seabed=sb)
+                               seabed=sb, classes=classes)
 
     def done():
-        return finish_histograms(hist) if own else hist
+        return finish_histograms(hist, classes=classes) if own else hist
 
     if flow.alone:
         for eg, sb in flow.each_alone():
@@ -1720,8 +1809,6 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
                 logits = eval_logits(eng, x, Pb, ph, pw, meta=meta, predict_fn=predict_fn, split=True)
                 if on_batch is not None:
                     emit(cen_h[b0:b0 + Pb], labels_t, logits, lambda: egs_h[b0:b0 + Pb])
-                B, nc, H, Wd = logits.shape
-                call("crimac_pr_histogram", ptr(logits), nc, ptr(labels_t), labels_t.element_size(), B, H, Wd, ptr(hist[0]),
-                     ptr(hist[1]))
+                add_pr_histograms(logits, labels_t, hist, classes)
             flow.feed.computed()
     return done()

@@ -130,7 +130,7 @@ extern "C" {
  * points changes, and a binding must refuse a library whose version differs from the header it was written against (an
  * older build that happens to export every symbol would walk a descriptor array with the wrong stride).
  * crimac_layer_desc_size() is sizeof(crimac_layer_desc) as the library was compiled. */
-#define CRIMAC_ABI_VERSION 15
+#define CRIMAC_ABI_VERSION 16
 int crimac_version(void);
 int crimac_layer_desc_size(void);
 const char* crimac_last_error(void);
@@ -612,6 +612,16 @@ int crimac_gather_patches_memm_meta_multi(int prec, const crimac_memm_desc* desc
 #define CRIMAC_PR_NAN_BIN (CRIMAC_PR_BINS - 1)
 int crimac_pr_histogram(const float* logits, int ncls, const void* labels, int label_bytes, int B, int H,
                         int W, unsigned int* hist_pos, unsigned int* hist_neg, void* stream);
+/* crimac_pr_histogram for several foreground classes in ONE pass over the logits: hist [ncls][2][CRIMAC_PR_BINS], row c =
+ * (pos, neg) of class c -- the float16 bit pattern of softmax(logits)[c] over the valid pixels with raw label == c (pos)
+ * and the others (neg).  class_mask: bit c selects class c; non-zero, bits 1 .. ncls-1 only (foreground classes); rows
+ * whose bit is clear, and row 0, are not touched.  Skipped labels as above; -50 (below seabed) counts in neg of EVERY
+ * selected class with probability 0.  One softmax per pixel with the arithmetic of crimac_pr_histogram, so row 1 equals
+ * its two histograms count for count.  Accumulates (caller zeroes); exact counts.  The counts of the subnormal bins
+ * 0 .. 1023 -- where below-seabed pixels and every probability under 2^-14 collect -- are summed per wave and per
+ * workgroup in LDS and reach global memory once per workgroup; the other bins take one global atomic per pixel. */
+int crimac_pr_histogram_classes(const float* logits, int ncls, const void* labels, int label_bytes, int B, int H, int W,
+                                unsigned int class_mask, unsigned int* hist, void* stream);
 
 /* Metadata planes of P crops (reference batch/dataset.py:288-351: the `meta` half of get_crop_memmap's result, which the
  * Dataset appends to the data channels, :109 / :241): built from the echogram's scalar `portion_of_year_scalar` and its
