@@ -1,0 +1,284 @@
+// Echo integration by predicted class (CDNA4 / gfx950): the reduction of a finished prediction chunk.
+//
+// The reference stops at the saved [2][range][pings] float16 probabilities (save_predict.py:212, :252); the next step of
+// a survey -- sum the linear sv of one frequency over the pixels assigned to a class, per cell of (ping bin x range bin)
+// -- is done downstream on the host.  Here both operands are already resident: pred [2][n_range][n_pings] (what
+// crimac_scatter_patches_ex wrote, ping contiguous) and one frequency plane sv [data_pings][n_range] of the chunk's data
+// (range contiguous).
+//
+// A stream of 8-12 bytes per pixel with one transposed operand.  Pass 1: a workgroup owns (cell, split): it walks tiles
+// split, split + S, ... of the cell's 64 x 64 tiles (pings fastest).  Per tile the sv rows go through an LDS tile
+// [64 pings][64 rows + 1] -- read from global along the range, read back along the pings -- while pred is read from global
+// along the pings by the thread that consumes it, so both global reads are coalesced (16 bytes per lane when the extents
+// and the base addresses allow it, 4 bytes otherwise).  sv outside the cell is staged as 0, which the pixel rule (finite
+// and > 0) then drops like any other empty sample.  Each thread keeps fp64 sums and 64-bit counts over its tiles in tile
+// order; lanes are combined by a butterfly, the four waves in wave order by thread 0, and the six results go to the
+// (cell, split) slot of the scratch.  Pass 2: one thread per cell adds its S slots in split order and does a plain
+// read-add-write of the cell's six outputs.  No atomics anywhere: launches that touch the same cell are ordered by the
+// stream, S depends on the shapes alone, so the result is bit-reproducible for a given chunking.
+#include "common.h"
+
+namespace {
+
+constexpr int kTile = 64;                 // tile edge, pings and rows
+constexpr int kPitch = kTile + 1;         // LDS row pitch in floats: the transposed read walks banks, not one bank
+constexpr int kThreads = 256;
+struct Slot { double sum[3]; long long cnt[3]; };
+static_assert(sizeof(Slot) == CRIMAC_INTEGRATE_SLOT_BYTES, "scratch slot size is part of the ABI");
+
+struct Geom {
+  int n_range, range_bin, n_rb, splits, mode;
+  long n_pings, sv_ping_off, ping_bin, ping_origin, n_pb_total, pb0;
+  float thr0, thr1;
+};
+
+// the cell's extent in the launch's coordinates (rows; pings relative to pred column 0), clipped to the launch
+struct Cell { int r0, r1; long p0, p1; };
+__device__ __forceinline__ Cell cell_of(const Geom& g, long cell) {
+  const long pb = g.pb0 + cell / g.n_rb;
+  const int rb = (int)(cell % g.n_rb);
+  Cell c;
+  c.r0 = rb * g.range_bin;
+  const long r1 = (long)c.r0 + g.range_bin, p0 = pb * g.ping_bin - g.ping_origin, p1 = p0 + g.ping_bin;
+  c.r1 = (int)(r1 < g.n_range ? r1 : g.n_range);
+  c.p0 = p0 > 0 ? p0 : 0;
+  c.p1 = p1 < g.n_pings ? p1 : g.n_pings;
+  return c;
+}
+
+template <typename TP> __device__ __forceinline__ float widen(TP v) { return (float)v; }
+
+// four consecutive pings (VEC: one 16- or 8-byte load) or pings l, l + 16, l + 32, l + 48 of one row; 0 outside the array
+template <typename TP, bool VEC>
+__device__ __forceinline__ void load_pred(const TP* __restrict__ row, long p, long n_pings, float (&v)[4]) {
+  if constexpr (VEC) {
+    typedef TP vec4 __attribute__((ext_vector_type(4)));
+    if (p < n_pings) {                                   // (p and n_pings are multiples of 4: all four or none)
+      const vec4 x = __builtin_nontemporal_load(reinterpret_cast<const vec4*>(row + p));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = widen(x[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = 0.f;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = p + 16 * j < n_pings ? widen(__builtin_nontemporal_load(row + p + 16 * j)) : 0.f;
+  }
+}
+
+template <typename TP, bool VEC_SV, bool VEC_PRED>
+__global__ __launch_bounds__(kThreads) void integrate_cells_kernel(const TP* __restrict__ pred, const float* __restrict__ sv,
+                                                                   Geom g, Slot* __restrict__ scratch) {
+  __shared__ float tile[kTile * kPitch];
+  __shared__ Slot wave_part[kThreads / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const long cell = blockIdx.x / g.splits;
+  const int split = (int)(blockIdx.x - cell * g.splits);
+  const Cell c = cell_of(g, cell);
+  // tile origins are multiples of 4 in both directions, so that a 16-byte access never straddles an edge it may not cross
+  const int ra = c.r0 & ~3;
+  const long pa = c.p0 & ~3L;
+  const int nrt = c.r1 > c.r0 ? (c.r1 - ra + kTile - 1) / kTile : 0;
+  const long npt = c.p1 > c.p0 ? (c.p1 - pa + kTile - 1) / kTile : 0;
+  const long tiles = nrt * npt;
+  const TP* pred0 = pred;
+  const TP* pred1 = pred + (long)g.n_range * g.n_pings;
+  const int row_in_group = t >> 4, l16 = t & 15;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  long long n0 = 0, n1 = 0, n2 = 0;
+
+  for (long tl = split; tl < tiles; tl += g.splits) {
+    const int tr = ra + (int)(tl / npt) * kTile;             // first row of the tile
+    const long tp = pa + (tl % npt) * kTile;                 // its first ping
+    // ---- sv: global (along the range) -> registers; 0 outside the cell and outside the array
+    float svr[16];
+    if constexpr (VEC_SV) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = t + kThreads * k, r = tr + 4 * (i & 15);
+        const long p = tp + (i >> 4);
+        f32x4 x = {0.f, 0.f, 0.f, 0.f};
+        if (r < c.r1 && p >= c.p0 && p < c.p1)                // (r, n_range multiples of 4: r < r1 <= n_range -> r + 3 < n_range)
+          x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(sv + (g.sv_ping_off + p) * g.n_range + r));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) svr[4 * k + j] = (r + j >= c.r0 && r + j < c.r1) ? x[j] : 0.f;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int i = t + kThreads * k, r = tr + (i & 63);
+        const long p = tp + (i >> 6);
+        svr[k] = (r >= c.r0 && r < c.r1 && p >= c.p0 && p < c.p1)
+                     ? __builtin_nontemporal_load(sv + (g.sv_ping_off + p) * g.n_range + r) : 0.f;
+      }
+    }
+    // ---- pred: global (along the pings) -> registers, for the 4 rows x 4 pings this thread consumes
+    float pr0[4][4], pr1[4][4];
+    const long pp = tp + (VEC_PRED ? 4 * l16 : l16);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int r = tr + row_in_group + 16 * k;
+      if (r < c.r1) {
+        load_pred<TP, VEC_PRED>(pred0 + (long)r * g.n_pings, pp, g.n_pings, pr0[k]);
+        load_pred<TP, VEC_PRED>(pred1 + (long)r * g.n_pings, pp, g.n_pings, pr1[k]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pr0[k][j] = pr1[k][j] = 0.f;
+      }
+    }
+    // ---- sv registers -> LDS tile [ping][row]
+    __syncthreads();                                          // (the previous tile has been consumed)
+    if constexpr (VEC_SV) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = t + kThreads * k;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tile[(i >> 4) * kPitch + 4 * (i & 15) + j] = svr[4 * k + j];
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int i = t + kThreads * k;
+        tile[(i >> 6) * kPitch + (i & 63)] = svr[k];
+      }
+    }
+    __syncthreads();
+    // ---- the pixel rule
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int rl = row_in_group + 16 * k;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int pl = VEC_PRED ? 4 * l16 + j : l16 + 16 * j;
+        const float s = tile[pl * kPitch + rl];
+        const bool ok = s > 0.f && s < __builtin_inff();      // finite and > 0 (NaN fails both)
+        const float a = pr0[k][j], b = pr1[k][j];
+        const double sd = ok ? (double)s : 0.0;
+        if (g.mode == 0) {
+          const bool in0 = ok && a >= g.thr0, in1 = ok && b >= g.thr1;
+          s0 += in0 ? sd : 0.0;
+          s1 += in1 ? sd : 0.0;
+          n0 += in0;
+          n1 += in1;
+        } else {
+          const bool in0 = ok && a > 0.f, in1 = ok && b > 0.f;        // (a NaN or negative weight counts as 0)
+          s0 += in0 ? sd * (double)a : 0.0;
+          s1 += in1 ? sd * (double)b : 0.0;
+          n0 += in0;
+          n1 += in1;
+        }
+        s2 += sd;
+        n2 += ok;
+      }
+    }
+  }
+  // ---- lane -> wave -> workgroup, each in a fixed order
+  s0 = wave_sum_d(s0);
+  s1 = wave_sum_d(s1);
+  s2 = wave_sum_d(s2);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    n0 += __shfl_xor(n0, o, 64);
+    n1 += __shfl_xor(n1, o, 64);
+    n2 += __shfl_xor(n2, o, 64);
+  }
+  if (lane == 0) wave_part[wave] = Slot{{s0, s1, s2}, {n0, n1, n2}};
+  __syncthreads();
+  if (t == 0) {
+    Slot out = wave_part[0];
+    for (int w = 1; w < kThreads / 64; ++w)
+      for (int k = 0; k < 3; ++k) {
+        out.sum[k] += wave_part[w].sum[k];
+        out.cnt[k] += wave_part[w].cnt[k];
+      }
+    scratch[blockIdx.x] = out;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void integrate_finish_kernel(const Slot* __restrict__ scratch, Geom g, long cells,
+                                                                    double* __restrict__ acc, long long* __restrict__ cnt) {
+  const long cell = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (cell >= cells) return;
+  Slot out = scratch[cell * g.splits];
+  for (int s = 1; s < g.splits; ++s) {
+    const Slot& x = scratch[cell * g.splits + s];
+    for (int k = 0; k < 3; ++k) {
+      out.sum[k] += x.sum[k];
+      out.cnt[k] += x.cnt[k];
+    }
+  }
+  const long pb = g.pb0 + cell / g.n_rb, rb = cell % g.n_rb;
+  for (int k = 0; k < 3; ++k) {
+    const long at = ((long)k * g.n_pb_total + pb) * g.n_rb + rb;
+    acc[at] += out.sum[k];
+    cnt[at] += out.cnt[k];
+  }
+}
+
+template <typename TP>
+void launch_cells(bool vec_sv, bool vec_pred, unsigned blocks, hipStream_t st, const void* pred, const float* sv,
+                  const Geom& g, Slot* scratch) {
+  const TP* p = static_cast<const TP*>(pred);
+  if (vec_sv && vec_pred) hipLaunchKernelGGL((integrate_cells_kernel<TP, true, true>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
+  else if (vec_sv) hipLaunchKernelGGL((integrate_cells_kernel<TP, true, false>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
+  else if (vec_pred) hipLaunchKernelGGL((integrate_cells_kernel<TP, false, true>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
+  else hipLaunchKernelGGL((integrate_cells_kernel<TP, false, false>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
+}
+
+}  // namespace
+
+extern "C" int crimac_integrate_classes(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv,
+                                        long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode,
+                                        long ping_bin, int range_bin, long ping_origin, long n_pb_total, double* acc,
+                                        long long* cnt, void* scratch, long scratch_bytes, void* stream) {
+  CRIMAC_REQUIRE(pred && sv && acc && cnt && scratch, "integrate_classes: null pointer");
+  CRIMAC_REQUIRE(pred_f16 == 0 || pred_f16 == 1, "integrate_classes: pred_f16 is 0 or 1");
+  CRIMAC_REQUIRE(n_range > 0 && n_pings > 0, "integrate_classes: empty prediction array (%d x %ld)", n_range, n_pings);
+  CRIMAC_REQUIRE(mode == 0 || mode == 1, "integrate_classes: mode %d (0 threshold, 1 probability)", mode);
+  CRIMAC_REQUIRE(thr_sandeel > 0.f && thr_other > 0.f, "integrate_classes: thr = (%g, %g) must be > 0 (pixels the scatter "
+                 "left at 0 belong to no class)", (double)thr_sandeel, (double)thr_other);
+  CRIMAC_REQUIRE(ping_bin > 0 && range_bin > 0, "integrate_classes: ping_bin=%ld, range_bin=%d must be positive", ping_bin,
+                 range_bin);
+  CRIMAC_REQUIRE(ping_bin <= 2147483647L && n_pb_total <= 2147483647L, "integrate_classes: ping_bin=%ld, n_pb_total=%ld "
+                 "beyond 2^31 - 1", ping_bin, n_pb_total);
+  CRIMAC_REQUIRE(sv_ping_off >= 0 && sv_ping_off + n_pings <= data_pings, "integrate_classes: sv columns [%ld, %ld) outside "
+                 "the sv extent of %ld pings", sv_ping_off, sv_ping_off + n_pings, data_pings);
+  CRIMAC_REQUIRE(ping_origin >= 0 && n_pb_total > 0 && ping_origin + n_pings <= n_pb_total * ping_bin,
+                 "integrate_classes: pings [%ld, %ld) outside the accumulator's %ld bins of %ld pings", ping_origin,
+                 ping_origin + n_pings, n_pb_total, ping_bin);
+  Geom g;
+  g.n_range = n_range;
+  g.range_bin = range_bin;
+  g.n_rb = (n_range + range_bin - 1) / range_bin;
+  g.mode = mode;
+  g.n_pings = n_pings;
+  g.sv_ping_off = sv_ping_off;
+  g.ping_bin = ping_bin;
+  g.ping_origin = ping_origin;
+  g.n_pb_total = n_pb_total;
+  g.pb0 = ping_origin / ping_bin;
+  g.thr0 = thr_sandeel;
+  g.thr1 = thr_other;
+  const long cells = ((ping_origin + n_pings - 1) / ping_bin - g.pb0 + 1) * g.n_rb;
+  // tiles of a full cell (its origin may sit up to 3 short of a multiple of 4 in either direction)
+  const long span_r = (range_bin < n_range ? range_bin : n_range) + 3, span_p = (ping_bin < n_pings ? ping_bin : n_pings) + 3;
+  const long tiles = ((span_r + kTile - 1) / kTile) * ((span_p + kTile - 1) / kTile);
+  const long want = (CRIMAC_INTEGRATE_SPLIT_WGS + cells - 1) / cells;
+  g.splits = (int)(want < tiles ? want : tiles);
+  CRIMAC_REQUIRE(cells * g.splits <= 2147483647L, "integrate_classes: %ld cells in one launch", cells);
+  CRIMAC_REQUIRE(scratch_bytes >= cells * g.splits * (long)sizeof(Slot) && (uintptr_t)scratch % 8 == 0,
+                 "integrate_classes: scratch of %ld bytes, this launch needs %ld (8-byte aligned; (cells + "
+                 "CRIMAC_INTEGRATE_SPLIT_WGS) * CRIMAC_INTEGRATE_SLOT_BYTES always suffices)", scratch_bytes,
+                 cells * g.splits * (long)sizeof(Slot));
+  const bool vec_sv = n_range % 4 == 0 && (uintptr_t)sv % 16 == 0;
+  const bool vec_pred = n_pings % 4 == 0 && (uintptr_t)pred % (pred_f16 ? 8 : 16) == 0;
+  const hipStream_t st = (hipStream_t)stream;
+  if (pred_f16) launch_cells<half_t>(vec_sv, vec_pred, (unsigned)(cells * g.splits), st, pred, sv, g, (Slot*)scratch);
+  else launch_cells<float>(vec_sv, vec_pred, (unsigned)(cells * g.splits), st, pred, sv, g, (Slot*)scratch);
+  CRIMAC_LAUNCH_CHECK();
+  hipLaunchKernelGGL(integrate_finish_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                     (const Slot*)scratch, g, cells, acc, cnt);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}

@@ -135,6 +135,8 @@ del _header
 
 ABI_VERSION = DEFINES["CRIMAC_ABI_VERSION"]      # a built library of another version is stale (load_library)
 PR_BINS = DEFINES["CRIMAC_PR_BINS"]
+# scratch of crimac_integrate_classes: (cells of the launch + INTEGRATE_SPLIT_WGS) slots of INTEGRATE_SLOT_BYTES
+INTEGRATE_SPLIT_WGS, INTEGRATE_SLOT_BYTES = DEFINES["CRIMAC_INTEGRATE_SPLIT_WGS"], DEFINES["CRIMAC_INTEGRATE_SLOT_BYTES"]
 # name -> argtypes of every entry point that returns a status and takes the stream as its last argument (`call`)
 SIGNATURES = {name: args for name, (res, args, stream) in PROTOTYPES.items() if stream and res is C.c_int}
 

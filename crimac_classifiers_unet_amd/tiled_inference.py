@@ -24,7 +24,9 @@ exact).  Writing zarr / npy is the caller's business: ``pr
 that a caller appends with the reference's ``create_xarray_ds_predictions`` / ``append_to_zarr``;
 ``predict_echogram_memm`` returns the array ``save_reader_predictions_memm`` would ``np.save``;
 ``predict_echograms_memm`` does so for a whole memm survey, its forward batches packed across the echograms, and
-``evaluate_echograms_memm`` evaluates one (PR histograms) in the same way.
+``evaluate_echograms_memm`` evaluates one (PR histograms) in the same way.  ``integrate_survey`` /
+``integrate_echogram_memm`` reduce the predictions on the GPU instead of returning them: echo integration by predicted
+class (``crimac_integrate_classes``), the sv of one frequency summed per class and (ping bin x range bin) cell.
 """
 from __future__ import annotations
 
@@ -221,6 +223,34 @@ class ChunkPredictor:
         if world > 1:
             torch.distributed.all_reduce(self.out)      # interiors are disjoint: sum == union (exact in fp16 too)
         return self.out
+
+    def integrate(self, acc, cnt, spec):
+        """Echo integration of the chunk ``predict`` has just filled (``crimac_integrate_classes``): the linear sv of
+        ``self.data[spec.channel]`` summed per class and cell into ``acc`` float64 / ``cnt`` int64
+        ``[3, n_pb_total, n_rb]`` on the GPU (``new_integration``), which cover global pings from 0.  ``spec``: a bound
+        ``IntegrationSpec``.  Launches on the current stream, after the scatter; nothing comes back."""
+        if self.wide or self.out is None:
+            raise ValueError("ChunkPredictor.integrate: the chunk was loaded for evaluate() (wide=True) and has no predictions")
+        if spec.channel is None:
+            raise ValueError("ChunkPredictor.integrate: bind the spec to the model's frequencies first (IntegrationSpec.bind)")
+        if not 0 <= spec.channel < self.data.shape[0]:
+            raise ValueError(f"ChunkPredictor.integrate: channel {spec.channel} of {self.data.shape[0]} data planes")
+        n_pb, n_rb = spec.bins(self.end_ping, self.n_range)
+        want = (3, acc.shape[1], n_rb)
+        if acc.dtype != torch.float64 or cnt.dtype != torch.int64 or tuple(acc.shape) != want or tuple(cnt.shape) != want \
+                or acc.shape[1] < n_pb or not acc.is_contiguous() or not cnt.is_contiguous():
+            raise ValueError(f"ChunkPredictor.integrate: acc float64 / cnt int64, contiguous [3, >= {n_pb}, {n_rb}]; got "
+                             f"{acc.dtype} {tuple(acc.shape)}, {cnt.dtype} {tuple(cnt.shape)}")
+        n = self.end_ping - self.start_ping
+        cells = ((self.end_ping - 1) // spec.ping_bin - self.start_ping // spec.ping_bin + 1) * n_rb
+        scratch = self.engine._buf("integrate.scratch", ((cells + hip.INTEGRATE_SPLIT_WGS) * hip.INTEGRATE_SLOT_BYTES // 8,),
+                                   torch.float64)
+        sv = self.data[spec.channel]
+        with torch.cuda.device(self.out.device):
+            call("crimac_integrate_classes", ptr(self.out), 1 if self.out_f16 else 0, self.n_range, n, ptr(sv),
+                 int(sv.shape[0]), self.start_ping - self.data_ping0, spec.thresholds[0], spec.thresholds[1],
+                 IntegrationSpec.MODES.index(spec.mode), spec.ping_bin, spec.range_bin, self.start_ping,
+                 int(acc.shape[1]), ptr(acc), ptr(cnt), ptr(scratch), scratch.numel() * 8)
 
     def _early(self):       # metadata planes as extra input channels
         return not self.engine.lmi and self.engine.in_channels > self.data.shape[0]
@@ -647,6 +677,114 @@ def _load_staged(cp, data, lo, labels, s, e, seabed, mask, wide=False):
         cp.load_chunk(data, lo, labels, mask, s, e, wide=wide)
 
 
+class _SurveyChunks:
+    """What ``predict_survey`` and ``integrate_survey`` share: the chunk plan of a zarr survey, the reader-thread ``fetch``
+    into pinned staging, the staging table of their ``_ChunkFeed``, and the per-chunk loop body -- load the uploaded chunk,
+    predict it, mark its device slot computed.  ``name``: the caller, for messages; ``f16``: the type of ``cp.out``."""
+
+    def __init__(self, name, reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, start_ping,
+                 labels_available, f16, stats, predict_fn, share_patches):
+        self.name, self.reader, self.segpipe, self.stats, self.predict_fn = name, reader, segpipe, stats, predict_fn
+        self.patch_size, self.patch_overlap, self.labels_available = patch_size, patch_overlap, labels_available
+        self.share_patches = share_patches
+        self.n_pings, self.n_range = reader.shape
+        self.dev = segpipe.device
+        model = segpipe.model.to(self.dev).eval()
+        self.cp = ChunkPredictor(model, self.n_range, patch_size, patch_overlap, batch_size, out_f16=f16)
+        self.all_chunks = self.chunks = plan_chunks(start_ping, self.n_pings, preload_n_pings)
+        self.n_freq = len(segpipe.frequencies)
+
+    def note(self, key, t0):
+        if self.stats is not None:
+            self.stats.setdefault(key, []).append(time.perf_counter() - t0)
+
+    def own(self, rank, world):
+        """Chunk sharding: this rank keeps chunks rank, rank + world, ..."""
+        self.chunks = self.chunks[rank::world]
+
+    def check_model(self):
+        cp, n_freq = self.cp, self.n_freq
+        if not cp.engine.lmi and cp.engine.in_channels > n_freq:
+            raise NotImplementedError(f"{self.name}: the model takes {cp.engine.in_channels} input channels for "
+                                      f"{n_freq} frequencies (metadata planes as input channels); the zarr preload path has "
+                                      "no metadata (batch/dataset.py:210-216) -- use predict_echogram_memm(meta_channels=...)")
+
+    def feed(self, tag, extra=None):
+        """The ``_ChunkFeed`` over this rank's chunks (3 host slots: two chunks are being read while one is uploaded)."""
+        patch_size, patch_overlap, n_range, n_freq = self.patch_size, self.patch_overlap, self.n_range, self.n_freq
+        self.widest = widest = max(e - s for s, e in self.chunks)
+        halo = patch_size[1]
+        n_data = n_freq * (widest + 2 * halo) * n_range
+        max_patches = 4 * (widest // (patch_size[0] - 2 * patch_overlap) + 2) * (n_range // (patch_size[1] - 2 * patch_overlap) + 2)
+        self.n_misc = (widest + 2 * halo) + 4 * max_patches       # int32: seabed | global centres | slice-relative centres
+        # staging (pinned host + device) is kept between surveys of the same geometry: page-locking 3 x 75 MB + the result
+        # buffers costs 10-20 ms per call, a tenth of a 65536-ping survey
+        table = {"data": (n_data, torch.float32), "lab": (widest * n_range, torch.int16), "misc": (self.n_misc, torch.int32)}
+        return _ChunkFeed(self.dev, tag, table, 3, self.chunks, self.fetch, extra=extra, note=self.note)
+
+    def fetch(self, chunk, slot):
+        reader, segpipe, patch_size, patch_overlap = self.reader, self.segpipe, self.patch_size, self.patch_overlap
+        n_pings, n_range, n_freq, n_misc = self.n_pings, self.n_range, self.n_freq, self.n_misc
+        t0 = time.perf_counter()
+        s, e = chunk
+        # ping extent of the data a patch of the chunk can touch (dataset.py:175-177): the patch columns depend on
+        # (s, e) only, so the seabed of [lo, hi) -- which contains [s, e) -- is read ONCE (the zarr reader derives it from
+        # the full 2-D mask every time, data_reader.py:864-865)
+        xs = np.arange(s - (patch_overlap + 1), e - (patch_overlap + 1), patch_size[0] - 2 * patch_overlap) + patch_size[0] // 2
+        lo = max(0, int(xs[0]) - patch_size[1] // 2)
+        hi = min(n_pings, int(xs[-1]) + patch_size[1] // 2)
+        sb = np.asarray(reader.get_seabed(lo, hi - lo, return_numpy=True)).astype(np.int32)
+        seabed = sb[max(s - lo, 0):e - lo] if lo <= s else np.asarray(reader.get_seabed(s, e - s, return_numpy=True)).astype(np.int32)
+        grid = plan_grid(n_range, int(seabed.max()), s, e, patch_size, patch_overlap)
+        assert lo == max(0, int(grid[0, 1]) - patch_size[1] // 2) and hi == min(n_pings, int(grid[-1, 1]) + patch_size[1] // 2)
+        host = slot()
+        data = reader.get_data_slice(idx_ping=lo, n_pings=hi - lo, frequencies=segpipe.frequencies,
+                                     return_numpy=True)
+        d_t = host["data"][:n_freq * (hi - lo) * n_range].view(n_freq, hi - lo, n_range)     # contiguous
+        np.copyto(d_t.numpy(), data, casting="same_kind")
+        l_t = None
+        if self.labels_available:
+            lab = reader.get_label_slice(idx_ping=s, n_pings=e - s, return_numpy=True)
+            l_t = host["lab"][:(e - s) * n_range].view(e - s, n_range)
+            np.copyto(l_t.numpy(), lab, casting="unsafe")
+        # the seabed of every ping a patch of the chunk can touch (the scatter kernel evaluates the mask from it)
+        sb, mask = seabed_vector_or_mask(reader, s, e, n_range, sb, lo)
+        P = len(grid)
+        assert (hi - lo) + 4 * P <= n_misc, "misc staging too small"
+        m = host["misc"].numpy()
+        m[:hi - lo] = sb
+        cen = np.asarray(grid, dtype=np.int32)
+        m[hi - lo:hi - lo + 2 * P] = cen.reshape(-1)
+        loc = cen.copy()
+        loc[:, 1] -= lo
+        m[hi - lo + 2 * P:hi - lo + 4 * P] = loc.reshape(-1)
+        self.note("fetch_s", t0)
+        return {"data": d_t, "lab": l_t, "misc": host["misc"][:hi - lo + 4 * P]}, (s, e, lo, hi, grid, mask)
+
+    def predicted(self, feed, then=None):
+        """Per chunk of ``feed``: load, predict, ``then(cp)`` -- whatever else reads the chunk's device slot --, mark the
+        slot computed; yields ``(i, s, e, cp.out)`` with all of that enqueued."""
+        cp, stats, note = self.cp, self.stats, self.note
+        for i, (d, (s, e, lo, hi, grid, mask)) in enumerate(feed):
+            P = len(grid)
+            if stats is not None:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+            _load_staged(cp, d["data"], lo, d["lab"], s, e, d["misc"][:hi - lo], mask)
+            note("enq_load_s", feed.t_uploaded)
+            t1 = time.perf_counter()
+            out = cp.predict(grid, predict_fn=self.predict_fn, centres_dev=d["misc"][hi - lo:].view(2, P, 2),
+                             share_patches=self.share_patches)
+            note("enq_predict_s", t1)
+            if then is not None:
+                then(cp)
+            if stats is not None:
+                ev1.record()
+                stats.setdefault("gpu_events", []).append((ev0, ev1))
+            feed.computed()
+            yield i, s, e, out
+
+
 def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings,
                    start_ping=0, labels_available=True, out_dtype=np.float32, stats=None, predict_fn=None,
                    shard="chunk", ordered_to_rank0=False, **kwargs):
@@ -680,12 +818,10 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
     (numpy / zarr I/O, no GPU calls) while the GPU uploads (copy stream), gathers, predicts and scatters chunk i, and
     the result of chunk i-1 comes back through a pinned buffer (asynchronous D2H) before it is handed to the caller.
     """
-    n_pings, n_range = reader.shape
-    dev = segpipe.device
-    model = segpipe.model.to(dev).eval()
     f16 = np.dtype(out_dtype) == np.float16
-    cp = ChunkPredictor(model, n_range, patch_size, patch_overlap, batch_size, out_f16=f16)
-    chunks = plan_chunks(start_ping, n_pings, preload_n_pings)
+    flow = _SurveyChunks("predict_survey", reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings,
+                         start_ping, labels_available, f16, stats, predict_fn, share_patches=shard == "patch")
+    n_range, note = flow.n_range, flow.note
     if shard not in ("chunk", "patch"):
         raise ValueError(f"predict_survey: shard must be 'chunk' or 'patch', got {shard!r}")
     share_patches = shard == "patch"
@@ -695,76 +831,20 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
         raise ValueError("predict_survey: ordered_to_rank0 belongs to shard='chunk' (with shard='patch' every rank already "
                          "yields every chunk)")
     ordered = multi and not share_patches and bool(ordered_to_rank0)
-    all_chunks = chunks
     if multi and not share_patches:
-        chunks = chunks[rank::world]
+        flow.own(rank, world)
     sender = ordered and rank != 0
-    hand = _OrderedHandoff(rank, world, all_chunks, n_range, np.dtype(out_dtype)) if ordered else None
-    if not chunks:
+    hand = _OrderedHandoff(rank, world, flow.all_chunks, n_range, np.dtype(out_dtype)) if ordered else None
+    if not flow.chunks:
         return
-    n_freq = len(segpipe.frequencies)
-    if not cp.engine.lmi and cp.engine.in_channels > n_freq:
-        raise NotImplementedError(f"predict_survey: the model takes {cp.engine.in_channels} input channels for "
-                                  f"{n_freq} frequencies (metadata planes as input channels); the zarr preload path has "
-                                  "no metadata (batch/dataset.py:210-216) -- use predict_echogram_memm(meta_channels=...)")
-    widest = max(e - s for s, e in chunks)
-    halo = patch_size[1]
-    n_data = n_freq * (widest + 2 * halo) * n_range
-    max_patches = 4 * (widest // (patch_size[0] - 2 * patch_overlap) + 2) * (n_range // (patch_size[1] - 2 * patch_overlap) + 2)
-    n_misc = (widest + 2 * halo) + 4 * max_patches            # int32: seabed | global centres | slice-relative centres
+    flow.check_model()
     tick = time.perf_counter
-
-    def note(key, t0):
-        if stats is not None:
-            stats.setdefault(key, []).append(tick() - t0)
-
-    def fetch(chunk, slot):
-        t0 = tick()
-        s, e = chunk
-        # ping extent of the data a patch of the chunk can touch (dataset.py:175-177): the patch columns depend on
-        # (s, e) only, so the seabed of [lo, hi) -- which contains [s, e) -- is read ONCE (the zarr reader derives it from
-        # the full 2-D mask every time, data_reader.py:864-865)
-        xs = np.arange(s - (patch_overlap + 1), e - (patch_overlap + 1), patch_size[0] - 2 * patch_overlap) + patch_size[0] // 2
-        lo = max(0, int(xs[0]) - patch_size[1] // 2)
-        hi = min(n_pings, int(xs[-1]) + patch_size[1] // 2)
-        sb = np.asarray(reader.get_seabed(lo, hi - lo, return_numpy=True)).astype(np.int32)
-        seabed = sb[max(s - lo, 0):e - lo] if lo <= s else np.asarray(reader.get_seabed(s, e - s, return_numpy=True)).astype(np.int32)
-        grid = plan_grid(n_range, int(seabed.max()), s, e, patch_size, patch_overlap)
-        assert lo == max(0, int(grid[0, 1]) - patch_size[1] // 2) and hi == min(n_pings, int(grid[-1, 1]) + patch_size[1] // 2)
-        host = slot()
-        data = reader.get_data_slice(idx_ping=lo, n_pings=hi - lo, frequencies=segpipe.frequencies,
-                                     return_numpy=True)
-        d_t = host["data"][:n_freq * (hi - lo) * n_range].view(n_freq, hi - lo, n_range)     # contiguous
-        np.copyto(d_t.numpy(), data, casting="same_kind")
-        l_t = None
-        if labels_available:
-            lab = reader.get_label_slice(idx_ping=s, n_pings=e - s, return_numpy=True)
-            l_t = host["lab"][:(e - s) * n_range].view(e - s, n_range)
-            np.copyto(l_t.numpy(), lab, casting="unsafe")
-        # the seabed of every ping a patch of the chunk can touch (the scatter kernel evaluates the mask from it)
-        sb, mask = seabed_vector_or_mask(reader, s, e, n_range, sb, lo)
-        P = len(grid)
-        assert (hi - lo) + 4 * P <= n_misc, "misc staging too small"
-        m = host["misc"].numpy()
-        m[:hi - lo] = sb
-        cen = np.asarray(grid, dtype=np.int32)
-        m[hi - lo:hi - lo + 2 * P] = cen.reshape(-1)
-        loc = cen.copy()
-        loc[:, 1] -= lo
-        m[hi - lo + 2 * P:hi - lo + 4 * P] = loc.reshape(-1)
-        note("fetch_s", t0)
-        return {"data": d_t, "lab": l_t, "misc": host["misc"][:hi - lo + 4 * P]}, (s, e, lo, hi, grid, mask)
-
-    # staging (pinned host + device) is kept between surveys of the same geometry: page-locking 3 x 75 MB + the result
-    # buffers costs 10-20 ms per call, a tenth of a 65536-ping survey.  3 host slots: two chunks are being read while
-    # one is uploaded
-    table = {"data": (n_data, torch.float32), "lab": (widest * n_range, torch.int16), "misc": (n_misc, torch.int32)}
     out_t = torch.float16 if f16 else torch.float32
 
     def result_ring():                   # flat: every chunk's [2, range, e - s] view of it is contiguous
-        return {"pinned": [torch.empty(2 * n_range * widest, dtype=out_t).pin_memory() for _ in range(2)]}
+        return {"pinned": [torch.empty(2 * n_range * flow.widest, dtype=out_t).pin_memory() for _ in range(2)]}
 
-    with _ChunkFeed(dev, ("predict", f16), table, 3, chunks, fetch, extra=result_ring, note=note) as feed:
+    with flow.feed(("predict", f16), extra=result_ring) as feed:
         pinned = feed.bufs["pinned"]
         events = [torch.cuda.Event() for _ in range(2)]
 
@@ -779,21 +859,7 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
 
         def _loop():
             pending = None                      # (s, e, ring) of the chunk whose D2H copy is in flight
-            for i, (d, (s, e, lo, hi, grid, mask)) in enumerate(feed):
-                P = len(grid)
-                if stats is not None:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record()
-                _load_staged(cp, d["data"], lo, d["lab"], s, e, d["misc"][:hi - lo], mask)
-                note("enq_load_s", feed.t_uploaded)
-                t1 = tick()
-                out = cp.predict(grid, predict_fn=predict_fn, centres_dev=d["misc"][hi - lo:].view(2, P, 2),
-                                 share_patches=share_patches)
-                note("enq_predict_s", t1)
-                if stats is not None:
-                    ev1.record()
-                    stats.setdefault("gpu_events", []).append((ev0, ev1))
-                feed.computed()
+            for i, s, e, out in flow.predicted(feed):
                 if sender:                            # ordered hand-off: the chunk goes to rank 0, nothing comes back here
                     hand.send(out)
                     note("enqueue_s", feed.t_taken)
@@ -813,6 +879,109 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
             yield from hand.merge(_loop())
         else:
             yield from _loop()
+
+
+# ---- echo integration by predicted class: the reduction of the prediction flows (csrc/integrate.hip) ---------------------
+INTEGRATION_CLASSES = ("sandeel", "other", "all")
+
+
+class IntegrationSpec:
+    """What to integrate and on which grid.  ``ping_bin`` / ``range_bin``: the cell size in pings / range rows (cell
+    (pb, rb) = global pings [pb * ping_bin, (pb + 1) * ping_bin) x rows [rb * range_bin, (rb + 1) * range_bin), the last
+    bin of either axis may be partial).  ``frequency``: the frequency whose linear sv is summed, a value of
+    ``segpipe.frequencies``; None takes 38 (kHz, the memm readers and the yaml) or, failing that, 38000 (Hz, the zarr
+    readers).  ``mode`` "threshold": a pixel belongs to class k when its stored probability >= ``thresholds[k]``
+    (sandeel, other; it may belong to both); "probability": its sv counts with weight = the stored probability.
+    ``thresholds`` must be > 0 in both modes.  ``bind(frequencies)`` returns the spec with ``channel`` looked up."""
+    MODES = ("threshold", "probability")
+
+    def __init__(self, ping_bin, range_bin, frequency=None, thresholds=(0.5, 0.5), mode="threshold", channel=None):
+        for name, v in (("ping_bin", ping_bin), ("range_bin", range_bin)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"IntegrationSpec: {name}={v!r} must be a positive integer")
+        if mode not in self.MODES:
+            raise ValueError(f"IntegrationSpec: mode={mode!r}: 'threshold' or 'probability'")
+        try:
+            thresholds = tuple(float(t) for t in thresholds)
+        except TypeError:
+            raise ValueError(f"IntegrationSpec: thresholds={thresholds!r}: two numbers (sandeel, other)") from None
+        if len(thresholds) != 2 or not all(0.0 < t < float("inf") for t in thresholds):
+            raise ValueError(f"IntegrationSpec: thresholds={thresholds!r}: two finite numbers > 0 (pixels the scatter left "
+                             "at 0 belong to no class)")
+        self.ping_bin, self.range_bin, self.frequency = int(ping_bin), int(range_bin), frequency
+        self.thresholds, self.mode, self.channel = thresholds, mode, channel
+
+    def bind(self, frequencies):
+        """The spec with ``channel`` = the index of its frequency in ``frequencies``; ValueError if it is not there."""
+        freqs = [float(f) for f in frequencies]
+        wanted = (38, 38000) if self.frequency is None else (self.frequency,)
+        for f in wanted:
+            if float(f) in freqs:
+                return IntegrationSpec(self.ping_bin, self.range_bin, f, self.thresholds, self.mode, freqs.index(float(f)))
+        raise ValueError(f"IntegrationSpec: frequency {' / '.join(str(f) for f in wanted)} is not among the model's "
+                         f"frequencies {list(frequencies)}")
+
+    def bins(self, n_pings, n_range):
+        """(ping bins, range bins) that cover global pings [0, n_pings) and rows [0, n_range)."""
+        return -(-int(n_pings) // self.ping_bin), -(-int(n_range) // self.range_bin)
+
+
+def new_integration(dev, spec, n_pings, n_range):
+    """Zeroed accumulators of ``ChunkPredictor.integrate`` on ``dev``: (acc float64, cnt int64), both [3, n_pb, n_rb]."""
+    shape = (3, *spec.bins(n_pings, n_range))
+    return torch.zeros(shape, dtype=torch.float64, device=dev), torch.zeros(shape, dtype=torch.int64, device=dev)
+
+
+def finish_integration(acc, cnt, spec, n_pings, n_range, all_reduce=True):
+    """The accumulators -> the result of the integration flows (numpy, ONE download): ``sv_sum`` float64 and ``pixels``
+    int64 ``[3, n_pb, n_rb]`` (planes ``classes`` = sandeel, other, all counted pixels), ``ping_edges`` int64 [n_pb + 1]
+    and ``range_edges`` int64 [n_rb + 1] (the last edge is the survey's end, so a partial last bin shows).  With several
+    ranks the accumulators are all-reduced first (sum), the one collective of the flow."""
+    if all_reduce and parallel.rank_world()[1] > 1:
+        torch.distributed.all_reduce(acc)
+        torch.distributed.all_reduce(cnt)
+    n_pb, n_rb = spec.bins(n_pings, n_range)
+    return {"sv_sum": acc.cpu().numpy(), "pixels": cnt.cpu().numpy(),
+            "ping_edges": np.minimum(np.arange(n_pb + 1, dtype=np.int64) * spec.ping_bin, int(n_pings)),
+            "range_edges": np.minimum(np.arange(n_rb + 1, dtype=np.int64) * spec.range_bin, int(n_range)),
+            "classes": INTEGRATION_CLASSES}
+
+
+def integrate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, spec, start_ping=0,
+                     labels_available=True, predict_fn=None, stats=None):
+    """Echo integration by predicted class over one zarr survey: ``predict_survey``'s chunk feed, staging and upload
+    overlap, but each chunk's float16 predictions -- the values the reference would save -- are reduced on the GPU
+    (``ChunkPredictor.integrate``) against the sv plane that is resident anyway, instead of being downloaded: no result
+    ring, no per-chunk copy, one download of a few kilobytes at the end.
+
+    Pixel rule: a pixel is counted when its sv (of ``spec.frequency``) is finite and > 0; it belongs to a class by
+    ``spec.mode``; pixels without a prediction (overlap border, below the seabed) belong to none but count in the ``all``
+    plane; pings before ``start_ping`` are not visited and count nowhere.  Returns ``{"sv_sum": float64 [3, n_pb, n_rb] (sum of linear sv: sandeel, other, all
+    counted pixels), "pixels": int64 [3, n_pb, n_rb], "ping_edges", "range_edges", "classes"}`` (``finish_integration``);
+    ``nasc`` turns ``sv_sum`` into area backscattering.  Bins count global pings from 0 whatever ``start_ping``.
+    With torch.distributed initialised the chunks are dealt to the ranks as in ``predict_survey(shard="chunk")`` and the
+    accumulators all-reduced once at the end: every rank must call it and every rank returns the survey's result.  Sums
+    are fp64 in a fixed order: bit-reproducible for a given chunking and rank count, whatever ``batch_size``."""
+    flow = _SurveyChunks("integrate_survey", reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings,
+                         start_ping, labels_available, True, stats, predict_fn, share_patches=False)
+    spec = spec.bind(segpipe.frequencies)
+    acc, cnt = new_integration(flow.dev, spec, flow.n_pings, flow.n_range)
+    rank, world = parallel.rank_world()
+    if world > 1:
+        flow.own(rank, world)
+    if flow.chunks:
+        flow.check_model()
+        with flow.feed(("integrate",)) as feed:
+            for _ in flow.predicted(feed, then=lambda cp: cp.integrate(acc, cnt, spec)):
+                flow.note("enqueue_s", feed.t_taken)
+    return finish_integration(acc, cnt, spec, flow.n_pings, flow.n_range)
+
+
+def nasc(result, range_step_m):
+    """Nautical area scattering coefficient per cell and class from an integration result: ``4 pi 1852^2 * range_step_m *
+    sv_sum`` (m^2 nmi^-2 summed over the cell's pings; divide by the pings of a cell, ``np.diff(result["ping_edges"])``,
+    for the cell's mean NASC).  Assumes a UNIFORM range grid: every sample is ``range_step_m`` metres thick."""
+    return 4.0 * np.pi * 1852.0 ** 2 * float(range_step_m) * np.asarray(result["sv_sum"], dtype=np.float64)
 
 
 # ---- seabed line of a memmap echogram without a stored seabed.npy (Echogram.get_seabed, data_reader.py:433-507) ---------
@@ -987,6 +1156,22 @@ def predict_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_si
     grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
     out = cp.predict(grid, predict_fn=predict_fn)
     return out.cpu().numpy().astype(np.float64)
+
+
+def integrate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, spec, predict_fn=None,
+                            meta_channels=None, seabed=None):
+    """``integrate_survey`` for ONE memmap echogram: ``predict_echogram_memm``'s prediction (same arguments, the float16
+    values it would return) reduced on the GPU against the resident sv plane; same pixel rule, same return value; the
+    accumulators are not all-reduced (every rank that calls it returns the echogram's whole result).  The packed multi-echogram flow
+    (``predict_echograms_memm``) has no integrating counterpart yet: call this per echogram."""
+    cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
+                                     out_f16=True, wide=False, seabed=seabed)
+    spec = spec.bind(segpipe.frequencies)
+    grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
+    cp.predict(grid, predict_fn=predict_fn)
+    acc, cnt = new_integration(segpipe.device, spec, cp.end_ping, cp.n_range)
+    cp.integrate(acc, cnt, spec)
+    return finish_integration(acc, cnt, spec, cp.end_ping, cp.n_range, all_reduce=False)
 
 
 # ---- a memm survey: many small echograms in one prediction feed ----------------------------------------------------------

@@ -130,7 +130,7 @@ extern "C" {
  * points changes, and a binding must refuse a library whose version differs from the header it was written against (an
  * older build that happens to export every symbol would walk a descriptor array with the wrong stride).
  * crimac_layer_desc_size() is sizeof(crimac_layer_desc) as the library was compiled. */
-#define CRIMAC_ABI_VERSION 16
+#define CRIMAC_ABI_VERSION 17
 int crimac_version(void);
 int crimac_layer_desc_size(void);
 const char* crimac_last_error(void);
@@ -827,6 +827,37 @@ int crimac_upconv2x2_dgrad_narrow(int prec, const void* dy, long dy_ld, int B, i
  *   Element offsets are 64-bit: F * Pc * R may pass 2^31. */
 int crimac_seabed_columns(const float* data, int F, long Pc, int R, int has_left, int has_right, int n, int* idx,
                           float* colmax, long out_ld, void* stream);
+
+/* ---- echo integration by predicted class (csrc/integrate.hip) ------------------------------------------------
+ * The reduction of a finished prediction chunk: the linear sv of ONE frequency summed over the pixels assigned to a class,
+ * per cell of (ping bin x range bin).  The reference stops at the saved probabilities (save_predict.py:212, :252) and has
+ * no counterpart; the pixel rule is its remove_nan_inf (remove_nan_inf.py:24-32) plus positivity.
+ *   pred [2][n_range][n_pings]: what crimac_scatter_patches_ex wrote, float16 (pred_f16 = 1) or float32 (0); plane 0
+ *     sandeel, plane 1 other.  sv [data_pings][n_range] fp32 linear: one frequency plane of the chunk's data; column
+ *     sv_ping_off of sv belongs to column 0 of pred (sv_ping_off >= 0, sv_ping_off + n_pings <= data_pings).
+ *   mode 0 (threshold): the pixel belongs to class k when the stored pred_k, widened exactly to fp32, is >= thr_k (fp32
+ *     comparison); it may belong to both; its weight w_k is 1 or 0.  mode 1 (probability): w_k = pred_k (a negative or NaN
+ *     pred_k counts as 0).  thr_sandeel, thr_other must be > 0 in both modes: pixels the scatter left at 0 (overlap
+ *     border, below the seabed, outside the data) then belong to no class.
+ *   Cell (pb, rb) covers GLOBAL pings [pb * ping_bin, (pb + 1) * ping_bin) and rows [rb * range_bin, (rb + 1) * range_bin)
+ *     (the last range bin may be partial: n_rb = ceil(n_range / range_bin)); ping_origin is the global ping of pred column
+ *     0, ping_origin + n_pings <= n_pb_total * ping_bin, so that one survey-wide accumulator serves every chunk.
+ *   A pixel is COUNTED only when its sv is finite and > 0; NaN, +-Inf, 0 and negative sv add nothing anywhere.
+ *   acc fp64 [3][n_pb_total][n_rb] += (sum sv * w_sandeel, sum sv * w_other, sum sv) over the counted pixels;
+ *   cnt int64 [3][n_pb_total][n_rb] += (counted pixels with w_sandeel > 0, with w_other > 0, all counted pixels).
+ *   Both ACCUMULATE (caller zeroes) by a plain read-add-write: no atomics, so launches that touch the same cell must be
+ *   ordered (one stream).  Sums run in fp64 in a fixed order (thread over its tiles, lanes, waves, splits) that depends on
+ *   the arguments alone: bit-reproducible for a given chunking.  Counts are exact.
+ *   scratch: scratch_bytes of device memory, 8-byte aligned, at least ((cells of the launch) + CRIMAC_INTEGRATE_SPLIT_WGS)
+ *     * CRIMAC_INTEGRATE_SLOT_BYTES with cells = (ping bins that [ping_origin, ping_origin + n_pings) touches) * n_rb:
+ *     the partial results of a cell whose tiles were split over several workgroups (a launch with few cells would
+ *     otherwise leave most compute units idle); contents are undefined before and after. */
+#define CRIMAC_INTEGRATE_SPLIT_WGS 1024
+#define CRIMAC_INTEGRATE_SLOT_BYTES 48
+int crimac_integrate_classes(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv, long data_pings,
+                             long sv_ping_off, float thr_sandeel, float thr_other, int mode, long ping_bin, int range_bin,
+                             long ping_origin, long n_pb_total, double* acc, long long* cnt, void* scratch,
+                             long scratch_bytes, void* stream);
 
 /* ---- measurement support (bench.py only, not on the product path) --------------------------- */
 

@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""Echo integration by predicted class over a whole survey, patches/s of the two ways to get it on the same synthetic survey
+and model:
+
+  A  host    -- tiled_inference.predict_survey(out_dtype=np.float16), every chunk downloaded, the sv read a second time from
+                the reader, transposed, thresholded and binned in numpy: what a user does today;
+  A0 predict -- leg A's prediction part alone (the chunks are taken and dropped);
+  B  device  -- tiled_inference.integrate_survey: the chunk reduced on the GPU by crimac_integrate_classes, one download of a
+                few kilobytes at the end.
+
+Survey: synth.SyntheticSurveyReader (sv [4, pings, 1024] fp32, flat seabed 900, NaN / inf samples), patch 256, overlap 20,
+h3p inference.  The legs alternate in one process (A0, A, B per round) after one warm-up each; the figure of a leg is the
+median of its rounds.  Leg B is checked against leg A: counts equal, every sum within (n_cell_pixels + 2) * 2^-52 relative
+(tests/test_gpu_integrate.py).  The last line is one JSON object; --out writes it to a file as well."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import yaml  # noqa: E402
+
+import crimac_classifiers_unet_amd as pkg  # noqa: E402
+from crimac_classifiers_unet_amd import synth, tiled_inference as ti  # noqa: E402
+
+
+def host_chunk(acc, cnt, geo, out, sv, spec, s):
+    """One downloaded chunk ``out`` [2, R, e - s] float16 and the reader's ``sv`` [e - s, R] into the host accumulators."""
+    R, P = out.shape[1:]
+    sv_t = np.ascontiguousarray(sv.T)                                     # [R, P], as the predictions lie
+    ok = np.isfinite(sv_t) & (sv_t > 0)
+    s64 = np.where(ok, sv_t, 0).astype(np.float64)
+    p32 = out.astype(np.float32)
+    if spec.mode == "threshold":
+        member = p32 >= np.asarray(spec.thresholds, dtype=np.float32)[:, None, None]
+        weight = member.astype(np.float64)
+    else:
+        member = p32 > 0
+        weight = np.where(member, p32, 0).astype(np.float64)
+    pb = (s + np.arange(P)) // spec.ping_bin
+    p_starts = np.nonzero(np.diff(pb, prepend=pb[0] - 1))[0]
+    r_starts = np.arange(0, R, spec.range_bin)
+
+    def binned(a):
+        return np.add.reduceat(np.add.reduceat(a, r_starts, axis=-2), p_starts, axis=-1).swapaxes(-1, -2)
+    cells = slice(int(pb[0]), int(pb[-1]) + 1)
+    acc[:, cells] += binned(np.stack([s64 * weight[0], s64 * weight[1], s64]))
+    cnt[:, cells] += binned(np.stack([ok & member[0], ok & member[1], ok]).astype(np.int64))
+    geo[cells] += binned(np.ones((R, P), dtype=np.int64))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pings", type=int, default=16384)
+    ap.add_argument("--range", type=int, default=1024)
+    ap.add_argument("--preload", type=int, default=4096)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--precision", default="h3p", help="infer_precision")
+    ap.add_argument("--ping-bin", type=int, default=500)
+    ap.add_argument("--range-bin", type=int, default=50)
+    ap.add_argument("--mode", default="threshold")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    reader = synth.SyntheticSurveyReader(n_pings=a.pings, n_range=a.range, seabed_index=900, block=4096, schools=40,
+                                         bad_frac=1e-4)
+    cfg = yaml.safe_load(open(os.path.join(os.path.dirname(pkg.__file__), "configs", "pipeline_config.yaml")))
+    cfg.update(save_model_params=False, data_mode="zarr", infer_precision=a.precision)
+    pipe = pkg.SegPipeUNet(experiment_name="bench", **cfg)
+    pipe.model.load_state_dict(synth.synth_state_dict(seed=0))
+    pipe.model.to(pipe.device).eval()
+    pipe.model_is_loaded = True
+    patch, overlap = (256, 256), 20
+    spec = ti.IntegrationSpec(a.ping_bin, a.range_bin, mode=a.mode)
+    channel = spec.bind(pipe.frequencies).channel
+    n_pb, n_rb = spec.bins(a.pings, a.range)
+    patches = sum(len(ti.plan_grid(a.range, 900, s, e, patch, overlap)) for s, e in ti.plan_chunks(0, a.pings, a.preload))
+
+    def leg_predict():
+        for _ in ti.predict_survey(reader, pipe, patch, overlap, a.batch, a.preload, out_dtype=np.float16):
+            pass
+
+    def leg_host():
+        acc, cnt = np.zeros((3, n_pb, n_rb)), np.zeros((3, n_pb, n_rb), dtype=np.int64)
+        geo = np.zeros((n_pb, n_rb), dtype=np.int64)
+        for s, e, out in ti.predict_survey(reader, pipe, patch, overlap, a.batch, a.preload, out_dtype=np.float16):
+            sv = reader.get_data_slice(idx_ping=s, n_pings=e - s, frequencies=pipe.frequencies)[channel]
+            host_chunk(acc, cnt, geo, out, sv, spec, s)
+        return acc, cnt, geo
+
+    def leg_device():
+        return ti.integrate_survey(reader, pipe, patch, overlap, a.batch, a.preload, spec)
+
+    legs = {"predict": leg_predict, "host": leg_host, "device": leg_device}
+    times, last = {k: [] for k in legs}, {}
+    for rnd in range(-1, a.rounds):                                       # round -1: warm-up (staging, packed weights)
+        for name, fn in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            last[name] = fn()
+            torch.cuda.synchronize()
+            if rnd >= 0:
+                times[name].append(time.perf_counter() - t0)
+    acc, cnt, geo = last["host"]
+    got = last["device"]
+    counts_equal = bool(np.array_equal(got["pixels"], cnt))
+    err, bound = np.abs(got["sv_sum"] - acc), (geo[None] + 2) * 2.0 ** -52 * acc
+    within = bool((err <= bound).all() and (got["sv_sum"][acc == 0] == 0).all())
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    line = {
+        "bench": "integrate_survey", "pings": a.pings, "range": a.range, "preload": a.preload, "batch": a.batch,
+        "precision": a.precision, "ping_bin": a.ping_bin, "range_bin": a.range_bin, "mode": a.mode, "cells": [n_pb, n_rb],
+        "patches": patches, "rounds": a.rounds, "seconds": {k: [round(t, 4) for t in v] for k, v in times.items()},
+        "patches_per_s": {k: round(patches / t, 1) for k, t in med.items()},
+        "device_over_host": round(med["host"] / med["device"], 4),
+        "device_over_predict_alone": round(med["predict"] / med["device"], 4),
+        "counts_equal": counts_equal, "sums_within_bound": within,
+        "largest_error_over_bound": float((err[acc > 0] / bound[acc > 0]).max()),
+        "classified_pixels": [int(cnt[0].sum()), int(cnt[1].sum()), int(cnt[2].sum())],
+    }
+    for k in legs:
+        print(f"{k:8s}: {patches} patches, median {med[k]:.3f} s -> {patches / med[k]:.0f} patches/s", flush=True)
+    text = json.dumps(line)
+    print(text, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    assert counts_equal and within, "integrate_survey disagrees with the host integration"
+    assert med["device"] <= 1.03 * med["predict"], \
+        f"integrate_survey ({med['device']:.3f} s) is more than 3 % slower than the prediction alone ({med['predict']:.3f} s)"
+
+
+if __name__ == "__main__":
+    main()
