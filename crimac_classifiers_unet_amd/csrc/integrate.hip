@@ -16,6 +16,16 @@
 // (cell, split) slot of the scratch.  Pass 2: one thread per cell adds its S slots in split order and does a plain
 // read-add-write of the cell's six outputs.  No atomics anywhere: launches that touch the same cell are ordered by the
 // stream, S depends on the shapes alone, so the result is bit-reproducible for a given chunking.
+//
+// crimac_integrate_layers (the SEABED instantiations of the same kernel): ping p of the launch has a row limit
+// L[p] = clamp(seabed[p] + seabed_offset, 0, n_range) and rows >= L[p] count nowhere.  Surface reference: the cells above,
+// each ping's rows cut at its limit.  Seabed reference: column l of the accumulator is layer l, rows [L[p] - (l + 1) *
+// range_bin, L[p] - l * range_bin) of ping p -- counted from the limit, so the layer follows the relief.  The workgroup
+// stays (ping bin, layer, split): it first reduces min and max of L over its ping span, walks the tiles of that row
+// bounding box and keeps a pixel when its row lies in its ping's own interval [lo, hi), which the tile's 64 pings hold in
+// LDS (written once per tile, read into registers by the four pings a thread consumes).  With relief above range_bin the
+// boxes of neighbouring layers overlap and those tiles are read once per layer.  S is bounded by the tiles of the whole
+// column, whatever the seabed values: a workgroup whose split finds no tile writes a zero slot.
 #include "common.h"
 
 namespace {
@@ -30,6 +40,9 @@ struct Geom {
   int n_range, range_bin, n_rb, splits, mode;
   long n_pings, sv_ping_off, ping_bin, ping_origin, n_pb_total, pb0;
   float thr0, thr1;
+  // crimac_integrate_layers: the seabed line from the launch's ping 0 on, the offset of the limit, 0 surface / 1 seabed
+  const int* seabed;
+  int seabed_offset, reference;
 };
 
 // the cell's extent in the launch's coordinates (rows; pings relative to pred column 0), clipped to the launch
@@ -44,6 +57,12 @@ __device__ __forceinline__ Cell cell_of(const Geom& g, long cell) {
   c.p0 = p0 > 0 ? p0 : 0;
   c.p1 = p1 < g.n_pings ? p1 : g.n_pings;
   return c;
+}
+
+// L[p]: the first row of ping p (relative to the launch) that counts nowhere
+__device__ __forceinline__ int row_limit(const Geom& g, long p) {
+  const long v = (long)g.seabed[p] + g.seabed_offset;
+  return (int)(v < 0 ? 0 : v < g.n_range ? v : g.n_range);
 }
 
 template <typename TP> __device__ __forceinline__ float widen(TP v) { return (float)v; }
@@ -67,7 +86,7 @@ __device__ __forceinline__ void load_pred(const TP* __restrict__ row, long p, lo
   }
 }
 
-template <typename TP, bool VEC_SV, bool VEC_PRED>
+template <typename TP, bool VEC_SV, bool VEC_PRED, bool SEABED>
 __global__ __launch_bounds__(kThreads) void integrate_cells_kernel(const TP* __restrict__ pred, const float* __restrict__ sv,
                                                                    Geom g, Slot* __restrict__ scratch) {
   __shared__ float tile[kTile * kPitch];
@@ -75,7 +94,40 @@ __global__ __launch_bounds__(kThreads) void integrate_cells_kernel(const TP* __r
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const long cell = blockIdx.x / g.splits;
   const int split = (int)(blockIdx.x - cell * g.splits);
-  const Cell c = cell_of(g, cell);
+  Cell c = cell_of(g, cell);
+  // SEABED: rows [lo, hi) of a tile's 64 pings; seabed reference: the layer ends `top` rows above the limit
+  __shared__ int row_lo[SEABED ? kTile : 1], row_hi[SEABED ? kTile : 1];
+  const int cell_r0 = c.r0, cell_r1 = c.r1;
+  long top = 0;
+  if constexpr (SEABED) {
+    __shared__ int span_min[kThreads / 64], span_max[kThreads / 64];
+    int lmin = g.n_range, lmax = 0;                             // (every limit lies in [0, n_range])
+    for (long p = c.p0 + t; p < c.p1; p += kThreads) {
+      const int L = row_limit(g, p);
+      lmin = L < lmin ? L : lmin;
+      lmax = L > lmax ? L : lmax;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int a = __shfl_xor(lmin, o, 64), b = __shfl_xor(lmax, o, 64);
+      lmin = a < lmin ? a : lmin;
+      lmax = b > lmax ? b : lmax;
+    }
+    if (lane == 0) span_min[wave] = lmin, span_max[wave] = lmax;
+    __syncthreads();
+    for (int w = 0; w < kThreads / 64; ++w) {
+      lmin = span_min[w] < lmin ? span_min[w] : lmin;
+      lmax = span_max[w] > lmax ? span_max[w] : lmax;
+    }
+    if (g.reference == 1) {                                     // the row bounding box of the layer over the ping span
+      top = (cell % g.n_rb) * g.range_bin;
+      const long b0 = lmin - top - g.range_bin, b1 = lmax - top;
+      c.r0 = (int)(b0 > 0 ? b0 : 0);
+      c.r1 = (int)(b1 > 0 ? b1 : 0);
+    } else {
+      c.r1 = c.r1 < lmax ? c.r1 : lmax;                         // no ping of the span counts a row below
+    }
+  }
   // tile origins are multiples of 4 in both directions, so that a 16-byte access never straddles an edge it may not cross
   const int ra = c.r0 & ~3;
   const long pa = c.p0 & ~3L;
@@ -127,8 +179,24 @@ __global__ __launch_bounds__(kThreads) void integrate_cells_kernel(const TP* __r
         for (int j = 0; j < 4; ++j) pr0[k][j] = pr1[k][j] = 0.f;
       }
     }
+    int lo = 0, hi = 0;                                       // SEABED: the rows of ping tp + t that count here
+    if constexpr (SEABED) {
+      if (t < kTile && tp + t >= c.p0 && tp + t < c.p1) {
+        const long L = row_limit(g, tp + t);
+        if (g.reference == 1) {
+          lo = (int)(L - top - g.range_bin > 0 ? L - top - g.range_bin : 0);
+          hi = (int)(L - top > 0 ? L - top : 0);
+        } else {
+          lo = cell_r0;
+          hi = (int)(L < cell_r1 ? L : cell_r1);
+        }
+      }
+    }
     // ---- sv registers -> LDS tile [ping][row]
     __syncthreads();                                          // (the previous tile has been consumed)
+    if constexpr (SEABED) {
+      if (t < kTile) row_lo[t] = lo, row_hi[t] = hi;
+    }
     if constexpr (VEC_SV) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -145,6 +213,15 @@ __global__ __launch_bounds__(kThreads) void integrate_cells_kernel(const TP* __r
     }
     __syncthreads();
     // ---- the pixel rule
+    int plo[4], phi[4];
+    if constexpr (SEABED) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int pl = VEC_PRED ? 4 * l16 + j : l16 + 16 * j;
+        plo[j] = row_lo[pl] - tr;                               // (relative to the tile's first row)
+        phi[j] = row_hi[pl] - tr;
+      }
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int rl = row_in_group + 16 * k;
@@ -152,7 +229,8 @@ __global__ __launch_bounds__(kThreads) void integrate_cells_kernel(const TP* __r
       for (int j = 0; j < 4; ++j) {
         const int pl = VEC_PRED ? 4 * l16 + j : l16 + 16 * j;
         const float s = tile[pl * kPitch + rl];
-        const bool ok = s > 0.f && s < __builtin_inff();      // finite and > 0 (NaN fails both)
+        bool ok = s > 0.f && s < __builtin_inff();            // finite and > 0 (NaN fails both)
+        if constexpr (SEABED) ok = ok && rl >= plo[j] && rl < phi[j];
         const float a = pr0[k][j], b = pr1[k][j];
         const double sd = ok ? (double)s : 0.0;
         if (g.mode == 0) {
@@ -216,41 +294,52 @@ __global__ __launch_bounds__(kThreads) void integrate_finish_kernel(const Slot* 
   }
 }
 
-template <typename TP>
+template <typename TP, bool SEABED>
 void launch_cells(bool vec_sv, bool vec_pred, unsigned blocks, hipStream_t st, const void* pred, const float* sv,
                   const Geom& g, Slot* scratch) {
   const TP* p = static_cast<const TP*>(pred);
-  if (vec_sv && vec_pred) hipLaunchKernelGGL((integrate_cells_kernel<TP, true, true>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
-  else if (vec_sv) hipLaunchKernelGGL((integrate_cells_kernel<TP, true, false>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
-  else if (vec_pred) hipLaunchKernelGGL((integrate_cells_kernel<TP, false, true>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
-  else hipLaunchKernelGGL((integrate_cells_kernel<TP, false, false>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
+  if (vec_sv && vec_pred) hipLaunchKernelGGL((integrate_cells_kernel<TP, true, true, SEABED>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
+  else if (vec_sv) hipLaunchKernelGGL((integrate_cells_kernel<TP, true, false, SEABED>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
+  else if (vec_pred) hipLaunchKernelGGL((integrate_cells_kernel<TP, false, true, SEABED>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
+  else hipLaunchKernelGGL((integrate_cells_kernel<TP, false, false, SEABED>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
 }
 
-}  // namespace
+// what crimac_integrate_layers adds to the arguments of crimac_integrate_classes (null: that entry point)
+struct SeabedArgs { const int* line; long first, len; int offset, reference, n_layers; };
 
-extern "C" int crimac_integrate_classes(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv,
-                                        long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode,
-                                        long ping_bin, int range_bin, long ping_origin, long n_pb_total, double* acc,
-                                        long long* cnt, void* scratch, long scratch_bytes, void* stream) {
-  CRIMAC_REQUIRE(pred && sv && acc && cnt && scratch, "integrate_classes: null pointer");
-  CRIMAC_REQUIRE(pred_f16 == 0 || pred_f16 == 1, "integrate_classes: pred_f16 is 0 or 1");
-  CRIMAC_REQUIRE(n_range > 0 && n_pings > 0, "integrate_classes: empty prediction array (%d x %ld)", n_range, n_pings);
-  CRIMAC_REQUIRE(mode == 0 || mode == 1, "integrate_classes: mode %d (0 threshold, 1 probability)", mode);
-  CRIMAC_REQUIRE(thr_sandeel > 0.f && thr_other > 0.f, "integrate_classes: thr = (%g, %g) must be > 0 (pixels the scatter "
-                 "left at 0 belong to no class)", (double)thr_sandeel, (double)thr_other);
-  CRIMAC_REQUIRE(ping_bin > 0 && range_bin > 0, "integrate_classes: ping_bin=%ld, range_bin=%d must be positive", ping_bin,
-                 range_bin);
-  CRIMAC_REQUIRE(ping_bin <= 2147483647L && n_pb_total <= 2147483647L, "integrate_classes: ping_bin=%ld, n_pb_total=%ld "
-                 "beyond 2^31 - 1", ping_bin, n_pb_total);
-  CRIMAC_REQUIRE(sv_ping_off >= 0 && sv_ping_off + n_pings <= data_pings, "integrate_classes: sv columns [%ld, %ld) outside "
-                 "the sv extent of %ld pings", sv_ping_off, sv_ping_off + n_pings, data_pings);
+// Both entry points: the argument checks, the geometry, the two launches.  `who` names the caller in the messages.
+int integrate(const char* who, const SeabedArgs* sb, const void* pred, int pred_f16, int n_range, long n_pings,
+              const float* sv, long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode, long ping_bin,
+              int range_bin, long ping_origin, long n_pb_total, double* acc, long long* cnt, void* scratch,
+              long scratch_bytes, void* stream) {
+  CRIMAC_REQUIRE(pred && sv && acc && cnt && scratch, "%s: null pointer", who);
+  CRIMAC_REQUIRE(pred_f16 == 0 || pred_f16 == 1, "%s: pred_f16 is 0 or 1", who);
+  CRIMAC_REQUIRE(n_range > 0 && n_pings > 0, "%s: empty prediction array (%d x %ld)", who, n_range, n_pings);
+  CRIMAC_REQUIRE(mode == 0 || mode == 1, "%s: mode %d (0 threshold, 1 probability)", who, mode);
+  CRIMAC_REQUIRE(thr_sandeel > 0.f && thr_other > 0.f, "%s: thr = (%g, %g) must be > 0 (pixels the scatter "
+                 "left at 0 belong to no class)", who, (double)thr_sandeel, (double)thr_other);
+  CRIMAC_REQUIRE(ping_bin > 0 && range_bin > 0, "%s: ping_bin=%ld, range_bin=%d must be positive", who, ping_bin, range_bin);
+  CRIMAC_REQUIRE(ping_bin <= 2147483647L && n_pb_total <= 2147483647L, "%s: ping_bin=%ld, n_pb_total=%ld "
+                 "beyond 2^31 - 1", who, ping_bin, n_pb_total);
+  CRIMAC_REQUIRE(sv_ping_off >= 0 && sv_ping_off + n_pings <= data_pings, "%s: sv columns [%ld, %ld) outside "
+                 "the sv extent of %ld pings", who, sv_ping_off, sv_ping_off + n_pings, data_pings);
   CRIMAC_REQUIRE(ping_origin >= 0 && n_pb_total > 0 && ping_origin + n_pings <= n_pb_total * ping_bin,
-                 "integrate_classes: pings [%ld, %ld) outside the accumulator's %ld bins of %ld pings", ping_origin,
+                 "%s: pings [%ld, %ld) outside the accumulator's %ld bins of %ld pings", who, ping_origin,
                  ping_origin + n_pings, n_pb_total, ping_bin);
+  const bool layers = sb && sb->reference == 1;
+  if (sb) {
+    CRIMAC_REQUIRE(sb->line, "%s: null seabed vector", who);
+    CRIMAC_REQUIRE(sb->first >= 0 && sb->first + n_pings <= sb->len, "%s: pings [%ld, %ld) outside the seabed vector of "
+                   "%ld pings", who, sb->first, sb->first + n_pings, sb->len);
+    CRIMAC_REQUIRE(sb->reference == 0 || sb->reference == 1, "%s: reference %d (0 surface, 1 seabed)", who, sb->reference);
+    CRIMAC_REQUIRE(!layers || (sb->n_layers >= 1 && (long)sb->n_layers * range_bin <= 2147483647L),
+                   "%s: n_layers=%d with the seabed reference must be >= 1 (and n_layers * range_bin below 2^31)", who,
+                   sb->n_layers);
+  }
   Geom g;
   g.n_range = n_range;
   g.range_bin = range_bin;
-  g.n_rb = (n_range + range_bin - 1) / range_bin;
+  g.n_rb = layers ? sb->n_layers : (n_range + range_bin - 1) / range_bin;
   g.mode = mode;
   g.n_pings = n_pings;
   g.sv_ping_off = sv_ping_off;
@@ -260,25 +349,55 @@ extern "C" int crimac_integrate_classes(const void* pred, int pred_f16, int n_ra
   g.pb0 = ping_origin / ping_bin;
   g.thr0 = thr_sandeel;
   g.thr1 = thr_other;
+  g.seabed = sb ? sb->line + sb->first : nullptr;
+  g.seabed_offset = sb ? sb->offset : 0;
+  g.reference = sb ? sb->reference : 0;
   const long cells = ((ping_origin + n_pings - 1) / ping_bin - g.pb0 + 1) * g.n_rb;
-  // tiles of a full cell (its origin may sit up to 3 short of a multiple of 4 in either direction)
-  const long span_r = (range_bin < n_range ? range_bin : n_range) + 3, span_p = (ping_bin < n_pings ? ping_bin : n_pings) + 3;
+  // tiles of a full cell (its origin may sit up to 3 short of a multiple of 4 in either direction); the row bounding box
+  // of a seabed-referenced layer may be the whole column
+  const long span_r = (range_bin < n_range && !layers ? range_bin : n_range) + 3, span_p = (ping_bin < n_pings ? ping_bin : n_pings) + 3;
   const long tiles = ((span_r + kTile - 1) / kTile) * ((span_p + kTile - 1) / kTile);
   const long want = (CRIMAC_INTEGRATE_SPLIT_WGS + cells - 1) / cells;
   g.splits = (int)(want < tiles ? want : tiles);
-  CRIMAC_REQUIRE(cells * g.splits <= 2147483647L, "integrate_classes: %ld cells in one launch", cells);
+  CRIMAC_REQUIRE(cells * g.splits <= 2147483647L, "%s: %ld cells in one launch", who, cells);
   CRIMAC_REQUIRE(scratch_bytes >= cells * g.splits * (long)sizeof(Slot) && (uintptr_t)scratch % 8 == 0,
-                 "integrate_classes: scratch of %ld bytes, this launch needs %ld (8-byte aligned; (cells + "
-                 "CRIMAC_INTEGRATE_SPLIT_WGS) * CRIMAC_INTEGRATE_SLOT_BYTES always suffices)", scratch_bytes,
+                 "%s: scratch of %ld bytes, this launch needs %ld (8-byte aligned; (cells + "
+                 "CRIMAC_INTEGRATE_SPLIT_WGS) * CRIMAC_INTEGRATE_SLOT_BYTES always suffices)", who, scratch_bytes,
                  cells * g.splits * (long)sizeof(Slot));
   const bool vec_sv = n_range % 4 == 0 && (uintptr_t)sv % 16 == 0;
   const bool vec_pred = n_pings % 4 == 0 && (uintptr_t)pred % (pred_f16 ? 8 : 16) == 0;
   const hipStream_t st = (hipStream_t)stream;
-  if (pred_f16) launch_cells<half_t>(vec_sv, vec_pred, (unsigned)(cells * g.splits), st, pred, sv, g, (Slot*)scratch);
-  else launch_cells<float>(vec_sv, vec_pred, (unsigned)(cells * g.splits), st, pred, sv, g, (Slot*)scratch);
+  const unsigned blocks = (unsigned)(cells * g.splits);
+  if (sb) {
+    if (pred_f16) launch_cells<half_t, true>(vec_sv, vec_pred, blocks, st, pred, sv, g, (Slot*)scratch);
+    else launch_cells<float, true>(vec_sv, vec_pred, blocks, st, pred, sv, g, (Slot*)scratch);
+  } else {
+    if (pred_f16) launch_cells<half_t, false>(vec_sv, vec_pred, blocks, st, pred, sv, g, (Slot*)scratch);
+    else launch_cells<float, false>(vec_sv, vec_pred, blocks, st, pred, sv, g, (Slot*)scratch);
+  }
   CRIMAC_LAUNCH_CHECK();
   hipLaunchKernelGGL(integrate_finish_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
                      (const Slot*)scratch, g, cells, acc, cnt);
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
+}
+
+}  // namespace
+
+extern "C" int crimac_integrate_classes(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv,
+                                        long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode,
+                                        long ping_bin, int range_bin, long ping_origin, long n_pb_total, double* acc,
+                                        long long* cnt, void* scratch, long scratch_bytes, void* stream) {
+  return integrate("integrate_classes", nullptr, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, thr_sandeel,
+                   thr_other, mode, ping_bin, range_bin, ping_origin, n_pb_total, acc, cnt, scratch, scratch_bytes, stream);
+}
+
+extern "C" int crimac_integrate_layers(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv,
+                                       long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode,
+                                       long ping_bin, int range_bin, long ping_origin, long n_pb_total, const int* seabed,
+                                       long seabed_first, long seabed_len, int seabed_offset, int reference, int n_layers,
+                                       double* acc, long long* cnt, void* scratch, long scratch_bytes, void* stream) {
+  const SeabedArgs sb{seabed, seabed_first, seabed_len, seabed_offset, reference, n_layers};
+  return integrate("integrate_layers", &sb, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, thr_sandeel,
+                   thr_other, mode, ping_bin, range_bin, ping_origin, n_pb_total, acc, cnt, scratch, scratch_bytes, stream);
 }

@@ -135,7 +135,7 @@ del _header
 
 ABI_VERSION = DEFINES["CRIMAC_ABI_VERSION"]      # a built library of another version is stale (load_library)
 PR_BINS = DEFINES["CRIMAC_PR_BINS"]
-# scratch of crimac_integrate_classes: (cells of the launch + INTEGRATE_SPLIT_WGS) slots of INTEGRATE_SLOT_BYTES
+# scratch of crimac_integrate_classes / crimac_integrate_layers: (cells of the launch + INTEGRATE_SPLIT_WGS) slots of INTEGRATE_SLOT_BYTES
 INTEGRATE_SPLIT_WGS, INTEGRATE_SLOT_BYTES = DEFINES["CRIMAC_INTEGRATE_SPLIT_WGS"], DEFINES["CRIMAC_INTEGRATE_SLOT_BYTES"]
 # name -> argtypes of every entry point that returns a status and takes the stream as its last argument (`call`)
 SIGNATURES = {name: args for name, (res, args, stream) in PROTOTYPES.items() if stream and res is C.c_int}
@@ -209,6 +209,11 @@ def load_library():
         size = declare(size_fn)()
         if size != C.sizeof(mirror):
             raise HipLibraryError(f"{path}: {size_fn[:-5]} is {size} bytes in the library, {C.sizeof(mirror)} in this binding")
+    # additive entry points do not bump the ABI version: a build of the same version from before one was added is stale too
+    missing = [name for name in PROTOTYPES if not hasattr(lib, name)]
+    if missing:
+        raise HipLibraryError(f"{path} does not export {', '.join(missing)}: stale build, rebuild it "
+                              "(`python -m crimac_classifiers_unet_amd.build --force`)")
     for name in PROTOTYPES:
         fn = declare(name)
         if name in SIGNATURES:

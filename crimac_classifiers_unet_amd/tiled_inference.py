@@ -25,8 +25,10 @@ that a caller appends with the reference's ``create_xarray_ds_predictions`` / ``
 ``predict_echogram_memm`` returns the array ``save_reader_predictions_memm`` would ``np.save``;
 ``predict_echograms_memm`` does so for a whole memm survey, its forward batches packed across the echograms, and
 ``evaluate_echograms_memm`` evaluates one (PR histograms) in the same way.  ``integrate_survey`` /
-``integrate_echogram_memm`` reduce the predictions on the GPU instead of returning them: echo integration by predicted
-class (``crimac_integrate_classes``), the sv of one frequency summed per class and (ping bin x range bin) cell.
+``integrate_echogram_memm`` / ``integrate_echograms_memm`` (a whole memm survey, packed) reduce the predictions on the GPU
+instead of returning them: echo integration by predicted class (``crimac_integrate_classes``), the sv of one frequency
+summed per class and (ping bin x range bin) cell -- or, with a seabed-aware ``IntegrationSpec``
+(``crimac_integrate_layers``), only above a per-ping limit at the seabed line and per bottom layer counted from it.
 """
 from __future__ import annotations
 
@@ -130,7 +132,7 @@ class ChunkPredictor:
         self.batch_size = int(batch_size)
         self.out_f16 = bool(out_f16)
         self.flavour = "zarr"
-        self.seabed = self.mask = None
+        self.seabed = self.mask = self.mask_line = None
         # MetaSource: needed by a UNet_LateMetInject model (metadata planes per crop) and by an early-injection model
         # (UNet_Baseline whose input channels are the data planes + the metadata planes, gathered into the same crop)
         self.meta_source = None
@@ -166,6 +168,7 @@ class ChunkPredictor:
         self.data_ping0 = int(data_ping0)
         self.labels = up(labels, np.int16)
         self.mask = up(seabed_mask, np.uint8)
+        self.mask_line = None                # (the mask's limit line, built by the first seabed-aware integrate())
         self.seabed = up(seabed, np.int32)
         self.seabed_ping0 = int(start_ping if seabed_ping0 is None else seabed_ping0)
         self.start_ping, self.end_ping = int(start_ping), int(end_ping)
@@ -228,7 +231,10 @@ class ChunkPredictor:
         """Echo integration of the chunk ``predict`` has just filled (``crimac_integrate_classes``): the linear sv of
         ``self.data[spec.channel]`` summed per class and cell into ``acc`` float64 / ``cnt`` int64
         ``[3, n_pb_total, n_rb]`` on the GPU (``new_integration``), which cover global pings from 0.  ``spec``: a bound
-        ``IntegrationSpec``.  Launches on the current stream, after the scatter; nothing comes back."""
+        ``IntegrationSpec``.  Launches on the current stream, after the scatter; nothing comes back.
+        A seabed-aware spec (``seabed_offset`` given) runs ``crimac_integrate_layers`` with the chunk's seabed line
+        (``_limit_line``: the vector, or the first masked row per ping of a chunk loaded with a 2-D mask); with the seabed
+        reference the accumulators are ``[3, n_pb_total, layers]``."""
         if self.wide or self.out is None:
             raise ValueError("ChunkPredictor.integrate: the chunk was loaded for evaluate() (wide=True) and has no predictions")
         if spec.channel is None:
@@ -243,14 +249,28 @@ class ChunkPredictor:
                              f"{acc.dtype} {tuple(acc.shape)}, {cnt.dtype} {tuple(cnt.shape)}")
         n = self.end_ping - self.start_ping
         cells = ((self.end_ping - 1) // spec.ping_bin - self.start_ping // spec.ping_bin + 1) * n_rb
-        scratch = self.engine._buf("integrate.scratch", ((cells + hip.INTEGRATE_SPLIT_WGS) * hip.INTEGRATE_SLOT_BYTES // 8,),
-                                   torch.float64)
+        scratch = integration_scratch(self.engine, cells)
         sv = self.data[spec.channel]
         with torch.cuda.device(self.out.device):
-            call("crimac_integrate_classes", ptr(self.out), 1 if self.out_f16 else 0, self.n_range, n, ptr(sv),
-                 int(sv.shape[0]), self.start_ping - self.data_ping0, spec.thresholds[0], spec.thresholds[1],
-                 IntegrationSpec.MODES.index(spec.mode), spec.ping_bin, spec.range_bin, self.start_ping,
-                 int(acc.shape[1]), ptr(acc), ptr(cnt), ptr(scratch), scratch.numel() * 8)
+            launch_integration(spec, ptr(self.out), self.out_f16, self.n_range, n, ptr(sv), int(sv.shape[0]),
+                               self.start_ping - self.data_ping0, self.start_ping, int(acc.shape[1]), ptr(acc), ptr(cnt),
+                               scratch, seabed=self._limit_line() if spec.seabed_aware else None)
+
+    def _limit_line(self):
+        """The seabed line of a seabed-aware integration, as ``(pointer, index of ping start_ping, length)``: the chunk's
+        seabed vector; for a chunk that holds a 2-D mask instead -- a zarr block the vector could not express
+        (``seabed_vector_or_mask``) -- the first masked row of every ping, ``n_range`` where a ping has none, computed on
+        the device once per chunk; a chunk with neither has no line: ValueError."""
+        if self.seabed is not None:
+            return ptr(self.seabed), self.start_ping - self.seabed_ping0, self.seabed.numel()
+        if self.mask is None:
+            raise ValueError("ChunkPredictor.integrate: a spec with seabed_offset needs the chunk's seabed vector or mask, "
+                             "and the chunk was loaded with neither")
+        if self.mask_line is None:
+            below = self.mask != 0                               # [pings, range]; argmax: the FIRST maximal element
+            first = below.to(torch.uint8).argmax(dim=1)
+            self.mask_line = torch.where(below.any(dim=1), first, torch.full_like(first, self.n_range)).to(torch.int32)
+        return ptr(self.mask_line), 0, self.mask_line.numel()
 
     def _early(self):       # metadata planes as extra input channels
         return not self.engine.lmi and self.engine.in_channels > self.data.shape[0]
@@ -892,13 +912,42 @@ class IntegrationSpec:
     ``segpipe.frequencies``; None takes 38 (kHz, the memm readers and the yaml) or, failing that, 38000 (Hz, the zarr
     readers).  ``mode`` "threshold": a pixel belongs to class k when its stored probability >= ``thresholds[k]``
     (sandeel, other; it may belong to both); "probability": its sv counts with weight = the stored probability.
-    ``thresholds`` must be > 0 in both modes.  ``bind(frequencies)`` returns the spec with ``channel`` looked up."""
-    MODES = ("threshold", "probability")
+    ``thresholds`` must be > 0 in both modes.  ``bind(frequencies)`` returns the spec with ``channel`` looked up.
 
-    def __init__(self, ping_bin, range_bin, frequency=None, thresholds=(0.5, 0.5), mode="threshold", channel=None):
+    **Seabed** (``crimac_integrate_layers``).  ``seabed_offset`` = an integer k (it may be negative): ping p has the row
+    limit ``L[p] = clamp(seabed[p] + k, 0, n_range)`` and rows ``r >= L[p]`` count in NO plane, neither sums nor pixels;
+    k < 0 is the usual backstep above the detected bottom, k = ``+SEABED_PAD`` the row rule of the memm scatter.  None
+    (default): no limit, the bottom echo counts in the ``all`` plane.  ``reference`` "surface" (default): the cells above,
+    each ping's rows cut at its limit.  ``reference`` "seabed" (needs ``seabed_offset`` and ``layers``, a positive
+    integer): the range axis of the result is ``layers`` bottom layers -- layer l of ping p covers rows
+    ``[L[p] - (l + 1) * range_bin, L[p] - l * range_bin)`` clipped to ``[0, n_range)``.  Layer rows are counted FROM THE
+    LIMIT, not from the surface: layer 0 touches it, a layer follows the relief inside a ping bin, and rows above the
+    top layer belong to no layer and are dropped."""
+    MODES = ("threshold", "probability")
+    REFERENCES = ("surface", "seabed")
+
+    def __init__(self, ping_bin, range_bin, frequency=None, thresholds=(0.5, 0.5), mode="threshold", channel=None,
+                 seabed_offset=None, reference="surface", layers=None):
+        def integer(v):
+            return not isinstance(v, bool) and isinstance(v, (int, np.integer))
         for name, v in (("ping_bin", ping_bin), ("range_bin", range_bin)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            if not integer(v) or v < 1:
                 raise ValueError(f"IntegrationSpec: {name}={v!r} must be a positive integer")
+        if seabed_offset is not None and not (integer(seabed_offset) and abs(int(seabed_offset)) < 2 ** 30):
+            raise ValueError(f"IntegrationSpec: seabed_offset={seabed_offset!r} must be None or an integer (rows; negative: "
+                             "above the seabed line)")
+        if reference not in self.REFERENCES:
+            raise ValueError(f"IntegrationSpec: reference={reference!r}: 'surface' or 'seabed'")
+        if reference == "seabed":
+            if seabed_offset is None:
+                raise ValueError("IntegrationSpec: reference='seabed' needs seabed_offset (an integer; 0: layers end at the "
+                                 "seabed line)")
+            if not integer(layers) or layers < 1 or int(layers) * int(range_bin) >= 2 ** 31:
+                raise ValueError(f"IntegrationSpec: reference='seabed' needs layers, a positive integer (layers * range_bin "
+                                 f"below 2^31); got layers={layers!r}")
+        elif layers is not None:
+            raise ValueError(f"IntegrationSpec: layers={layers!r} belongs to reference='seabed' (the surface grid has "
+                             "ceil(n_range / range_bin) range bins)")
         if mode not in self.MODES:
             raise ValueError(f"IntegrationSpec: mode={mode!r}: 'threshold' or 'probability'")
         try:
@@ -910,6 +959,13 @@ class IntegrationSpec:
                              "at 0 belong to no class)")
         self.ping_bin, self.range_bin, self.frequency = int(ping_bin), int(range_bin), frequency
         self.thresholds, self.mode, self.channel = thresholds, mode, channel
+        self.seabed_offset = None if seabed_offset is None else int(seabed_offset)
+        self.reference, self.layers = reference, None if layers is None else int(layers)
+
+    @property
+    def seabed_aware(self):
+        """Whether the spec needs the seabed line (``crimac_integrate_layers``) or not (``crimac_integrate_classes``)."""
+        return self.seabed_offset is not None
 
     def bind(self, frequencies):
         """The spec with ``channel`` = the index of its frequency in ``frequencies``; ValueError if it is not there."""
@@ -917,13 +973,16 @@ class IntegrationSpec:
         wanted = (38, 38000) if self.frequency is None else (self.frequency,)
         for f in wanted:
             if float(f) in freqs:
-                return IntegrationSpec(self.ping_bin, self.range_bin, f, self.thresholds, self.mode, freqs.index(float(f)))
+                return IntegrationSpec(self.ping_bin, self.range_bin, f, self.thresholds, self.mode, freqs.index(float(f)),
+                                       seabed_offset=self.seabed_offset, reference=self.reference, layers=self.layers)
         raise ValueError(f"IntegrationSpec: frequency {' / '.join(str(f) for f in wanted)} is not among the model's "
                          f"frequencies {list(frequencies)}")
 
     def bins(self, n_pings, n_range):
-        """(ping bins, range bins) that cover global pings [0, n_pings) and rows [0, n_range)."""
-        return -(-int(n_pings) // self.ping_bin), -(-int(n_range) // self.range_bin)
+        """(ping bins, range bins) that cover global pings [0, n_pings) and rows [0, n_range); with the seabed reference
+        (ping bins, ``layers``)."""
+        n_pb = -(-int(n_pings) // self.ping_bin)
+        return n_pb, self.layers if self.reference == "seabed" else -(-int(n_range) // self.range_bin)
 
 
 def new_integration(dev, spec, n_pings, n_range):
@@ -932,19 +991,52 @@ def new_integration(dev, spec, n_pings, n_range):
     return torch.zeros(shape, dtype=torch.float64, device=dev), torch.zeros(shape, dtype=torch.int64, device=dev)
 
 
+def integration_scratch(engine, cells):
+    """The scratch of an integrate launch of ``cells`` = (ping bins it touches) x (range bins or layers), from the
+    engine's buffer cache: (cells + INTEGRATE_SPLIT_WGS) slots always suffice."""
+    return engine._buf("integrate.scratch", ((cells + hip.INTEGRATE_SPLIT_WGS) * hip.INTEGRATE_SLOT_BYTES // 8,), torch.float64)
+
+
+def launch_integration(spec, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, ping_origin, n_pb_total, acc,
+                       cnt, scratch, seabed=None):
+    """One integrate launch by a bound ``spec``: ``crimac_integrate_classes``, or -- a seabed-aware spec --
+    ``crimac_integrate_layers`` with ``seabed`` = (pointer to an int32 line, index of pred's column 0 in it, its length).
+    ``pred`` / ``sv`` / ``acc`` / ``cnt``: device pointers (``hip.ptr``); ``scratch``: a float64 tensor."""
+    head = (pred, 1 if pred_f16 else 0, n_range, n_pings, sv, data_pings, sv_ping_off, spec.thresholds[0],
+            spec.thresholds[1], IntegrationSpec.MODES.index(spec.mode), spec.ping_bin, spec.range_bin, ping_origin, n_pb_total)
+    tail = (acc, cnt, ptr(scratch), scratch.numel() * 8)
+    if not spec.seabed_aware:
+        call("crimac_integrate_classes", *head, *tail)
+    else:
+        call("crimac_integrate_layers", *head, *seabed, spec.seabed_offset, IntegrationSpec.REFERENCES.index(spec.reference),
+             spec.layers or 0, *tail)
+
+
 def finish_integration(acc, cnt, spec, n_pings, n_range, all_reduce=True):
     """The accumulators -> the result of the integration flows (numpy, ONE download): ``sv_sum`` float64 and ``pixels``
     int64 ``[3, n_pb, n_rb]`` (planes ``classes`` = sandeel, other, all counted pixels), ``ping_edges`` int64 [n_pb + 1]
     and ``range_edges`` int64 [n_rb + 1] (the last edge is the survey's end, so a partial last bin shows).  With several
-    ranks the accumulators are all-reduced first (sum), the one collective of the flow."""
+    ranks the accumulators are all-reduced first (sum), the one collective of the flow.  A seabed-aware spec
+    (``seabed_offset`` given) adds ``"reference"`` and ``"seabed_offset"``; with the seabed reference the range axis holds
+    the layers and ``range_edges`` their heights ABOVE THE LIMIT, ``arange(layers + 1) * range_bin`` (layer l: rows
+    ``[L - range_edges[l + 1], L - range_edges[l])`` of each ping, counted from its limit L, not from the surface)."""
     if all_reduce and parallel.rank_world()[1] > 1:
         torch.distributed.all_reduce(acc)
         torch.distributed.all_reduce(cnt)
+    return integration_result(acc.cpu().numpy(), cnt.cpu().numpy(), spec, n_pings, n_range)
+
+
+def integration_result(sv_sum, pixels, spec, n_pings, n_range):
+    """The result dict of ``finish_integration`` around downloaded accumulators (numpy ``[3, n_pb, n_rb]``)."""
     n_pb, n_rb = spec.bins(n_pings, n_range)
-    return {"sv_sum": acc.cpu().numpy(), "pixels": cnt.cpu().numpy(),
-            "ping_edges": np.minimum(np.arange(n_pb + 1, dtype=np.int64) * spec.ping_bin, int(n_pings)),
-            "range_edges": np.minimum(np.arange(n_rb + 1, dtype=np.int64) * spec.range_bin, int(n_range)),
-            "classes": INTEGRATION_CLASSES}
+    edges = np.arange(n_rb + 1, dtype=np.int64) * spec.range_bin
+    res = {"sv_sum": sv_sum, "pixels": pixels,
+           "ping_edges": np.minimum(np.arange(n_pb + 1, dtype=np.int64) * spec.ping_bin, int(n_pings)),
+           "range_edges": edges if spec.reference == "seabed" else np.minimum(edges, int(n_range)),
+           "classes": INTEGRATION_CLASSES}
+    if spec.seabed_aware:
+        res.update(reference=spec.reference, seabed_offset=spec.seabed_offset)
+    return res
 
 
 def integrate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, spec, start_ping=0,
@@ -1162,8 +1254,9 @@ def integrate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_
                             meta_channels=None, seabed=None):
     """``integrate_survey`` for ONE memmap echogram: ``predict_echogram_memm``'s prediction (same arguments, the float16
     values it would return) reduced on the GPU against the resident sv plane; same pixel rule, same return value; the
-    accumulators are not all-reduced (every rank that calls it returns the echogram's whole result).  The packed multi-echogram flow
-    (``predict_echograms_memm``) has no integrating counterpart yet: call this per echogram."""
+    accumulators are not all-reduced (every rank that calls it returns the echogram's whole result).  A seabed-aware
+    ``spec`` goes by the line the prediction used (``seabed``: None, an array or "estimate").  For a whole memm survey
+    ``integrate_echograms_memm`` is the integrating form of the packed flow (``predict_echograms_memm``)."""
     cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
                                      out_f16=True, wide=False, seabed=seabed)
     spec = spec.bind(segpipe.frequencies)
@@ -1485,6 +1578,27 @@ class _MemmSurveyFlow:
             self.stats["batches"].append(Pb)
             yield b0, Pb
 
+    def predict_group(self, g, predict_fn):
+        """The forward batches of staged group ``g``: gather, predict, scatter into the float16 predictions the group's
+        descriptors point at (``staged(out=...)``, zeroed by the caller)."""
+        eng, C, ph, pw = self.eng, self.C, self.ph, self.pw
+        for b0, Pb in self.batches(g.P):
+            x = eng._buf("tiled.x", (Pb * ph * pw, 16))
+            if self.pack and self.early:
+                call("crimac_gather_patches_memm_meta_multi", eng.prec, ptr(g.misc), ptr(g.meta), g.n, ptr(g.src, b0), C,
+                     ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16, None, 1, self.flags)
+            else:
+                call("crimac_gather_patches_memm_multi", eng.prec, ptr(g.misc), g.n, ptr(g.src, b0), C,
+                     ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16)
+            if predict_fn is not None:
+                probs = predict_fn(x, Pb, ph, pw)
+            elif eng.lmi:
+                probs = eng.forward_nhwc(x, Pb, ph, pw, False, softmax=True, meta=self.meta_planes(g, b0, Pb))
+            else:
+                probs = eng.forward_nhwc_eval_split(x, Pb, ph, pw, softmax=True)
+            call("crimac_scatter_patches_multi", ptr(probs), probs.shape[1], ptr(g.misc), g.n, ptr(g.src, b0),
+                 ptr(g.cen, 2 * b0), Pb, ph, pw, self.overlap, SEABED_PAD, 1)
+
     @contextlib.contextmanager
     def staged(self, tag, record=_MemmRecord, extra=None, out=None, tail=None):
         """Plans this rank's groups; inside ``with``: an iterator that stages them one by one and yields each as a
@@ -1554,7 +1668,7 @@ def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_
                            kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
                            group_patches, group_elems, stats, skip=skip, meta_channels=meta_channels,
                            pack_metadata=pack_metadata)
-    eng, C, ph, pw, cap = flow.eng, flow.C, flow.ph, flow.pw, flow.cap
+    cap = flow.cap
 
     def single(eg, sb, meta):            # the per-echogram path
         return eg, predict_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, predict_fn=predict_fn,
@@ -1588,28 +1702,104 @@ def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_
                 yield single(g.group[0].echogram, *flow.solo(g.group[0]))
                 continue
             out[:2 * g.total].zero_()
-            for b0, Pb in flow.batches(g.P):
-                x = eng._buf("tiled.x", (Pb * ph * pw, 16))
-                if flow.pack and flow.early:
-                    call("crimac_gather_patches_memm_meta_multi", eng.prec, ptr(g.misc), ptr(g.meta), g.n, ptr(g.src, b0), C,
-                         ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16, None, 1, flow.flags)
-                else:
-                    call("crimac_gather_patches_memm_multi", eng.prec, ptr(g.misc), g.n, ptr(g.src, b0), C,
-                         ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16)
-                if predict_fn is not None:
-                    probs = predict_fn(x, Pb, ph, pw)
-                elif eng.lmi:
-                    probs = eng.forward_nhwc(x, Pb, ph, pw, False, softmax=True, meta=flow.meta_planes(g, b0, Pb))
-                else:
-                    probs = eng.forward_nhwc_eval_split(x, Pb, ph, pw, softmax=True)
-                call("crimac_scatter_patches_multi", ptr(probs), probs.shape[1], ptr(g.misc), g.n, ptr(g.src, b0),
-                     ptr(g.cen, 2 * b0), Pb, ph, pw, flow.overlap, SEABED_PAD, 1)
+            flow.predict_group(g, predict_fn)
             flow.feed.computed()
             pinned[g.k & 1][:2 * g.total].copy_(out[:2 * g.total], non_blocking=True)
             events[g.k & 1].record()
             if pending is not None:
                 yield from take(*pending)
             pending = (g.group, g.offs, g.k & 1)
+        if pending is not None:
+            yield from take(*pending)
+
+
+def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, spec, predict_fn=None,
+                             meta_channels=None, seabed=None, group_patches=None, stats=None, group_elems=None, skip=None,
+                             pack_metadata=False, **kwargs):
+    """Echo integration by predicted class for a whole memm survey: ``predict_echograms_memm``'s packed feed with every
+    echogram's predictions reduced on the GPU instead of downloaded.  A generator of ``(echogram, result)`` in input
+    order, every result that of ``integrate_echogram_memm`` for the echogram: the same counts; the same sums bit for bit
+    when the echogram's place in the group's staging keeps the 16-byte alignment of its operands, otherwise the same
+    terms added in another fixed order (the kernel's narrow reads deal the pixels to the threads differently).  Each rank
+    yields the echograms of its own groups, no collective.
+
+    Groups, batches, ``seabed`` (None, ``"estimate"`` or a callable; a seabed-aware ``spec`` goes by the same line),
+    metadata models and ``pack_metadata``, ``skip``, ``stats`` and ``kwargs``: ``_MemmSurveyFlow``.  After a group's
+    scatters one integrate launch per echogram (``crimac_integrate_classes`` / ``crimac_integrate_layers`` by ``spec``)
+    reads the echogram's float16 predictions, its plane of the transposed staging and its seabed line inside the group's
+    uploaded ``misc``, and accumulates into the echogram's share of ONE flat fp64 / int64 buffer; the group's few
+    kilobytes leave through a ring of two pinned buffers with events, nothing in the feed blocks.  Metadata models
+    without ``pack_metadata`` and echograms larger than ``group_elems`` go through ``integrate_echogram_memm``, in their
+    place in the order."""
+    flow = _MemmSurveyFlow("integrate_echograms_memm",
+                           ("spec", "group_patches", "group_elems", "seabed", "skip", "stats", "predict_fn", "meta_channels",
+                            "pack_metadata"),
+                           kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
+                           group_patches, group_elems, stats, skip=skip, meta_channels=meta_channels,
+                           pack_metadata=pack_metadata)
+    spec = spec.bind(segpipe.frequencies)
+    C, W = flow.C, hip.MEMM_DESC_WORDS
+
+    def single(eg, sb, meta):            # the per-echogram path
+        return eg, integrate_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, spec, predict_fn=predict_fn,
+                                           meta_channels=meta, seabed=sb)
+
+    if flow.alone:
+        for eg, sb in flow.each_alone():
+            yield single(eg, sb, meta_channels)
+        return
+
+    def take(group, shares, total, host, event):            # the group whose accumulators went into ``host``
+        event.synchronize()
+        sums, counts = host[:total].numpy(), host[total:2 * total].view(torch.int64).numpy()
+        for r, (at, shape) in zip(group, shares):
+            n = 3 * shape[0] * shape[1]
+            yield r.echogram, integration_result(sums[at:at + n].reshape(3, *shape).copy(),
+                                                 counts[at:at + n].reshape(3, *shape).copy(), spec, r.n_pings, r.n_range)
+
+    with flow.staged("memm_integrate", extra=lambda: dict(out=torch.empty(2 * flow.cap, dtype=torch.float16, device=flow.dev)),
+                     out="out") as groups:
+        pending = None
+        words = 0                          # fp64 words of the accumulator buffers: [sums | counts] of the largest group so far
+        for g in groups:
+            if g.k == 0:                             # (there is a group: the staging exists)
+                out = flow.feed.bufs["out"]
+                events = [torch.cuda.Event() for _ in range(2)]
+                pinned = [None, None]
+            if g.offs is None:
+                if pending is not None:
+                    yield from take(*pending)
+                    pending = None
+                yield single(g.group[0].echogram, *flow.solo(g.group[0]))
+                continue
+            shares, total = [], 0                    # (first word, (n_pb, range bins or layers)) of every echogram
+            for r in g.group:
+                shape = spec.bins(r.n_pings, r.n_range)
+                shares.append((total, shape))
+                total += 3 * shape[0] * shape[1]
+            if 2 * total > words:
+                words = 2 * total
+                acc = torch.empty(words, dtype=torch.float64, device=flow.dev)
+            if pinned[g.k & 1] is None or pinned[g.k & 1].numel() < 2 * total:
+                pinned[g.k & 1] = torch.empty(words, dtype=torch.float64).pin_memory()
+            acc[:2 * total].zero_()                   # (all-zero bits: 0.0 and 0 alike)
+            out[:2 * g.total].zero_()
+            flow.predict_group(g, predict_fn)
+            scratch = integration_scratch(flow.eng, max(s[0] * s[1] for _, s in shares))
+            data_t = flow.feed.bufs["data_t"][g.k & 1]
+            o_sb = 2 * W * g.n + 3 * g.P              # the seabed lines inside ``misc``, one after the other
+            for r, off, (at, shape) in zip(g.group, g.offs, shares):
+                launch_integration(spec, ptr(out, 2 * off), True, r.n_range, r.n_pings,
+                                   ptr(data_t, C * off + spec.channel * r.pixels), r.n_pings, 0, 0, shape[0], ptr(acc, at),
+                                   ptr(acc, total + at), scratch, seabed=(ptr(g.misc, o_sb), 0, r.n_pings))
+                o_sb += r.n_pings
+            flow.feed.computed()
+            host = pinned[g.k & 1]
+            host[:2 * total].copy_(acc[:2 * total], non_blocking=True)
+            events[g.k & 1].record()
+            if pending is not None:
+                yield from take(*pending)
+            pending = (g.group, shares, total, host, events[g.k & 1])
         if pending is not None:
             yield from take(*pending)
 

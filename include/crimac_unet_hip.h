@@ -128,7 +128,9 @@ extern "C" {
 /* Library identity / error text.  crimac_version() returns CRIMAC_ABI_VERSION of the build: it is bumped whenever a
  * struct passed by pointer (crimac_layer_desc), the meaning of an argument, the set of precisions or the set of entry
  * points changes, and a binding must refuse a library whose version differs from the header it was written against (an
- * older build that happens to export every symbol would walk a descriptor array with the wrong stride).
+ * older build that happens to export every symbol would walk a descriptor array with the wrong stride).  An ADDITIVE
+ * entry point (crimac_integrate_layers) does not bump it: nothing an older caller uses has changed, and a binding that
+ * needs the new symbol refuses a build without it by looking the symbol up.
  * crimac_layer_desc_size() is sizeof(crimac_layer_desc) as the library was compiled. */
 #define CRIMAC_ABI_VERSION 17
 int crimac_version(void);
@@ -858,6 +860,26 @@ int crimac_integrate_classes(const void* pred, int pred_f16, int n_range, long n
                              long sv_ping_off, float thr_sandeel, float thr_other, int mode, long ping_bin, int range_bin,
                              long ping_origin, long n_pb_total, double* acc, long long* cnt, void* scratch,
                              long scratch_bytes, void* stream);
+
+/* The same reduction below a per-ping ROW LIMIT, and on layers counted from it (bottom channels).  The arguments of
+ * crimac_integrate_classes, the same pixel rule, sums, counts, ordering and reproducibility, plus:
+ *   seabed int32 [seabed_len]: a seabed row per ping; element seabed_first belongs to column 0 of pred (seabed_first >= 0,
+ *     seabed_first + n_pings <= seabed_len).  Ping p has the limit L[p] = clamp(seabed[p] + seabed_offset, 0, n_range);
+ *     rows r >= L[p] count in NO plane, neither sums nor pixels.  seabed_offset < 0 backs off above the detected bottom;
+ *     seabed_offset = +pad is the row rule of the memm scatter (crimac_scatter_patches_ex, seabed_rule 1).
+ *   reference 0 (surface): the cells of crimac_integrate_classes, every ping's rows cut at its limit; n_layers is not
+ *     read; acc / cnt [3][n_pb_total][n_rb].
+ *   reference 1 (seabed): column l = 0 .. n_layers - 1 of the accumulators is LAYER l, rows [L[p] - (l + 1) * range_bin,
+ *     L[p] - l * range_bin) of ping p clipped to [0, n_range) -- counted from the limit, not from the surface: layer 0
+ *     touches it, and rows above layer n_layers - 1 belong to no layer.  n_layers >= 1; acc / cnt [3][n_pb_total][n_layers].
+ *   scratch: as above with cells = (ping bins touched) * (n_rb or n_layers); (cells + CRIMAC_INTEGRATE_SPLIT_WGS) *
+ *     CRIMAC_INTEGRATE_SLOT_BYTES always suffices.  The number of workgroups and the slot layout depend on the shapes, never
+ *     on the seabed values. */
+int crimac_integrate_layers(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv, long data_pings,
+                            long sv_ping_off, float thr_sandeel, float thr_other, int mode, long ping_bin, int range_bin,
+                            long ping_origin, long n_pb_total, const int* seabed, long seabed_first, long seabed_len,
+                            int seabed_offset, int reference, int n_layers, double* acc, long long* cnt, void* scratch,
+                            long scratch_bytes, void* stream);
 
 /* ---- measurement support (bench.py only, not on the product path) --------------------------- */
 

@@ -11,7 +11,16 @@ and model:
 Survey: synth.SyntheticSurveyReader (sv [4, pings, 1024] fp32, flat seabed 900, NaN / inf samples), patch 256, overlap 20,
 h3p inference.  The legs alternate in one process (A0, A, B per round) after one warm-up each; the figure of a leg is the
 median of its rounds.  Leg B is checked against leg A: counts equal, every sum within (n_cell_pixels + 2) * 2^-52 relative
-(tests/test_gpu_integrate.py).  The last line is one JSON object; --out writes it to a file as well."""
+(tests/test_gpu_integrate.py).  The last line is one JSON object; --out writes it to a file as well.
+
+--layers N (> 0) adds the seabed-reference legs to every round, same survey, same protocol:
+
+  L  layers      -- integrate_survey with IntegrationSpec(seabed_offset=--seabed-offset, reference="seabed", layers=N):
+                    crimac_integrate_layers; its yardstick is leg B of the same run (the default spec);
+  LH host_layers -- predict_survey float16 followed by the numpy bottom-layer integration of every downloaded chunk.
+
+Leg L is checked against leg LH with the same bound, and the JSON line gains layers_over_device (B / L) and
+layers_over_host (LH / L)."""
 import argparse
 import json
 import os
@@ -52,6 +61,32 @@ def host_chunk(acc, cnt, geo, out, sv, spec, s):
     geo[cells] += binned(np.ones((R, P), dtype=np.int64))
 
 
+def host_chunk_layers(acc, cnt, geo, out, sv, line, spec, s):
+    """``host_chunk`` for a seabed-reference ``spec``: ``line`` [e - s] the reader's seabed rows; layer l of ping p covers
+    rows [L - (l + 1) * range_bin, L - l * range_bin) below the limit L = clip(line + seabed_offset, 0, R)."""
+    R, P = out.shape[1:]
+    sv_t = np.ascontiguousarray(sv.T)
+    L = np.clip(np.asarray(line).astype(np.int64) + spec.seabed_offset, 0, R)
+    r = np.arange(R)[:, None]
+    layer = (L[None, :] - 1 - r) // spec.range_bin
+    inside = (r < L[None, :]) & (layer < spec.layers)
+    ok = np.isfinite(sv_t) & (sv_t > 0) & inside
+    s64 = np.where(ok, sv_t, 0).astype(np.float64)
+    p32 = out.astype(np.float32)
+    if spec.mode == "threshold":
+        member = p32 >= np.asarray(spec.thresholds, dtype=np.float32)[:, None, None]
+        weight = member.astype(np.float64)
+    else:
+        member = p32 > 0
+        weight = np.where(member, p32, 0).astype(np.float64)
+    n = acc[0].size
+    at = np.where(inside, ((s + np.arange(P)) // spec.ping_bin)[None, :] * spec.layers + layer, 0)
+    for k, (terms, counted) in enumerate(((s64 * weight[0], ok & member[0]), (s64 * weight[1], ok & member[1]), (s64, ok))):
+        acc[k] += np.bincount(at[counted], weights=terms[counted], minlength=n).reshape(acc[k].shape)
+        cnt[k] += np.bincount(at[counted], minlength=n).reshape(acc[k].shape)
+    geo += np.bincount(at[inside], minlength=n).reshape(geo.shape)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pings", type=int, default=16384)
@@ -63,6 +98,8 @@ def main():
     ap.add_argument("--range-bin", type=int, default=50)
     ap.add_argument("--mode", default="threshold")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--layers", type=int, default=0, help="> 0: add the seabed-reference legs with this many layers")
+    ap.add_argument("--seabed-offset", type=int, default=-5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     reader = synth.SyntheticSurveyReader(n_pings=a.pings, n_range=a.range, seabed_index=900, block=4096, schools=40,
@@ -95,6 +132,21 @@ def main():
         return ti.integrate_survey(reader, pipe, patch, overlap, a.batch, a.preload, spec)
 
     legs = {"predict": leg_predict, "host": leg_host, "device": leg_device}
+    if a.layers > 0:
+        lspec = ti.IntegrationSpec(a.ping_bin, a.range_bin, mode=a.mode, seabed_offset=a.seabed_offset, reference="seabed",
+                                   layers=a.layers)
+
+        def leg_layers():
+            return ti.integrate_survey(reader, pipe, patch, overlap, a.batch, a.preload, lspec)
+
+        def leg_host_layers():
+            acc, cnt = np.zeros((3, n_pb, a.layers)), np.zeros((3, n_pb, a.layers), dtype=np.int64)
+            geo = np.zeros((n_pb, a.layers), dtype=np.int64)
+            for s, e, out in ti.predict_survey(reader, pipe, patch, overlap, a.batch, a.preload, out_dtype=np.float16):
+                sv = reader.get_data_slice(idx_ping=s, n_pings=e - s, frequencies=pipe.frequencies)[channel]
+                host_chunk_layers(acc, cnt, geo, out, sv, reader.get_seabed(s, e - s, return_numpy=True), lspec, s)
+            return acc, cnt, geo
+        legs.update(layers=leg_layers, host_layers=leg_host_layers)
     times, last = {k: [] for k in legs}, {}
     for rnd in range(-1, a.rounds):                                       # round -1: warm-up (staging, packed weights)
         for name, fn in legs.items():
@@ -121,6 +173,16 @@ def main():
         "largest_error_over_bound": float((err[acc > 0] / bound[acc > 0]).max()),
         "classified_pixels": [int(cnt[0].sum()), int(cnt[1].sum()), int(cnt[2].sum())],
     }
+    if a.layers > 0:
+        lacc, lcnt, lgeo = last["host_layers"]
+        lgot = last["layers"]
+        lerr, lbound = np.abs(lgot["sv_sum"] - lacc), (lgeo[None] + 2) * 2.0 ** -52 * lacc
+        counts_equal = counts_equal and bool(np.array_equal(lgot["pixels"], lcnt))
+        within = within and bool((lerr <= lbound).all() and (lgot["sv_sum"][lacc == 0] == 0).all())
+        line.update(layers=a.layers, seabed_offset=a.seabed_offset, counts_equal=counts_equal, sums_within_bound=within,
+                    layers_over_device=round(med["device"] / med["layers"], 4),
+                    layers_over_host=round(med["host_layers"] / med["layers"], 4),
+                    layer_pixels=[int(lcnt[0].sum()), int(lcnt[1].sum()), int(lcnt[2].sum())])
     for k in legs:
         print(f"{k:8s}: {patches} patches, median {med[k]:.3f} s -> {patches / med[k]:.0f} patches/s", flush=True)
     text = json.dumps(line)
