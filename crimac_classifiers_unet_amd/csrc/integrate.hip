@@ -26,7 +26,11 @@
 // LDS (written once per tile, read into registers by the four pings a thread consumes).  With relief above range_bin the
 // boxes of neighbouring layers overlap and those tiles are read once per layer.  S is bounded by the tiles of the whole
 // column, whatever the seabed values: a workgroup whose split finds no tile writes a zero slot.
+//
+// crimac_integrate_confusion (further down, its own two kernels): the sums of an EVALUATION batch -- logits, raw crops and
+// transformed labels in patch layout -- split by the annotated class as well.
 #include "common.h"
+#include "pr_softmax.h"
 
 namespace {
 
@@ -382,7 +386,206 @@ int integrate(const char* who, const SeabedArgs* sb, const void* pred, int pred_
   return CRIMAC_OK;
 }
 
+// ---- crimac_integrate_confusion: the same sums split by the ANNOTATED class, from an evaluation batch --------------------
+// All five operands of a pixel -- sv, the transformed label, three logits -- lie in patch layout [ph][pw], ping
+// contiguous, so nothing is transposed and no LDS tile is needed: a workgroup owns (patch, i, j), the (i, j)-th cell of the
+// (ncp x ncr) window of cells the patch can overlap, counted from the cell that holds its pixel (0, 0).  It walks the
+// rectangle patch x cell x grid row by row with consecutive lanes on consecutive pings (4-byte loads, coalesced up to
+// the row ends of the rectangle); the logits are read only for the pixels that count.  Thread -> lanes (butterfly) -> waves
+// (in order, by thread 0) -> the (patch, i, j) slot of the scratch, as above.  A window cell outside the accumulator grid
+// gets no workgroup work and no slot write: nothing is read for its pixels.
+// Finish: one thread per slot.  The thread of the FIRST patch of the batch whose window holds the slot's cell owns that
+// cell: it adds the cell's slots in patch order and does the plain read-add-write of its 18 outputs; the others leave.
+// Who owns what depends on the origins alone, so the order of every sum is a function of the arguments.
+struct CSlot { Slot a[3]; };                                 // per annotated class: background, sandeel, other
+static_assert(sizeof(CSlot) == CRIMAC_CONFUSION_SLOT_BYTES, "scratch slot size is part of the ABI");
+constexpr int kConfusionMaxPatches = CRIMAC_CONFUSION_MAX_PATCHES;
+
+struct CGeom {
+  int P, C, channel, ph, pw, n_range, range_bin, n_rb, ncp, ncr, mode;
+  long ping_bin, n_pb_total;
+  float thr0, thr1;
+};
+
+__device__ __forceinline__ long floor_div(long a, long b) {      // b > 0
+  const long q = a / b;
+  return q - (a % b != 0 && a < 0);
+}
+
+__global__ __launch_bounds__(kThreads) void confusion_cells_kernel(const float* __restrict__ logits,
+                                                                   const float* __restrict__ raw,
+                                                                   const short* __restrict__ labels,
+                                                                   const int* __restrict__ origins, CGeom g,
+                                                                   CSlot* __restrict__ scratch) {
+  __shared__ CSlot wave_part[kThreads / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int i = blockIdx.x % g.ncp, j = blockIdx.x / g.ncp % g.ncr, p = blockIdx.x / (g.ncp * g.ncr);
+  const long y0 = origins[2 * p], x0 = origins[2 * p + 1];
+  const long pb = floor_div(x0, g.ping_bin) + i, rb = floor_div(y0, g.range_bin) + j;
+  if (pb < 0 || pb >= g.n_pb_total || rb < 0 || rb >= g.n_rb) return;     // (uniform: nobody waits at the barrier)
+  // the cell in patch coordinates, clipped to the patch and to rows below n_range (its pings lie inside the grid)
+  long c0 = pb * g.ping_bin - x0, c1 = c0 + g.ping_bin, r0 = rb * g.range_bin - y0, r1 = r0 + g.range_bin;
+  c0 = c0 > 0 ? c0 : 0;
+  r0 = r0 > 0 ? r0 : 0;
+  c1 = c1 < g.pw ? c1 : g.pw;
+  r1 = r1 < g.ph ? r1 : g.ph;
+  r1 = r1 < g.n_range - y0 ? r1 : g.n_range - y0;
+  const int w = c1 > c0 ? (int)(c1 - c0) : 0, h = r1 > r0 ? (int)(r1 - r0) : 0;
+  const int n = w * h;                                       // (<= ph * pw < 2^31)
+  const long HW = (long)g.ph * g.pw;
+  const short* __restrict__ lab_p = labels + p * HW;
+  const float* __restrict__ sv_p = raw + ((long)p * g.C + g.channel) * HW;
+  const float* __restrict__ logit_p = logits + (long)p * 3 * HW;
+  double s[3][3] = {};
+  int m[3][3] = {};                                          // (a thread sees n / 256 + 1 pixels at most)
+  for (int k = t; k < n; k += kThreads) {
+    const long at = (r0 + k / w) * g.pw + c0 + k % w;
+    const int l = lab_p[at];
+    const float sv = sv_p[at];
+    // finite and > 0; the largest finite float is what the zarr crop's nan_to_num made of +Inf, so it is not finite here
+    if (l < 0 || l > 2 || !(sv > 0.f && sv < 3.402823466e+38f)) continue;
+    float z[8], den;
+    pr_softmax_terms(logit_p + at, HW, 3, z, den);
+    const float a = (float)pr_prob_f16(z[1], den), b = (float)pr_prob_f16(z[2], den);
+    const double sd = (double)sv;
+    bool in0, in1;
+    double v0, v1;
+    if (g.mode == 0) {
+      in0 = a >= g.thr0, in1 = b >= g.thr1;
+      v0 = in0 ? sd : 0.0, v1 = in1 ? sd : 0.0;
+    } else {
+      in0 = a > 0.f, in1 = b > 0.f;                          // (a NaN or negative weight counts as 0)
+      v0 = in0 ? sd * (double)a : 0.0, v1 = in1 ? sd * (double)b : 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const bool is = l == c;
+      s[c][0] += is ? v0 : 0.0;
+      s[c][1] += is ? v1 : 0.0;
+      s[c][2] += is ? sd : 0.0;
+      m[c][0] += is && in0;
+      m[c][1] += is && in1;
+      m[c][2] += is;
+    }
+  }
+  // ---- lane -> wave -> workgroup, each in a fixed order
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      s[c][k] = wave_sum_d(s[c][k]);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) m[c][k] += __shfl_xor(m[c][k], o, 64);
+    }
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      wave_part[wave].a[c] = Slot{{s[c][0], s[c][1], s[c][2]}, {m[c][0], m[c][1], m[c][2]}};
+  }
+  __syncthreads();
+  if (t == 0) {
+    CSlot out = wave_part[0];
+    for (int wv = 1; wv < kThreads / 64; ++wv)
+      for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 3; ++k) {
+          out.a[c].sum[k] += wave_part[wv].a[c].sum[k];
+          out.a[c].cnt[k] += wave_part[wv].a[c].cnt[k];
+        }
+    scratch[blockIdx.x] = out;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void confusion_finish_kernel(const CSlot* __restrict__ scratch,
+                                                                    const int* __restrict__ origins, CGeom g,
+                                                                    double* __restrict__ acc, long long* __restrict__ cnt) {
+  // the first cell of every patch's window, once per workgroup
+  __shared__ long pb0[kConfusionMaxPatches];
+  __shared__ int rb0[kConfusionMaxPatches];
+  for (int q = threadIdx.x; q < g.P; q += kThreads) {
+    rb0[q] = (int)floor_div(origins[2 * q], g.range_bin);
+    pb0[q] = floor_div(origins[2 * q + 1], g.ping_bin);
+  }
+  __syncthreads();
+  const long slot = (long)blockIdx.x * kThreads + threadIdx.x;
+  const int per_patch = g.ncp * g.ncr;
+  if (slot >= (long)g.P * per_patch) return;
+  const int p = (int)(slot / per_patch), i = (int)(slot % g.ncp), j = (int)(slot / g.ncp % g.ncr);
+  const long pb = pb0[p] + i, rb = (long)rb0[p] + j;
+  if (pb < 0 || pb >= g.n_pb_total || rb < 0 || rb >= g.n_rb) return;      // (no workgroup wrote this slot)
+  for (int q = 0; q < p; ++q) {                                            // an earlier patch owns the cell
+    const long qi = pb - pb0[q], qj = rb - rb0[q];
+    if (qi >= 0 && qi < g.ncp && qj >= 0 && qj < g.ncr) return;
+  }
+  CSlot out = scratch[slot];
+  for (int q = p + 1; q < g.P; ++q) {
+    const long qi = pb - pb0[q], qj = rb - rb0[q];
+    if (qi < 0 || qi >= g.ncp || qj < 0 || qj >= g.ncr) continue;
+    const CSlot& x = scratch[((long)q * g.ncr + qj) * g.ncp + qi];
+    for (int c = 0; c < 3; ++c)
+      for (int k = 0; k < 3; ++k) {
+        out.a[c].sum[k] += x.a[c].sum[k];
+        out.a[c].cnt[k] += x.a[c].cnt[k];
+      }
+  }
+  for (int c = 0; c < 3; ++c)
+    for (int k = 0; k < 3; ++k) {
+      const long at = (((long)c * 3 + k) * g.n_pb_total + pb) * g.n_rb + rb;
+      acc[at] += out.a[c].sum[k];
+      cnt[at] += out.a[c].cnt[k];
+    }
+}
+
 }  // namespace
+
+extern "C" int crimac_integrate_confusion(const float* logits, int ncls, const float* raw, int C, int channel,
+                                          const short* labels, const int* origins, int P, int ph, int pw, int n_range,
+                                          long ping_bin, int range_bin, long n_pb_total, float thr_sandeel, float thr_other,
+                                          int mode, double* acc, long long* cnt, void* scratch, long scratch_bytes,
+                                          void* stream) {
+  const char* who = "integrate_confusion";
+  CRIMAC_REQUIRE(logits && raw && labels && origins && acc && cnt && scratch, "%s: null pointer", who);
+  CRIMAC_REQUIRE(ncls == 3, "%s: ncls=%d: the planes are those of a 3-class model (background, sandeel, other)", who, ncls);
+  CRIMAC_REQUIRE(P > 0 && P <= kConfusionMaxPatches, "%s: P=%d patches (1 .. CRIMAC_CONFUSION_MAX_PATCHES = %d per launch)",
+                 who, P, kConfusionMaxPatches);
+  CRIMAC_REQUIRE(ph > 0 && pw > 0 && ph <= 32768 && pw <= 32768, "%s: patch %d x %d (1 .. 32768 each)", who, ph, pw);
+  CRIMAC_REQUIRE(C > 0 && channel >= 0 && channel < C, "%s: channel %d of %d sv planes", who, channel, C);
+  CRIMAC_REQUIRE(n_range > 0, "%s: n_range=%d", who, n_range);
+  CRIMAC_REQUIRE(mode == 0 || mode == 1, "%s: mode %d (0 threshold, 1 probability)", who, mode);
+  CRIMAC_REQUIRE(thr_sandeel > 0.f && thr_other > 0.f, "%s: thr = (%g, %g) must be > 0", who, (double)thr_sandeel,
+                 (double)thr_other);
+  CRIMAC_REQUIRE(ping_bin > 0 && range_bin > 0, "%s: ping_bin=%ld, range_bin=%d must be positive", who, ping_bin, range_bin);
+  CRIMAC_REQUIRE(ping_bin <= 2147483647L && n_pb_total > 0 && n_pb_total <= 2147483647L, "%s: ping_bin=%ld, n_pb_total=%ld "
+                 "outside 1 .. 2^31 - 1", who, ping_bin, n_pb_total);
+  CGeom g;
+  g.P = P;
+  g.C = C;
+  g.channel = channel;
+  g.ph = ph;
+  g.pw = pw;
+  g.n_range = n_range;
+  g.range_bin = range_bin;
+  g.n_rb = (n_range + range_bin - 1) / range_bin;
+  g.ncp = (int)((pw + ping_bin - 1) / ping_bin) + 1;
+  g.ncr = (ph + range_bin - 1) / range_bin + 1;
+  g.mode = mode;
+  g.ping_bin = ping_bin;
+  g.n_pb_total = n_pb_total;
+  g.thr0 = thr_sandeel;
+  g.thr1 = thr_other;
+  const long slots = (long)P * g.ncp * g.ncr;
+  CRIMAC_REQUIRE(slots <= 2147483647L, "%s: %ld (patch, cell) slots in one launch", who, slots);
+  CRIMAC_REQUIRE(scratch_bytes >= slots * (long)sizeof(CSlot) && (uintptr_t)scratch % 8 == 0,
+                 "%s: scratch of %ld bytes, this launch needs %ld (8-byte aligned; P * (ceil(pw / ping_bin) + 1) * "
+                 "(ceil(ph / range_bin) + 1) * CRIMAC_CONFUSION_SLOT_BYTES)", who, scratch_bytes, slots * (long)sizeof(CSlot));
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(confusion_cells_kernel, dim3((unsigned)slots), dim3(kThreads), 0, st, logits, raw, labels, origins, g,
+                     (CSlot*)scratch);
+  CRIMAC_LAUNCH_CHECK();
+  hipLaunchKernelGGL(confusion_finish_kernel, dim3((unsigned)((slots + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                     (const CSlot*)scratch, origins, g, acc, cnt);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}
 
 extern "C" int crimac_integrate_classes(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv,
                                         long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode,

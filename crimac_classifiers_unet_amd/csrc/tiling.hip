@@ -17,6 +17,7 @@
 // bf16/fp32 conversion are fused into it -- the patch lands directly in the first conv's input layout.
 #include "common.h"
 #include "meta_planes.h"
+#include "pr_softmax.h"
 
 namespace {
 
@@ -298,19 +299,12 @@ __global__ __launch_bounds__(256) void pr_histogram_classes_kernel(const float* 
     float z[8], den = 0.f;
     if (!seabed) {
       const long b = p / HW, hw = p % HW;
-      float mx = -INFINITY;
-#pragma unroll
-      for (int o = 0; o < 8; ++o)
-        if (o < ncls) { z[o] = logits[(b * ncls + o) * HW + hw]; mx = fmaxf(mx, z[o]); }
-#pragma unroll
-      for (int o = 0; o < 8; ++o)
-        if (o < ncls) { z[o] = expf(z[o] - mx); den += z[o]; }
+      pr_softmax_terms(logits + b * ncls * HW + hw, HW, ncls, z, den);
     }
 #pragma unroll
     for (int c = 1; c < 8; ++c) {
       if (!((mask >> c) & 1u)) continue;       // (uniform; the entry point admits bits 1 .. ncls-1 only)
-      const float prob = seabed ? 0.f : z[c] / den;
-      const _Float16 h = (_Float16)prob;
+      const _Float16 h = seabed ? (_Float16)0.f : pr_prob_f16(z[c], den);
       unsigned short bits = *reinterpret_cast<const unsigned short*>(&h);
       if (bits > 0x3C00) bits = CRIMAC_PR_NAN_BIN;
       const int side = (!seabed && l == c) ? 0 : 1;
@@ -347,6 +341,25 @@ __global__ __launch_bounds__(256) void pr_histogram_classes_kernel(const float* 
 // reading, along ping (contiguous in the crop) when writing; `vec`: 16-byte stores (pw % 8 == 0, 16-byte aligned bases).
 // One block = one 32 x 32 tile of patch blockIdx.z.  With a descriptor table (flavour 1 only) the centre-row rule of a
 // water column not deeper than the patch is the patch's own echogram's; a descriptor without data or labels is skipped.
+//
+// eval_crop_origin: the placement rule itself -- the (row, ping) of crop pixel (0, 0) in the coordinates of the centre --
+// which crimac_eval_crop_origins hands to whoever must know where a crop's pixels lie (crimac_integrate_confusion).
+__device__ __forceinline__ void eval_crop_origin(int cy, int cx, int ph, int pw, int H, int flavour, int& y0, int& x0) {
+  if (flavour == 1 && H <= ph) cy = H / 2;                  // dataset.py:259-261
+  y0 = cy - (flavour == 1 ? (ph + 1) / 2 : ph / 2) + 1;
+  x0 = cx - (flavour == 1 ? (pw + 1) / 2 : pw / 2) + 1;
+}
+
+__global__ __launch_bounds__(256) void eval_crop_origins_kernel(const int* __restrict__ centres, int P, int ph, int pw, int H,
+                                                                int flavour, int* __restrict__ origins) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  int y0, x0;
+  eval_crop_origin(centres[2 * p], centres[2 * p + 1], ph, pw, H, flavour, y0, x0);
+  origins[2 * p] = y0;
+  origins[2 * p + 1] = x0;
+}
+
 __global__ __launch_bounds__(256) void gather_eval_crops_kernel(PatchSrc s, int C, const int* __restrict__ centres, int ph,
                                                                 int pw, int flavour, int vec, float* __restrict__ data_out,
                                                                 short* __restrict__ labels_out) {
@@ -358,11 +371,10 @@ __global__ __launch_bounds__(256) void gather_eval_crops_kernel(PatchSrc s, int 
   __shared__ short ltile[TS][TS + 2];
   const int p = blockIdx.z;
   const int ty0 = blockIdx.y * TS, tx0 = blockIdx.x * TS;
-  int cy = centres[2 * p];
-  const int cx = centres[2 * p + 1];
-  if (flavour == 1 && H <= ph) cy = H / 2;                  // dataset.py:259-261
-  const int y_base = cy - (flavour == 1 ? (ph + 1) / 2 : ph / 2) + 1 + ty0;
-  const int x_base = cx - (flavour == 1 ? (pw + 1) / 2 : pw / 2) + 1 + tx0;
+  int y_base, x_base;
+  eval_crop_origin(centres[2 * p], centres[2 * p + 1], ph, pw, H, flavour, y_base, x_base);
+  y_base += ty0;
+  x_base += tx0;
   const int tx = threadIdx.x & 31, tr = threadIdx.x >> 5;   // read phase: tx along range, tr + 8k along ping
   const int y = y_base + tx;
   // labels
@@ -451,6 +463,16 @@ extern "C" int crimac_gather_eval_crops_multi(const crimac_memm_desc* descs, int
   CRIMAC_REQUIRE(descs, "gather_eval_crops_multi: needs the descriptor table");
   return eval_crops_run("gather_eval_crops_multi", PatchSrc{nullptr, 0, 0, nullptr, descs, n_desc, src}, C, centres, P,
                         ph, pw, 1, data_out, labels_out, stream);
+}
+
+extern "C" int crimac_eval_crop_origins(const int* centres, int P, int ph, int pw, int H, int flavour, int* origins,
+                                        void* stream) {
+  CRIMAC_REQUIRE(centres && origins && P > 0 && ph > 0 && pw > 0 && H > 0, "eval_crop_origins: bad arguments");
+  CRIMAC_REQUIRE(flavour == 0 || flavour == 1, "eval_crop_origins: flavour=%d (0 zarr, 1 memm)", flavour);
+  hipLaunchKernelGGL(eval_crop_origins_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     centres, P, ph, pw, H, flavour, origins);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
 }
 
 extern "C" int crimac_pr_histogram(const float* logits, int ncls, const void* labels, int label_bytes,

@@ -333,7 +333,8 @@ class ChunkPredictor:
                  ptr(x), 16)
         return x
 
-    def evaluate(self, grid, hist, eval_mode="all", boxes=None, predict_fn=None, on_batch=None, classes=None):
+    def evaluate(self, grid, hist, eval_mode="all", boxes=None, predict_fn=None, on_batch=None, classes=None,
+                 integration=None):
         """Test-set evaluation of the patches of ``grid`` ([P, 2] global centres) on a ``wide`` chunk: what the reference's
         gridded test Dataset + ``get_predictions_dataloader`` + the masking of ``validate_model_testing`` do per patch
         (batch/dataset.py:207-242; pipeline.py:242-282, :347-353), accumulated into ``hist`` (int32 [2, 16384] on the GPU:
@@ -355,8 +356,17 @@ class ChunkPredictor:
         GPU (tests).
         ``classes`` (a tuple of foreground class indices, ``check_classes``): ``hist`` is int32 [n_classes, 2, 16384] and
         row c takes the float16 probability of class c, by label == c / the rest, for every c of ``classes`` in one
-        ``crimac_pr_histogram_classes`` pass per batch; a below-seabed pixel counts in ``neg`` of each with probability 0."""
+        ``crimac_pr_histogram_classes`` pass per batch; a below-seabed pixel counts in ``neg`` of each with probability 0.
+        ``integration`` (a ``ScoredIntegration`` that has begun): every batch is also reduced by
+        ``crimac_integrate_confusion``, right after its histograms and on the same stream, from the raw crops, the
+        transformed labels and the logits it has on the GPU anyway; None: no launch, no buffer."""
         classes = model_classes(classes, self.engine, hist)
+        if integration is not None:
+            if not isinstance(integration, ScoredIntegration):
+                raise TypeError(f"integration is a ScoredIntegration, got {type(integration).__name__}")
+            if self.engine.n_classes != 3:
+                raise ValueError(f"integration=: the model has n_classes={self.engine.n_classes}, the scored integration "
+                                 "is that of a 3-class model")
         if not self.wide:
             raise ValueError("ChunkPredictor.evaluate needs a chunk loaded with wide=True (labels and seabed for every "
                              "ping a patch can touch)")
@@ -405,6 +415,8 @@ class ChunkPredictor:
             if on_batch is not None:
                 on_batch(cen, labels_t, logits)
             add_pr_histograms(logits, labels_t, hist, classes)
+            if integration is not None:
+                integration.add_batch(eng, logits, raw, labels_t, cen_d, self.n_range, memm)
         return hist
 
 
@@ -1074,6 +1086,139 @@ def nasc(result, range_step_m):
     sv_sum`` (m^2 nmi^-2 summed over the cell's pings; divide by the pings of a cell, ``np.diff(result["ping_edges"])``,
     for the cell's mean NASC).  Assumes a UNIFORM range grid: every sample is ``range_step_m`` metres thick."""
     return 4.0 * np.pi * 1852.0 ** 2 * float(range_step_m) * np.asarray(result["sv_sum"], dtype=np.float64)
+
+
+# ---- echo integration scored against the annotations (the evaluation flows) --------------------------------------------
+ANNOTATED_CLASSES = ("background", "sandeel", "other")
+CONFUSION_SLOT_BYTES, CONFUSION_MAX_PATCHES = hip.DEFINES["CRIMAC_CONFUSION_SLOT_BYTES"], hip.DEFINES["CRIMAC_CONFUSION_MAX_PATCHES"]
+
+
+def confusion_scratch_bytes(P, ph, pw, ping_bin, range_bin):
+    """The scratch of one ``crimac_integrate_confusion`` launch, as the header states it: one slot per patch and cell of
+    the window of cells a patch can overlap."""
+    return P * (-(-pw // ping_bin) + 1) * (-(-ph // range_bin) + 1) * CONFUSION_SLOT_BYTES
+
+
+class ScoredIntegration:
+    """Echo integration scored against the annotations: hand one to ``evaluate_survey`` / ``evaluate_echogram_memm`` /
+    ``ChunkPredictor.evaluate`` as ``integration=`` and every evaluation batch is reduced on the GPU
+    (``crimac_integrate_confusion``), while its raw crops, transformed labels and logits are resident, to the linear sv of
+    ``spec.frequency`` per ANNOTATED class, predicted class and cell.  ``spec``: an ``IntegrationSpec`` (cells, frequency,
+    ``mode``, ``thresholds``); the flow binds it to the model's frequencies (``begin``) and the holder owns the device
+    accumulators.  A pixel counts when its transformed label is 0, 1 or 2 -- the pixels the PR histograms see, minus those
+    below the seabed -- and its sv is finite and > 0; its class weights come from the float16 softmax probabilities the
+    histograms bin, so a threshold read off the PR curve selects the same pixels here.
+
+    A seabed-aware spec (``seabed_offset`` / ``reference="seabed"``) is refused: the labels already exclude the pixels
+    below the seabed, and bottom layers are not scored."""
+
+    def __init__(self, spec):
+        if not isinstance(spec, IntegrationSpec):
+            raise TypeError(f"ScoredIntegration: spec is an IntegrationSpec, got {type(spec).__name__}")
+        if spec.seabed_aware or spec.reference != "surface":
+            raise NotImplementedError("ScoredIntegration: a seabed-aware spec (seabed_offset / reference='seabed') is not "
+                                      "scored: the transformed labels already exclude the pixels below the seabed")
+        self.spec = spec
+        self.acc = self.cnt = None
+        self.n_pings = self.n_range = None
+
+    def begin(self, frequencies, n_classes, dev, n_pings, n_range):
+        """What a flow does first: bind the spec to the model's ``frequencies``, check the model (3 classes) and allocate
+        the zeroed accumulators, float64 / int64 ``[3, 3, n_pb, n_rb]`` on ``dev``, for a survey of ``n_pings`` x
+        ``n_range``.  A holder that has begun keeps accumulating when the extent is the same one and raises otherwise."""
+        if int(n_classes) != 3:
+            raise ValueError(f"ScoredIntegration: the model has n_classes={n_classes}; the planes (sandeel, other, all) and "
+                             "the annotated classes (background, sandeel, other) are those of a 3-class model")
+        spec = self.spec.bind(frequencies)
+        extent = (int(n_pings), int(n_range))
+        if self.acc is not None:
+            if (self.n_pings, self.n_range) != extent or spec.channel != self.spec.channel:
+                raise ValueError(f"ScoredIntegration: begun for {self.n_pings} pings x {self.n_range} rows (channel "
+                                 f"{self.spec.channel}), now asked for {extent[0]} x {extent[1]} (channel {spec.channel}): "
+                                 "one holder per survey")
+            return self
+        self.spec = spec
+        self.n_pings, self.n_range = extent
+        shape = (3, 3, *spec.bins(*extent))
+        self.acc = torch.zeros(shape, dtype=torch.float64, device=dev)
+        self.cnt = torch.zeros(shape, dtype=torch.int64, device=dev)
+        return self
+
+    def add_batch(self, engine, logits, raw, labels_t, centres, n_range, memm):
+        """One evaluation batch: ``logits`` fp32 [P, 3, ph, pw], ``raw`` fp32 [P, C, ph, pw] linear sv, ``labels_t`` int16
+        [P, ph, pw] transformed labels, ``centres`` int32 [P, 2] GLOBAL centres, all on the GPU; ``n_range`` / ``memm``:
+        the water column and the crop flavour of the gather that cut ``raw``, whose placement ``crimac_eval_crop_origins``
+        restates.  Launches on the current stream; nothing comes back."""
+        if self.acc is None:
+            raise ValueError("ScoredIntegration: begin() first (the evaluation flows do)")
+        P, ncls, ph, pw = logits.shape
+        C = raw.shape[1]
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or tuple(raw.shape) != (P, C, ph, pw) \
+                or tuple(labels_t.shape) != (P, ph, pw) or labels_t.dtype != torch.int16 or not labels_t.is_contiguous():
+            raise ValueError(f"ScoredIntegration: logits {logits.dtype} {tuple(logits.shape)}, raw {tuple(raw.shape)}, labels "
+                             f"{labels_t.dtype} {tuple(labels_t.shape)}: contiguous fp32 [P, 3, H, W], fp32 [P, C, H, W], "
+                             "int16 [P, H, W]")
+        if not 0 <= self.spec.channel < C:
+            raise ValueError(f"ScoredIntegration: channel {self.spec.channel} of {C} data planes")
+        spec = self.spec
+        centres = centres.contiguous()
+        with torch.cuda.device(logits.device):
+            for b0 in range(0, P, CONFUSION_MAX_PATCHES):
+                n = min(CONFUSION_MAX_PATCHES, P - b0)
+                origins = engine._buf("confusion.origins", (n, 2), torch.int32)
+                scratch = engine._buf("confusion.scratch",
+                                      (confusion_scratch_bytes(n, ph, pw, spec.ping_bin, spec.range_bin) // 8,), torch.float64)
+                call("crimac_eval_crop_origins", ptr(centres[b0:b0 + n]), n, ph, pw, n_range, 1 if memm else 0, ptr(origins))
+                call("crimac_integrate_confusion", ptr(logits[b0:b0 + n]), ncls, ptr(raw[b0:b0 + n]), C, spec.channel,
+                     ptr(labels_t[b0:b0 + n]), ptr(origins), n, ph, pw, self.n_range, spec.ping_bin, spec.range_bin,
+                     int(self.acc.shape[2]), spec.thresholds[0], spec.thresholds[1], IntegrationSpec.MODES.index(spec.mode),
+                     ptr(self.acc), ptr(self.cnt), ptr(scratch), scratch.numel() * 8)
+
+    def all_reduce(self):
+        """Sum the accumulators over the ranks (where ``evaluate_survey`` reduces its histograms)."""
+        if self.acc is not None and parallel.rank_world()[1] > 1:
+            torch.distributed.all_reduce(self.acc)
+            torch.distributed.all_reduce(self.cnt)
+
+    def result(self):
+        """ONE download -> ``{"sv_sum": float64 [3, 3, n_pb, n_rb], "pixels": int64, same shape, "annotated":
+        ("background", "sandeel", "other"), "classes": ("sandeel", "other", "all"), "ping_edges", "range_edges"}``:
+        ``sv_sum[a, k]`` is the linear sv of the counted pixels annotated ``a`` that the model books in plane ``k`` (plane
+        "all": every counted pixel annotated ``a``), ``pixels`` their numbers; edges as ``finish_integration`` builds them.
+        ``nasc`` takes the result as it is."""
+        if self.acc is None:
+            raise ValueError("ScoredIntegration: nothing was evaluated into this holder yet")
+        res = integration_result(self.acc.cpu().numpy(), self.cnt.cpu().numpy(), self.spec, self.n_pings, self.n_range)
+        res["annotated"] = ANNOTATED_CLASSES
+        return res
+
+    @staticmethod
+    def _class(k):
+        k = {"sandeel": 1, "other": 2}.get(k, k)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k not in (1, 2):
+            raise ValueError(f"ScoredIntegration: class {k!r}: 1 / 'sandeel' or 2 / 'other'")
+        return int(k)
+
+    @staticmethod
+    def _ratio(num, den):
+        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+        return np.divide(num, den, out=np.full(num.shape, np.nan), where=den > 0)
+
+    def recall(self, k, result=None):
+        """sv-weighted recall of class ``k`` (1 / "sandeel", 2 / "other"): of the backscatter ANNOTATED ``k``, the share
+        the model books as ``k`` -- ``sv_sum[k, k - 1] / sv_sum[k, 2]``.  Returns ``(per cell float64 [n_pb, n_rb], over
+        the survey float)``; NaN where nothing is annotated ``k``.  ``result``: a ``result()`` already downloaded."""
+        k = self._class(k)
+        sv = (self.result() if result is None else result)["sv_sum"]
+        return self._ratio(sv[k, k - 1], sv[k, 2]), float(self._ratio(sv[k, k - 1].sum(), sv[k, 2].sum()))
+
+    def precision(self, k, result=None):
+        """sv-weighted precision of class ``k``: of the backscatter the model books as ``k``, the share that is annotated
+        ``k`` -- ``sv_sum[k, k - 1] / sv_sum[:, k - 1].sum(0)``.  Returns as ``recall``; NaN where nothing is booked."""
+        k = self._class(k)
+        sv = (self.result() if result is None else result)["sv_sum"]
+        booked = sv[:, k - 1].sum(axis=0)
+        return self._ratio(sv[k, k - 1], booked), float(self._ratio(sv[k, k - 1].sum(), booked.sum()))
 
 
 # ---- seabed line of a memmap echogram without a stored seabed.npy (Echogram.get_seabed, data_reader.py:433-507) ---------
@@ -1945,7 +2090,7 @@ def split_histograms(h, classes=None):
 
 
 def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, eval_mode="all",
-                    extend_size=20, predict_fn=None, on_batch=None, stats=None, classes=None, **kwargs):
+                    extend_size=20, predict_fn=None, on_batch=None, stats=None, classes=None, integration=None, **kwargs):
     """Test-set evaluation of one zarr survey (``validate_model_survey_zarr``, evaluate.py:39-81) on the tiled path:
     returns ``(hist_pos, hist_neg)`` int64 numpy [16384] -- what ``SegPipe.get_pr_histograms_dataloader`` returns for the
     reference's gridded test DataLoader over the same survey; ``SegPipe.validate_model_testing_from_histograms`` turns
@@ -1961,11 +2106,18 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
     get_object_bounding_boxes for ``eval_mode`` 'region' / 'trace').
     ``classes`` (e.g. ``(1, 2)``, ``check_classes``): the histograms of each named foreground class from the same pass --
     ``(hist_pos [K, 16384], hist_neg [K, 16384])``, rows in the order of ``classes``; row ``classes.index(1)`` is what
-    the call without ``classes`` returns."""
+    the call without ``classes`` returns.
+    ``integration`` (a ``ScoredIntegration``): the same pass also integrates the survey's sv by annotated and predicted
+    class (``ChunkPredictor.evaluate``); the return value is unchanged and the holder has the result
+    (``integration.result()``).  With several ranks its accumulators are sum-reduced where the histograms are."""
     if classes is not None:
         classes = check_classes(classes, segpipe.model.n_classes)
     n_pings, n_range = (int(v) for v in reader.shape)
     dev = segpipe.device
+    if integration is not None:
+        if not isinstance(integration, ScoredIntegration):
+            raise TypeError(f"evaluate_survey: integration is a ScoredIntegration, got {type(integration).__name__}")
+        integration.begin(segpipe.frequencies, segpipe.model.n_classes, dev, n_pings, n_range)
     model = segpipe.model.to(dev).eval()
     cp = ChunkPredictor(model, n_range, patch_size, patch_overlap, batch_size)
     n_freq = len(segpipe.frequencies)
@@ -1985,6 +2137,8 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
         stats["patches"] = int(sum(len(c[0]) for c in mine))
         stats["chunks"] = len(mine)
     if not mine:
+        if integration is not None:
+            integration.all_reduce()
         return finish_histograms(hist, classes=classes)
     widest = max(hi - lo for _, lo, hi in mine)
 
@@ -2011,8 +2165,11 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
     with _ChunkFeed(dev, "eval", table, 2, mine, fetch) as feed:      # 2 host slots: one chunk is read while one is uploaded
         for (idx, lo, hi), (d, mask) in zip(mine, feed):
             _load_staged(cp, d["data"], lo, d["lab"], lo, hi, d["sb"], mask, wide=True)
-            cp.evaluate(grid[idx], hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch, classes=classes)
+            cp.evaluate(grid[idx], hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch, classes=classes,
+                        integration=integration)
             feed.computed()
+        if integration is not None:
+            integration.all_reduce()
         out = finish_histograms(hist, classes=classes)
     if stats is not None:
         stats["seconds"] = time.perf_counter() - t_start
@@ -2021,7 +2178,7 @@ def evaluate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prel
 
 def evaluate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, eval_mode="all", extend_size=20,
                            predict_fn=None, meta_channels=None, hist=None, on_batch=None, seabed=None, classes=None,
-                           **kwargs):
+                           integration=None, **kwargs):
     """Test-set evaluation of one memmap echogram (one Dataset of ``validate_model_survey_memm``, evaluate.py:84-117) on
     the tiled path.  The echogram is one resident chunk, its grid the echogram's (``plan_eval_grid``); metadata models
     (late injection and metadata input channels) take ``meta_channels`` and ``seabed`` (None / "estimate" / an integer
@@ -2030,9 +2187,17 @@ def evaluate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_s
     ``hist`` (int32 [2, 16384] on the GPU): accumulate into it and return it -- a survey of several echograms, whose caller
     finishes with ``finish_histograms``; None: returns this echogram's ``(hist_pos, hist_neg)`` int64 numpy (no
     collective: every rank that calls it evaluates the echogram it passes).
-    ``classes``: per-class histograms as ``evaluate_survey`` returns them; ``hist`` is then int32 [n_classes, 2, 16384]."""
+    ``classes``: per-class histograms as ``evaluate_survey`` returns them; ``hist`` is then int32 [n_classes, 2, 16384].
+    ``integration`` (a ``ScoredIntegration``): the echogram's sv by annotated and predicted class from the same pass, as in
+    ``evaluate_survey``; no collective, and the return value is unchanged."""
     if classes is not None:            # (the default path asks nothing new of its arguments)
         classes = check_classes(classes, segpipe.model.n_classes, hist)
+    if integration is not None:
+        if not isinstance(integration, ScoredIntegration):
+            raise TypeError(f"evaluate_echogram_memm: integration is a ScoredIntegration, got {type(integration).__name__}")
+        if segpipe.model.n_classes != 3:            # (before the echogram is uploaded)
+            raise ValueError(f"evaluate_echogram_memm: integration= with a model of n_classes={segpipe.model.n_classes}; the "
+                             "scored integration is that of a 3-class model")
     cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
                                      out_f16=False, wide=True, seabed=seabed)
     dev = segpipe.device
@@ -2043,7 +2208,10 @@ def evaluate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_s
     own = hist is None
     if own:
         hist = new_histograms(dev, classes, cp.engine)
-    cp.evaluate(grid, hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch, classes=classes)
+    if integration is not None:
+        integration.begin(segpipe.frequencies, segpipe.model.n_classes, dev, cp.end_ping, cp.n_range)
+    cp.evaluate(grid, hist, eval_mode, boxes, predict_fn=predict_fn, on_batch=on_batch, classes=classes,
+                integration=integration)
     return finish_histograms(hist, all_reduce=False, classes=classes) if own else hist
 
 
@@ -2082,7 +2250,7 @@ def _takes_keyword(fn, name):
 
 def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, eval_mode="all", extend_size=20,
                             predict_fn=None, meta_channels=None, seabed=None, hist=None, on_batch=None, group_patches=None,
-                            group_elems=None, stats=None, pack_metadata=False, classes=None, **kwargs):
+                            group_elems=None, stats=None, pack_metadata=False, classes=None, integration=None, **kwargs):
     """Test-set evaluation of a whole memm survey (``validate_model_survey_memm``, evaluate.py:84-117) on the tiled path:
     ``(hist_pos, hist_neg)`` int64 numpy [16384], the sum of ``evaluate_echogram_memm`` over ``echograms``.
 
@@ -2102,7 +2270,13 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
     ``on_batch(centres [P, 2] numpy, labels int16 [P, H, W], logits [P, 3, H, W])`` sees every batch; a callback that
     declares the keyword ``echograms`` also gets the echogram of every patch of the batch (a list of P).
     ``classes``: per-class histograms as ``evaluate_survey`` returns them, from ``crimac_pr_histogram_classes`` on the
-    packed and on the per-echogram leg alike; ``hist`` is then int32 [n_classes, 2, 16384]."""
+    packed and on the per-echogram leg alike; ``hist`` is then int32 [n_classes, 2, 16384].
+    ``integration``: the scored integration is not built for packed batches -- NotImplementedError; call
+    ``evaluate_echogram_memm(..., integration=ScoredIntegration(spec))`` per echogram."""
+    if integration is not None:
+        raise NotImplementedError("evaluate_echograms_memm: integration= is not available on the packed flow (every echogram "
+                                  "has its own ping axis); call evaluate_echogram_memm(echogram, ..., integration="
+                                  "ScoredIntegration(spec)) per echogram")
     if classes is not None:            # (the default path asks nothing new of its arguments)
         classes = check_classes(classes, segpipe.model.n_classes, hist)
     flow = _MemmSurveyFlow("evaluate_echograms_memm",

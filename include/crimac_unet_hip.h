@@ -566,6 +566,11 @@ int crimac_scatter_patches_multi(const float* probs, int ncls, const crimac_memm
  * One launch for all P <= 65535 patches; 16-byte stores when pw % 8 == 0 and both outputs are 16-byte aligned. */
 int crimac_gather_eval_crops(const float* data, int C, int Wd, int H, const short* labels, const int* centres, int P,
                              int ph, int pw, int flavour, float* data_out, short* labels_out, void* stream);
+/* Where crimac_gather_eval_crops places its crops, by the same device function: origins [P][2] int32 = the (row, ping) of
+ * crop pixel (0, 0) of patch p in the coordinates its centre is given in -- GLOBAL centres give global origins.  Both
+ * flavours, the centre row H / 2 of flavour 1 when H <= ph included: a caller that must know where a crop's pixels lie
+ * (crimac_integrate_confusion) asks here and does not restate the rule. */
+int crimac_eval_crop_origins(const int* centres, int P, int ph, int pw, int H, int flavour, int* origins, void* stream);
 
 /* Evaluation batches packed from SEVERAL memmap echograms (tiled_inference.evaluate_echograms_memm): the evaluation chain
  * with the per-source arguments of each patch taken from descs[src[p]] (crimac_memm_desc above; `out` is unused here), as
@@ -880,6 +885,40 @@ int crimac_integrate_layers(const void* pred, int pred_f16, int n_range, long n_
                             long ping_origin, long n_pb_total, const int* seabed, long seabed_first, long seabed_len,
                             int seabed_offset, int reference, int n_layers, double* acc, long long* cnt, void* scratch,
                             long scratch_bytes, void* stream);
+
+/* Echo integration SCORED AGAINST THE ANNOTATIONS: the sums of crimac_integrate_classes split by the annotated class as
+ * well, from one evaluation batch while it is resident (ChunkPredictor.evaluate).  The reference has no counterpart.
+ *   logits fp32 [P][ncls][ph][pw] with ncls == 3 (anything else: CRIMAC_ERR_ARG); raw fp32 [P][C][ph][pw] linear sv (what
+ *     crimac_gather_eval_crops wrote), plane `channel` is summed; labels int16 [P][ph][pw] TRANSFORMED labels
+ *     (crimac_labels_test_transform: overlap border and ignored pixels negative, so every survey pixel is valid in at most
+ *     one patch); origins int32 [P][2] = the global (row, ping) of pixel (0, 0) of each patch, as
+ *     crimac_eval_crop_origins states them -- the placement rule stays with the gather.  1 <= P <=
+ *     CRIMAC_CONFUSION_MAX_PATCHES, ph, pw <= 32768.
+ *   Cells as in crimac_integrate_classes: cell (pb, rb) covers global pings [pb * ping_bin, (pb + 1) * ping_bin) and rows
+ *     [rb * range_bin, (rb + 1) * range_bin), n_rb = ceil(n_range / range_bin), the last range bin may be partial.
+ *   A pixel is COUNTED only when its label is 0, 1 or 2 (EVERY negative label is skipped: -100, -1, -50 ...), its sv is
+ *     finite and > 0, and its global position lies in [0, n_range) x [0, n_pb_total * ping_bin); a pixel outside that grid
+ *     is skipped whatever its label, and nothing is read or written for it.  The largest finite float counts as NOT
+ *     finite: it is what the zarr crop's nan_to_num makes of +Inf (crimac_gather_eval_crops, flavour 0).
+ *   p_k = softmax(logits)[k] rounded to float16, one softmax per pixel with the arithmetic of crimac_pr_histogram_classes
+ *     (the same device function), so a threshold read off its histograms selects exactly the pixels they counted.
+ *     mode 0 (threshold): w_k = 1 when p_k widened to fp32 is >= thr_k, else 0; a pixel may be in both classes.  mode 1
+ *     (probability): w_k = p_k, a NaN or negative p_k counts as 0.  thr_sandeel, thr_other > 0 in both modes.
+ *   acc fp64 [3][3][n_pb_total][n_rb]: acc[a][.] += (sv * w_sandeel, sv * w_other, sv) over the counted pixels annotated
+ *     a = 0 background, 1 sandeel, 2 other (the planes of crimac_integrate_classes: sandeel, other, all);
+ *   cnt int64, same shape: cnt[a][.] += (w_sandeel > 0, w_other > 0, 1).
+ *   Both ACCUMULATE (caller zeroes) by a plain read-add-write: no atomics, launches are ordered by the stream.  fp64 sums in
+ *     a fixed order (thread over its pixels, lanes, waves, then the patches of the batch in patch order) that depends on the
+ *     arguments alone: bit-reproducible for a given batching.  Counts are exact.  Element offsets are 64-bit.
+ *   scratch: scratch_bytes of device memory, 8-byte aligned, at least
+ *     P * (ceil(pw / ping_bin) + 1) * (ceil(ph / range_bin) + 1) * CRIMAC_CONFUSION_SLOT_BYTES
+ *     -- one slot per patch and cell of the window of cells a patch can overlap; contents undefined before and after. */
+#define CRIMAC_CONFUSION_SLOT_BYTES (3 * CRIMAC_INTEGRATE_SLOT_BYTES)
+#define CRIMAC_CONFUSION_MAX_PATCHES 1024
+int crimac_integrate_confusion(const float* logits, int ncls, const float* raw, int C, int channel, const short* labels,
+                               const int* origins, int P, int ph, int pw, int n_range, long ping_bin, int range_bin,
+                               long n_pb_total, float thr_sandeel, float thr_other, int mode, double* acc, long long* cnt,
+                               void* scratch, long scratch_bytes, void* stream);
 
 /* ---- measurement support (bench.py only, not on the product path) --------------------------- */
 
