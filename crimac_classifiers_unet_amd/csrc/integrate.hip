@@ -28,7 +28,8 @@
 // column, whatever the seabed values: a workgroup whose split finds no tile writes a zero slot.
 //
 // crimac_integrate_confusion (further down, its own two kernels): the sums of an EVALUATION batch -- logits, raw crops and
-// transformed labels in patch layout -- split by the annotated class as well.
+// transformed labels in patch layout -- split by the annotated class as well; crimac_integrate_confusion_multi: the same
+// two kernels for a batch packed from several echograms.
 #include "common.h"
 #include "pr_softmax.h"
 
@@ -397,6 +398,14 @@ int integrate(const char* who, const SeabedArgs* sb, const void* pred, int pred_
 // Finish: one thread per slot.  The thread of the FIRST patch of the batch whose window holds the slot's cell owns that
 // cell: it adds the cell's slots in patch order and does the plain read-add-write of its 18 outputs; the others leave.
 // Who owns what depends on the origins alone, so the order of every sum is a function of the arguments.
+//
+// crimac_integrate_confusion_multi (the MULTI instantiations of the same two kernels): a batch packed from several
+// echograms.  Patch p belongs to echogram src[p]; its workgroups take n_range from descs[src[p]], n_pb and the first word
+// of the echogram's [3][3][n_pb][n_rb] block inside acc / cnt from shares[src[p]], and a patch whose src names no
+// descriptor does no work.  Two patches of different echograms may have the same origin, so the finish keeps the src values
+// next to the window origins in LDS: the owner of a cell is the first patch WITH THE SAME src whose window holds it, and it
+// adds the slots of the patches with that src only, in patch order.  A (patch, cell) slot depends on the patch alone:
+// every echogram gets the bits a single-source launch over its patches of the batch, in batch order, would have given it.
 struct CSlot { Slot a[3]; };                                 // per annotated class: background, sandeel, other
 static_assert(sizeof(CSlot) == CRIMAC_CONFUSION_SLOT_BYTES, "scratch slot size is part of the ABI");
 constexpr int kConfusionMaxPatches = CRIMAC_CONFUSION_MAX_PATCHES;
@@ -405,13 +414,36 @@ struct CGeom {
   int P, C, channel, ph, pw, n_range, range_bin, n_rb, ncp, ncr, mode;
   long ping_bin, n_pb_total;
   float thr0, thr1;
+  // crimac_integrate_confusion_multi: the echogram of every patch; n_range, n_rb and n_pb_total above are not read
+  const crimac_memm_desc* descs;
+  int n_desc;
+  const int* src;
+  const long long* shares;                                   // [n_desc][2] = (first word of the echogram's block, n_pb)
 };
+
+// the grid patch p accumulates into: one for the launch, or (MULTI) its echogram's; false: src[p] names no descriptor
+struct CGrid { long n_range, n_rb, n_pb, first; };
+template <bool MULTI>
+__device__ __forceinline__ bool grid_of(const CGeom& g, int p, CGrid& out) {
+  if constexpr (MULTI) {
+    const int s = g.src[p];
+    if (s < 0 || s >= g.n_desc) return false;
+    out.n_range = g.descs[s].n_range;
+    out.n_rb = (out.n_range + g.range_bin - 1) / g.range_bin;
+    out.first = g.shares[2 * s];
+    out.n_pb = g.shares[2 * s + 1];
+  } else {
+    out = CGrid{g.n_range, g.n_rb, g.n_pb_total, 0};
+  }
+  return true;
+}
 
 __device__ __forceinline__ long floor_div(long a, long b) {      // b > 0
   const long q = a / b;
   return q - (a % b != 0 && a < 0);
 }
 
+template <bool MULTI>
 __global__ __launch_bounds__(kThreads) void confusion_cells_kernel(const float* __restrict__ logits,
                                                                    const float* __restrict__ raw,
                                                                    const short* __restrict__ labels,
@@ -420,16 +452,18 @@ __global__ __launch_bounds__(kThreads) void confusion_cells_kernel(const float* 
   __shared__ CSlot wave_part[kThreads / 64];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int i = blockIdx.x % g.ncp, j = blockIdx.x / g.ncp % g.ncr, p = blockIdx.x / (g.ncp * g.ncr);
+  CGrid e;
+  if (!grid_of<MULTI>(g, p, e)) return;                                    // (uniform, as the next return)
   const long y0 = origins[2 * p], x0 = origins[2 * p + 1];
   const long pb = floor_div(x0, g.ping_bin) + i, rb = floor_div(y0, g.range_bin) + j;
-  if (pb < 0 || pb >= g.n_pb_total || rb < 0 || rb >= g.n_rb) return;     // (uniform: nobody waits at the barrier)
+  if (pb < 0 || pb >= e.n_pb || rb < 0 || rb >= e.n_rb) return;            // (uniform: nobody waits at the barrier)
   // the cell in patch coordinates, clipped to the patch and to rows below n_range (its pings lie inside the grid)
   long c0 = pb * g.ping_bin - x0, c1 = c0 + g.ping_bin, r0 = rb * g.range_bin - y0, r1 = r0 + g.range_bin;
   c0 = c0 > 0 ? c0 : 0;
   r0 = r0 > 0 ? r0 : 0;
   c1 = c1 < g.pw ? c1 : g.pw;
   r1 = r1 < g.ph ? r1 : g.ph;
-  r1 = r1 < g.n_range - y0 ? r1 : g.n_range - y0;
+  r1 = r1 < e.n_range - y0 ? r1 : e.n_range - y0;
   const int w = c1 > c0 ? (int)(c1 - c0) : 0, h = r1 > r0 ? (int)(r1 - r0) : 0;
   const int n = w * h;                                       // (<= ph * pw < 2^31)
   const long HW = (long)g.ph * g.pw;
@@ -495,29 +529,36 @@ __global__ __launch_bounds__(kThreads) void confusion_cells_kernel(const float* 
   }
 }
 
+template <bool MULTI>
 __global__ __launch_bounds__(kThreads) void confusion_finish_kernel(const CSlot* __restrict__ scratch,
                                                                     const int* __restrict__ origins, CGeom g,
                                                                     double* __restrict__ acc, long long* __restrict__ cnt) {
-  // the first cell of every patch's window, once per workgroup
+  // the first cell of every patch's window (MULTI: and the patch's echogram), once per workgroup
   __shared__ long pb0[kConfusionMaxPatches];
   __shared__ int rb0[kConfusionMaxPatches];
+  __shared__ int src[MULTI ? kConfusionMaxPatches : 1];
   for (int q = threadIdx.x; q < g.P; q += kThreads) {
     rb0[q] = (int)floor_div(origins[2 * q], g.range_bin);
     pb0[q] = floor_div(origins[2 * q + 1], g.ping_bin);
+    if constexpr (MULTI) src[q] = g.src[q];
   }
   __syncthreads();
   const long slot = (long)blockIdx.x * kThreads + threadIdx.x;
   const int per_patch = g.ncp * g.ncr;
   if (slot >= (long)g.P * per_patch) return;
   const int p = (int)(slot / per_patch), i = (int)(slot % g.ncp), j = (int)(slot / g.ncp % g.ncr);
+  CGrid e;
+  if (!grid_of<MULTI>(g, p, e)) return;                                    // (no workgroup wrote this slot)
   const long pb = pb0[p] + i, rb = (long)rb0[p] + j;
-  if (pb < 0 || pb >= g.n_pb_total || rb < 0 || rb >= g.n_rb) return;      // (no workgroup wrote this slot)
+  if (pb < 0 || pb >= e.n_pb || rb < 0 || rb >= e.n_rb) return;            // (nor this one)
   for (int q = 0; q < p; ++q) {                                            // an earlier patch owns the cell
+    if (MULTI && src[q] != src[p]) continue;                               // (of the same echogram)
     const long qi = pb - pb0[q], qj = rb - rb0[q];
     if (qi >= 0 && qi < g.ncp && qj >= 0 && qj < g.ncr) return;
   }
   CSlot out = scratch[slot];
   for (int q = p + 1; q < g.P; ++q) {
+    if (MULTI && src[q] != src[p]) continue;
     const long qi = pb - pb0[q], qj = rb - rb0[q];
     if (qi < 0 || qi >= g.ncp || qj < 0 || qj >= g.ncr) continue;
     const CSlot& x = scratch[((long)q * g.ncr + qj) * g.ncp + qi];
@@ -529,7 +570,7 @@ __global__ __launch_bounds__(kThreads) void confusion_finish_kernel(const CSlot*
   }
   for (int c = 0; c < 3; ++c)
     for (int k = 0; k < 3; ++k) {
-      const long at = (((long)c * 3 + k) * g.n_pb_total + pb) * g.n_rb + rb;
+      const long at = e.first + (((long)c * 3 + k) * e.n_pb + pb) * e.n_rb + rb;
       acc[at] += out.a[c].sum[k];
       cnt[at] += out.a[c].cnt[k];
     }
@@ -537,39 +578,37 @@ __global__ __launch_bounds__(kThreads) void confusion_finish_kernel(const CSlot*
 
 }  // namespace
 
-extern "C" int crimac_integrate_confusion(const float* logits, int ncls, const float* raw, int C, int channel,
-                                          const short* labels, const int* origins, int P, int ph, int pw, int n_range,
-                                          long ping_bin, int range_bin, long n_pb_total, float thr_sandeel, float thr_other,
-                                          int mode, double* acc, long long* cnt, void* scratch, long scratch_bytes,
-                                          void* stream) {
-  const char* who = "integrate_confusion";
+// Both confusion entry points: the argument checks, the geometry, the two launches.  `g` arrives with the grid of the
+// launch (single: n_range, n_pb_total) or with the echogram tables (multi: descs != NULL).
+static int confusion(const char* who, CGeom g, const float* logits, int ncls, const float* raw, int C, int channel,
+                     const short* labels, const int* origins, int P, int ph, int pw, long ping_bin, int range_bin,
+                     float thr_sandeel, float thr_other, int mode, double* acc, long long* cnt, void* scratch,
+                     long scratch_bytes, void* stream) {
+  const bool multi = g.descs != nullptr;
   CRIMAC_REQUIRE(logits && raw && labels && origins && acc && cnt && scratch, "%s: null pointer", who);
   CRIMAC_REQUIRE(ncls == 3, "%s: ncls=%d: the planes are those of a 3-class model (background, sandeel, other)", who, ncls);
   CRIMAC_REQUIRE(P > 0 && P <= kConfusionMaxPatches, "%s: P=%d patches (1 .. CRIMAC_CONFUSION_MAX_PATCHES = %d per launch)",
                  who, P, kConfusionMaxPatches);
   CRIMAC_REQUIRE(ph > 0 && pw > 0 && ph <= 32768 && pw <= 32768, "%s: patch %d x %d (1 .. 32768 each)", who, ph, pw);
   CRIMAC_REQUIRE(C > 0 && channel >= 0 && channel < C, "%s: channel %d of %d sv planes", who, channel, C);
-  CRIMAC_REQUIRE(n_range > 0, "%s: n_range=%d", who, n_range);
+  CRIMAC_REQUIRE(multi || g.n_range > 0, "%s: n_range=%d", who, g.n_range);
   CRIMAC_REQUIRE(mode == 0 || mode == 1, "%s: mode %d (0 threshold, 1 probability)", who, mode);
   CRIMAC_REQUIRE(thr_sandeel > 0.f && thr_other > 0.f, "%s: thr = (%g, %g) must be > 0", who, (double)thr_sandeel,
                  (double)thr_other);
   CRIMAC_REQUIRE(ping_bin > 0 && range_bin > 0, "%s: ping_bin=%ld, range_bin=%d must be positive", who, ping_bin, range_bin);
-  CRIMAC_REQUIRE(ping_bin <= 2147483647L && n_pb_total > 0 && n_pb_total <= 2147483647L, "%s: ping_bin=%ld, n_pb_total=%ld "
-                 "outside 1 .. 2^31 - 1", who, ping_bin, n_pb_total);
-  CGeom g;
+  CRIMAC_REQUIRE(ping_bin <= 2147483647L && (multi || (g.n_pb_total > 0 && g.n_pb_total <= 2147483647L)),
+                 "%s: ping_bin=%ld, n_pb_total=%ld outside 1 .. 2^31 - 1", who, ping_bin, g.n_pb_total);
   g.P = P;
   g.C = C;
   g.channel = channel;
   g.ph = ph;
   g.pw = pw;
-  g.n_range = n_range;
   g.range_bin = range_bin;
-  g.n_rb = (n_range + range_bin - 1) / range_bin;
+  g.n_rb = multi ? 0 : (g.n_range + range_bin - 1) / range_bin;
   g.ncp = (int)((pw + ping_bin - 1) / ping_bin) + 1;
   g.ncr = (ph + range_bin - 1) / range_bin + 1;
   g.mode = mode;
   g.ping_bin = ping_bin;
-  g.n_pb_total = n_pb_total;
   g.thr0 = thr_sandeel;
   g.thr1 = thr_other;
   const long slots = (long)P * g.ncp * g.ncr;
@@ -578,13 +617,43 @@ extern "C" int crimac_integrate_confusion(const float* logits, int ncls, const f
                  "%s: scratch of %ld bytes, this launch needs %ld (8-byte aligned; P * (ceil(pw / ping_bin) + 1) * "
                  "(ceil(ph / range_bin) + 1) * CRIMAC_CONFUSION_SLOT_BYTES)", who, scratch_bytes, slots * (long)sizeof(CSlot));
   const hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(confusion_cells_kernel, dim3((unsigned)slots), dim3(kThreads), 0, st, logits, raw, labels, origins, g,
-                     (CSlot*)scratch);
+  const dim3 finish((unsigned)((slots + kThreads - 1) / kThreads));
+  if (multi) hipLaunchKernelGGL(confusion_cells_kernel<true>, dim3((unsigned)slots), dim3(kThreads), 0, st, logits, raw, labels, origins, g, (CSlot*)scratch);
+  else hipLaunchKernelGGL(confusion_cells_kernel<false>, dim3((unsigned)slots), dim3(kThreads), 0, st, logits, raw, labels, origins, g, (CSlot*)scratch);
   CRIMAC_LAUNCH_CHECK();
-  hipLaunchKernelGGL(confusion_finish_kernel, dim3((unsigned)((slots + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                     (const CSlot*)scratch, origins, g, acc, cnt);
+  if (multi) hipLaunchKernelGGL(confusion_finish_kernel<true>, finish, dim3(kThreads), 0, st, (const CSlot*)scratch, origins, g, acc, cnt);
+  else hipLaunchKernelGGL(confusion_finish_kernel<false>, finish, dim3(kThreads), 0, st, (const CSlot*)scratch, origins, g, acc, cnt);
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
+}
+
+extern "C" int crimac_integrate_confusion(const float* logits, int ncls, const float* raw, int C, int channel,
+                                          const short* labels, const int* origins, int P, int ph, int pw, int n_range,
+                                          long ping_bin, int range_bin, long n_pb_total, float thr_sandeel, float thr_other,
+                                          int mode, double* acc, long long* cnt, void* scratch, long scratch_bytes,
+                                          void* stream) {
+  CGeom g{};
+  g.n_range = n_range;
+  g.n_pb_total = n_pb_total;
+  return confusion("integrate_confusion", g, logits, ncls, raw, C, channel, labels, origins, P, ph, pw, ping_bin, range_bin,
+                   thr_sandeel, thr_other, mode, acc, cnt, scratch, scratch_bytes, stream);
+}
+
+extern "C" int crimac_integrate_confusion_multi(const float* logits, int ncls, const float* raw, int C, int channel,
+                                                const short* labels, const int* origins, const crimac_memm_desc* descs,
+                                                int n_desc, const int* src, const long long* shares, int P, int ph, int pw,
+                                                long ping_bin, int range_bin, float thr_sandeel, float thr_other, int mode,
+                                                double* acc, long long* cnt, void* scratch, long scratch_bytes,
+                                                void* stream) {
+  CRIMAC_REQUIRE(descs && src && shares, "integrate_confusion_multi: null pointer (descs, src, shares)");
+  CRIMAC_REQUIRE(n_desc > 0, "integrate_confusion_multi: n_desc=%d descriptors", n_desc);
+  CGeom g{};
+  g.descs = descs;
+  g.n_desc = n_desc;
+  g.src = src;
+  g.shares = shares;
+  return confusion("integrate_confusion_multi", g, logits, ncls, raw, C, channel, labels, origins, P, ph, pw, ping_bin,
+                   range_bin, thr_sandeel, thr_other, mode, acc, cnt, scratch, scratch_bytes, stream);
 }
 
 extern "C" int crimac_integrate_classes(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv,

@@ -350,12 +350,14 @@ __device__ __forceinline__ void eval_crop_origin(int cy, int cx, int ph, int pw,
   x0 = cx - (flavour == 1 ? (pw + 1) / 2 : pw / 2) + 1;
 }
 
-__global__ __launch_bounds__(256) void eval_crop_origins_kernel(const int* __restrict__ centres, int P, int ph, int pw, int H,
-                                                                int flavour, int* __restrict__ origins) {
+// `s`: H alone (crimac_eval_crop_origins) or the descriptor table (crimac_eval_crop_origins_multi: H is the n_range of the
+// patch's own echogram, and a patch whose src names no descriptor gets no write)
+__global__ __launch_bounds__(256) void eval_crop_origins_kernel(PatchSrc s, const int* __restrict__ centres, int P, int ph,
+                                                                int pw, int flavour, int* __restrict__ origins) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= P) return;
+  if (p >= P || !s.resolve(p)) return;
   int y0, x0;
-  eval_crop_origin(centres[2 * p], centres[2 * p + 1], ph, pw, H, flavour, y0, x0);
+  eval_crop_origin(centres[2 * p], centres[2 * p + 1], ph, pw, s.H, flavour, y0, x0);
   origins[2 * p] = y0;
   origins[2 * p + 1] = x0;
 }
@@ -470,7 +472,17 @@ extern "C" int crimac_eval_crop_origins(const int* centres, int P, int ph, int p
   CRIMAC_REQUIRE(centres && origins && P > 0 && ph > 0 && pw > 0 && H > 0, "eval_crop_origins: bad arguments");
   CRIMAC_REQUIRE(flavour == 0 || flavour == 1, "eval_crop_origins: flavour=%d (0 zarr, 1 memm)", flavour);
   hipLaunchKernelGGL(eval_crop_origins_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     centres, P, ph, pw, H, flavour, origins);
+                     PatchSrc{nullptr, 0, H}, centres, P, ph, pw, flavour, origins);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}
+
+extern "C" int crimac_eval_crop_origins_multi(const crimac_memm_desc* descs, int n_desc, const int* src, const int* centres,
+                                              int P, int ph, int pw, int* origins, void* stream) {
+  const PatchSrc s{nullptr, 0, 0, nullptr, descs, n_desc, src};
+  CRIMAC_REQUIRE(descs && s.ok() && centres && origins && P > 0 && ph > 0 && pw > 0, "eval_crop_origins_multi: bad arguments");
+  hipLaunchKernelGGL(eval_crop_origins_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s,
+                     centres, P, ph, pw, 1, origins);
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
 }

@@ -1099,7 +1099,42 @@ def confusion_scratch_bytes(P, ph, pw, ping_bin, range_bin):
     return P * (-(-pw // ping_bin) + 1) * (-(-ph // range_bin) + 1) * CONFUSION_SLOT_BYTES
 
 
-class ScoredIntegration:
+class _ScoredHolder:
+    """What ``ScoredIntegration`` and ``ScoredIntegrationSet`` share: the checks of the spec and of the model, the class
+    names and the NaN-safe ratio of their recall / precision."""
+
+    @classmethod
+    def _checked(cls, spec):
+        """``spec`` if a scored holder takes it (``ScoredIntegrationSet`` makes the same checks)."""
+        if not isinstance(spec, IntegrationSpec):
+            raise TypeError(f"{cls.__name__}: spec is an IntegrationSpec, got {type(spec).__name__}")
+        if spec.seabed_aware or spec.reference != "surface":
+            raise NotImplementedError(f"{cls.__name__}: a seabed-aware spec (seabed_offset / reference='seabed') is not "
+                                      "scored: the transformed labels already exclude the pixels below the seabed")
+        return spec
+
+    @classmethod
+    def _bound(cls, spec, frequencies, n_classes):
+        """``spec`` bound to the model's ``frequencies``, after the check that the model has 3 classes."""
+        if int(n_classes) != 3:
+            raise ValueError(f"{cls.__name__}: the model has n_classes={n_classes}; the planes (sandeel, other, all) and "
+                             "the annotated classes (background, sandeel, other) are those of a 3-class model")
+        return spec.bind(frequencies)
+
+    @staticmethod
+    def _class(k):
+        k = {"sandeel": 1, "other": 2}.get(k, k)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k not in (1, 2):
+            raise ValueError(f"scored integration: class {k!r}: 1 / 'sandeel' or 2 / 'other'")
+        return int(k)
+
+    @staticmethod
+    def _ratio(num, den):
+        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+        return np.divide(num, den, out=np.full(num.shape, np.nan), where=den > 0)
+
+
+class ScoredIntegration(_ScoredHolder):
     """Echo integration scored against the annotations: hand one to ``evaluate_survey`` / ``evaluate_echogram_memm`` /
     ``ChunkPredictor.evaluate`` as ``integration=`` and every evaluation batch is reduced on the GPU
     (``crimac_integrate_confusion``), while its raw crops, transformed labels and logits are resident, to the linear sv of
@@ -1113,12 +1148,7 @@ class ScoredIntegration:
     below the seabed, and bottom layers are not scored."""
 
     def __init__(self, spec):
-        if not isinstance(spec, IntegrationSpec):
-            raise TypeError(f"ScoredIntegration: spec is an IntegrationSpec, got {type(spec).__name__}")
-        if spec.seabed_aware or spec.reference != "surface":
-            raise NotImplementedError("ScoredIntegration: a seabed-aware spec (seabed_offset / reference='seabed') is not "
-                                      "scored: the transformed labels already exclude the pixels below the seabed")
-        self.spec = spec
+        self.spec = self._checked(spec)
         self.acc = self.cnt = None
         self.n_pings = self.n_range = None
 
@@ -1126,10 +1156,7 @@ class ScoredIntegration:
         """What a flow does first: bind the spec to the model's ``frequencies``, check the model (3 classes) and allocate
         the zeroed accumulators, float64 / int64 ``[3, 3, n_pb, n_rb]`` on ``dev``, for a survey of ``n_pings`` x
         ``n_range``.  A holder that has begun keeps accumulating when the extent is the same one and raises otherwise."""
-        if int(n_classes) != 3:
-            raise ValueError(f"ScoredIntegration: the model has n_classes={n_classes}; the planes (sandeel, other, all) and "
-                             "the annotated classes (background, sandeel, other) are those of a 3-class model")
-        spec = self.spec.bind(frequencies)
+        spec = self._bound(self.spec, frequencies, n_classes)
         extent = (int(n_pings), int(n_range))
         if self.acc is not None:
             if (self.n_pings, self.n_range) != extent or spec.channel != self.spec.channel:
@@ -1192,18 +1219,6 @@ class ScoredIntegration:
         res["annotated"] = ANNOTATED_CLASSES
         return res
 
-    @staticmethod
-    def _class(k):
-        k = {"sandeel": 1, "other": 2}.get(k, k)
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k not in (1, 2):
-            raise ValueError(f"ScoredIntegration: class {k!r}: 1 / 'sandeel' or 2 / 'other'")
-        return int(k)
-
-    @staticmethod
-    def _ratio(num, den):
-        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
-        return np.divide(num, den, out=np.full(num.shape, np.nan), where=den > 0)
-
     def recall(self, k, result=None):
         """sv-weighted recall of class ``k`` (1 / "sandeel", 2 / "other"): of the backscatter ANNOTATED ``k``, the share
         the model books as ``k`` -- ``sv_sum[k, k - 1] / sv_sum[k, 2]``.  Returns ``(per cell float64 [n_pb, n_rb], over
@@ -1219,6 +1234,158 @@ class ScoredIntegration:
         sv = (self.result() if result is None else result)["sv_sum"]
         booked = sv[:, k - 1].sum(axis=0)
         return self._ratio(sv[k, k - 1], booked), float(self._ratio(sv[k, k - 1].sum(), booked.sum()))
+
+
+class ScoredIntegrationSet(_ScoredHolder):
+    """``ScoredIntegration`` for a memm survey of many echograms, each with its own ping axis: hand one to
+    ``evaluate_echograms_memm`` as ``integration=``.  Every packed evaluation batch is reduced on the GPU by
+    ``crimac_integrate_confusion_multi`` into its echograms' shares of the group's accumulators; echograms that take the
+    per-echogram path are scored by a ``ScoredIntegration`` of their own.  ``spec``: as ``ScoredIntegration`` takes it, the
+    refusal of a seabed-aware spec included.  Afterwards ``results()`` has every echogram's result, ``totals()`` /
+    ``recall`` / ``precision`` the survey's figures."""
+
+    def __init__(self, spec):
+        self.spec = self._checked(spec)
+        self._results, self._reduced = [], None
+
+    def begin(self, frequencies, n_classes):
+        """What the flow does first: bind the spec to the model's ``frequencies`` and check the model (3 classes).  A set
+        that has begun keeps collecting when the channel is the same one and raises otherwise."""
+        spec = self._bound(self.spec, frequencies, n_classes)
+        if self.spec.channel is not None and spec.channel != self.spec.channel:
+            raise ValueError(f"ScoredIntegrationSet: begun for channel {self.spec.channel}, now asked for channel "
+                             f"{spec.channel}: one set per model")
+        self.spec = spec
+        return self
+
+    def shares(self, group):
+        """The layout of a packed group's flat accumulators: ``([(first word, (n_pb, n_rb))] per record, words)`` -- the
+        ``[3, 3, n_pb, n_rb]`` blocks of the echograms one after the other."""
+        shares, total = [], 0
+        for r in group:
+            shape = self.spec.bins(r.n_pings, r.n_range)
+            shares.append((total, shape))
+            total += 9 * shape[0] * shape[1]
+        return shares, total
+
+    def add_batch(self, engine, logits, raw, labels_t, cen, src, at, descs, n_desc, shares, acc, cnt):
+        """One packed evaluation batch: ``logits`` fp32 [P, 3, ph, pw], ``raw`` fp32 [P, C, ph, pw], ``labels_t`` int16
+        [P, ph, pw] as ``ScoredIntegration.add_batch`` takes them; ``cen`` / ``src``: the group's centres int32 [.][2] and
+        src int32 [.] on the GPU, of which the batch is patches ``at`` ...; ``descs`` / ``shares`` / ``acc`` / ``cnt``: device
+        pointers (``hip.ptr``) of the group's descriptor table, its share table int64 [n_desc][2] and its flat
+        accumulators.  Launches on the current stream; nothing comes back."""
+        P, ncls, ph, pw = logits.shape
+        C = raw.shape[1]
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or tuple(raw.shape) != (P, C, ph, pw) \
+                or tuple(labels_t.shape) != (P, ph, pw) or labels_t.dtype != torch.int16 or not labels_t.is_contiguous():
+            raise ValueError(f"ScoredIntegrationSet: logits {logits.dtype} {tuple(logits.shape)}, raw {tuple(raw.shape)}, "
+                             f"labels {labels_t.dtype} {tuple(labels_t.shape)}: contiguous fp32 [P, 3, H, W], fp32 [P, C, H, "
+                             "W], int16 [P, H, W]")
+        spec = self.spec
+        if spec.channel is None or not 0 <= spec.channel < C:
+            raise ValueError(f"ScoredIntegrationSet: channel {spec.channel} of {C} data planes (begin() binds it)")
+        for b0 in range(0, P, CONFUSION_MAX_PATCHES):
+            n = min(CONFUSION_MAX_PATCHES, P - b0)
+            origins = engine._buf("confusion.origins", (n, 2), torch.int32)
+            scratch = engine._buf("confusion.scratch",
+                                  (confusion_scratch_bytes(n, ph, pw, spec.ping_bin, spec.range_bin) // 8,), torch.float64)
+            call("crimac_eval_crop_origins_multi", descs, n_desc, ptr(src, at + b0), ptr(cen, 2 * (at + b0)), n, ph, pw,
+                 ptr(origins))
+            call("crimac_integrate_confusion_multi", ptr(logits[b0:b0 + n]), ncls, ptr(raw[b0:b0 + n]), C, spec.channel,
+                 ptr(labels_t[b0:b0 + n]), ptr(origins), descs, n_desc, ptr(src, at + b0), shares, n, ph, pw, spec.ping_bin,
+                 spec.range_bin, spec.thresholds[0], spec.thresholds[1], IntegrationSpec.MODES.index(spec.mode), acc, cnt,
+                 ptr(scratch), scratch.numel() * 8)
+
+    def add(self, echogram, result):
+        """``result`` (what ``ScoredIntegration.result()`` returns for ``echogram`` alone) as the next of the set."""
+        self._results.append((echogram, result))
+        self._reduced = None
+
+    def add_group(self, group, shares, sums, counts):
+        """The downloaded accumulators of a packed group (numpy, flat, laid out by ``shares``): one result per record."""
+        for r, (at, shape) in zip(group, shares):
+            n = 9 * shape[0] * shape[1]
+            res = integration_result(sums[at:at + n].reshape(3, 3, *shape).copy(), counts[at:at + n].reshape(3, 3, *shape).copy(),
+                                     self.spec, r.n_pings, r.n_range)
+            res["annotated"] = ANNOTATED_CLASSES
+            self.add(r.echogram, res)
+
+    def results(self):
+        """``[(echogram, result)]`` in evaluation order (with several ranks: this rank's echograms); every ``result`` is
+        what ``ScoredIntegration.result()`` returns for that echogram alone, its own ``ping_edges`` / ``range_edges``
+        included.  ``nasc`` takes a result as it is."""
+        return list(self._results)
+
+    def _own_totals(self):
+        sv, px = np.zeros((3, 3), dtype=np.float64), np.zeros((3, 3), dtype=np.int64)
+        for _, res in self._results:
+            sv += res["sv_sum"].sum(axis=(2, 3))
+            px += res["pixels"].sum(axis=(2, 3))
+        return sv, px
+
+    def all_reduce(self, dev):
+        """Sum the totals over the ranks (where ``evaluate_echograms_memm`` reduces its histograms); ``results()`` stay
+        the rank's own."""
+        if parallel.rank_world()[1] > 1:
+            sv, px = (torch.from_numpy(a).to(dev) for a in self._own_totals())
+            torch.distributed.all_reduce(sv)
+            torch.distributed.all_reduce(px)
+            self._reduced = (sv.cpu().numpy(), px.cpu().numpy())
+
+    def totals(self):
+        """``{"sv_sum": float64 [3, 3], "pixels": int64 [3, 3], "annotated", "classes"}``: ``results()`` summed over cells
+        and echograms -- with several ranks over every rank's echograms, reduced once at the end of the flow."""
+        sv, px = self._own_totals() if self._reduced is None else self._reduced
+        return {"sv_sum": sv, "pixels": px, "annotated": ANNOTATED_CLASSES, "classes": INTEGRATION_CLASSES}
+
+    def recall(self, k):
+        """sv-weighted recall of class ``k`` (1 / "sandeel", 2 / "other") by ``ScoredIntegration.recall``'s formula:
+        ``(per echogram float64 [n], over the survey float)``; NaN where nothing is annotated ``k``."""
+        k = self._class(k)
+        per = np.array([[res["sv_sum"][k, k - 1].sum(), res["sv_sum"][k, 2].sum()] for _, res in self._results]).reshape(-1, 2)
+        sv = self.totals()["sv_sum"]
+        return self._ratio(per[:, 0], per[:, 1]), float(self._ratio(sv[k, k - 1], sv[k, 2]))
+
+    def precision(self, k):
+        """sv-weighted precision of class ``k`` by ``ScoredIntegration.precision``'s formula; returns as ``recall``; NaN
+        where nothing is booked as ``k``."""
+        k = self._class(k)
+        per = np.array([[res["sv_sum"][k, k - 1].sum(), res["sv_sum"][:, k - 1].sum()] for _, res in self._results]).reshape(-1, 2)
+        sv = self.totals()["sv_sum"]
+        return self._ratio(per[:, 0], per[:, 1]), float(self._ratio(sv[k, k - 1], sv[:, k - 1].sum()))
+
+
+class _GroupAccumulators:
+    """The accumulators of the packed memm flows that reduce on the GPU: ONE flat fp64 buffer on the device, [sums |
+    counts] of the group at work, and a ring of two pinned buffers with events through which a group's few kilobytes leave
+    without blocking the feed."""
+
+    def __init__(self, dev):
+        self.dev, self.words, self.acc = dev, 0, None          # fp64 words of ``acc``: the largest group so far
+        self.pinned, self.events = [None, None], [torch.cuda.Event() for _ in range(2)]
+
+    def zeroed(self, k, total):
+        """The device buffer, its first ``2 * total`` words zeroed, for group ``k`` (all-zero bits: 0.0 and 0 alike)."""
+        if 2 * total > self.words:
+            self.words = 2 * total
+            self.acc = torch.empty(self.words, dtype=torch.float64, device=self.dev)
+        if self.pinned[k & 1] is None or self.pinned[k & 1].numel() < 2 * total:
+            self.pinned[k & 1] = torch.empty(self.words, dtype=torch.float64).pin_memory()
+        self.acc[:2 * total].zero_()
+        return self.acc
+
+    def download(self, k, total):
+        """Enqueue the download of group ``k``; returns what ``arrays`` takes once the next group has been enqueued."""
+        host = self.pinned[k & 1]
+        host[:2 * total].copy_(self.acc[:2 * total], non_blocking=True)
+        self.events[k & 1].record()
+        return host, self.events[k & 1], total
+
+    @staticmethod
+    def arrays(host, event, total):
+        """(sums float64 [total], counts int64 [total]) of a downloaded group: numpy views of its pinned buffer."""
+        event.synchronize()
+        return host[:total].numpy(), host[total:2 * total].view(torch.int64).numpy()
 
 
 # ---- seabed line of a memmap echogram without a stored seabed.npy (Echogram.get_seabed, data_reader.py:433-507) ---------
@@ -1894,9 +2061,8 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
             yield single(eg, sb, meta_channels)
         return
 
-    def take(group, shares, total, host, event):            # the group whose accumulators went into ``host``
-        event.synchronize()
-        sums, counts = host[:total].numpy(), host[total:2 * total].view(torch.int64).numpy()
+    def take(group, shares, download):            # the group whose accumulators went into a pinned buffer
+        sums, counts = _GroupAccumulators.arrays(*download)
         for r, (at, shape) in zip(group, shares):
             n = 3 * shape[0] * shape[1]
             yield r.echogram, integration_result(sums[at:at + n].reshape(3, *shape).copy(),
@@ -1905,12 +2071,10 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
     with flow.staged("memm_integrate", extra=lambda: dict(out=torch.empty(2 * flow.cap, dtype=torch.float16, device=flow.dev)),
                      out="out") as groups:
         pending = None
-        words = 0                          # fp64 words of the accumulator buffers: [sums | counts] of the largest group so far
         for g in groups:
             if g.k == 0:                             # (there is a group: the staging exists)
                 out = flow.feed.bufs["out"]
-                events = [torch.cuda.Event() for _ in range(2)]
-                pinned = [None, None]
+                ring = _GroupAccumulators(flow.dev)
             if g.offs is None:
                 if pending is not None:
                     yield from take(*pending)
@@ -1922,12 +2086,7 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
                 shape = spec.bins(r.n_pings, r.n_range)
                 shares.append((total, shape))
                 total += 3 * shape[0] * shape[1]
-            if 2 * total > words:
-                words = 2 * total
-                acc = torch.empty(words, dtype=torch.float64, device=flow.dev)
-            if pinned[g.k & 1] is None or pinned[g.k & 1].numel() < 2 * total:
-                pinned[g.k & 1] = torch.empty(words, dtype=torch.float64).pin_memory()
-            acc[:2 * total].zero_()                   # (all-zero bits: 0.0 and 0 alike)
+            acc = ring.zeroed(g.k, total)
             out[:2 * g.total].zero_()
             flow.predict_group(g, predict_fn)
             scratch = integration_scratch(flow.eng, max(s[0] * s[1] for _, s in shares))
@@ -1939,12 +2098,10 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
                                    ptr(acc, total + at), scratch, seabed=(ptr(g.misc, o_sb), 0, r.n_pings))
                 o_sb += r.n_pings
             flow.feed.computed()
-            host = pinned[g.k & 1]
-            host[:2 * total].copy_(acc[:2 * total], non_blocking=True)
-            events[g.k & 1].record()
+            download = ring.download(g.k, total)
             if pending is not None:
                 yield from take(*pending)
-            pending = (g.group, shares, total, host, events[g.k & 1])
+            pending = (g.group, shares, download)
         if pending is not None:
             yield from take(*pending)
 
@@ -2228,13 +2385,14 @@ def memm_box_table(boxes):
 
 class _MemmEvalRecord(_MemmRecord):
     """``_MemmRecord`` + the echogram's extended school boxes (None for eval_mode 'all'); the int32 words of the boxes and
-    of the echogram's entry in the offset table count towards what the echogram takes of a group's staging."""
+    of the echogram's entry in the offset table count towards what the echogram takes of a group's staging; ``scored``
+    (the flow has a ``ScoredIntegrationSet``): + its entry in the share table, and the word that aligns the table."""
 
-    def __init__(self, echogram, seabed, patch_size, patch_overlap, eval_mode="all", extend_size=20, **meta):
+    def __init__(self, echogram, seabed, patch_size, patch_overlap, eval_mode="all", extend_size=20, scored=False, **meta):
         super().__init__(echogram, seabed, patch_size, patch_overlap, **meta)
         self.boxes = eval_boxes(echogram, eval_mode, extend_size)
         words = 2 * hip.MEMM_DESC_WORDS + 3 * len(self.grid) + self.n_pings + 2 + \
-            (0 if self.boxes is None else 4 * len(self.boxes))
+            (0 if self.boxes is None else 4 * len(self.boxes)) + (5 if scored else 0)
         self.elems = max(self.elems, MEMM_MISC_SHARE * words)
 
 
@@ -2271,17 +2429,32 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
     declares the keyword ``echograms`` also gets the echogram of every patch of the batch (a list of P).
     ``classes``: per-class histograms as ``evaluate_survey`` returns them, from ``crimac_pr_histogram_classes`` on the
     packed and on the per-echogram leg alike; ``hist`` is then int32 [n_classes, 2, 16384].
-    ``integration``: the scored integration is not built for packed batches -- NotImplementedError; call
-    ``evaluate_echogram_memm(..., integration=ScoredIntegration(spec))`` per echogram."""
+    ``integration`` (a ``ScoredIntegrationSet``): the same pass also integrates every echogram's sv by annotated and
+    predicted class; the return value is unchanged and the set has the results -- ``integration.results()``: ``[(echogram,
+    result)]`` in evaluation order, every result that of ``evaluate_echogram_memm(..., integration=ScoredIntegration(spec))``
+    for the echogram: the same pixels, the same fp64 terms added in the order of the packed batches.  Per group ONE flat
+    fp64 / int64 buffer holds every echogram's ``[3, 3, n_pb, n_rb]`` share (the share table goes up behind the group's
+    ``misc``); every internal batch launches ``crimac_eval_crop_origins_multi`` -> ``crimac_integrate_confusion_multi``
+    right after its histograms, on the same stream, and the group's few kilobytes leave through a ring of two pinned
+    buffers with events: nothing in the feed blocks.  Metadata models without ``pack_metadata`` and echograms larger than
+    ``group_elems`` are scored by a ``ScoredIntegration`` of their own, in their place in the order.  With several ranks
+    ``results()`` holds the rank's own echograms (no collective) and ``totals()`` is sum-reduced once, where the histograms
+    are; with ``hist`` given nothing is reduced.  None: no buffer, no launch.  A ``ScoredIntegration`` has ONE ping axis
+    and is refused -- NotImplementedError; call ``evaluate_echogram_memm(..., integration=ScoredIntegration(spec))`` per
+    echogram, or pass a set."""
     if integration is not None:
-        raise NotImplementedError("evaluate_echograms_memm: integration= is not available on the packed flow (every echogram "
-                                  "has its own ping axis); call evaluate_echogram_memm(echogram, ..., integration="
-                                  "ScoredIntegration(spec)) per echogram")
+        if isinstance(integration, ScoredIntegration):
+            raise NotImplementedError("evaluate_echograms_memm: integration= is not available on the packed flow (every "
+                                      "echogram has its own ping axis); call evaluate_echogram_memm(echogram, ..., "
+                                      "integration=ScoredIntegration(spec)) per echogram, or pass a ScoredIntegrationSet")
+        if not isinstance(integration, ScoredIntegrationSet):
+            raise TypeError(f"evaluate_echograms_memm: integration is a ScoredIntegrationSet, got {type(integration).__name__}")
+        integration.begin(segpipe.frequencies, segpipe.model.n_classes)            # (before any data is touched)
     if classes is not None:            # (the default path asks nothing new of its arguments)
         classes = check_classes(classes, segpipe.model.n_classes, hist)
     flow = _MemmSurveyFlow("evaluate_echograms_memm",
                            ("group_patches", "group_elems", "seabed", "stats", "predict_fn", "meta_channels", "eval_mode",
-                            "extend_size", "hist", "on_batch", "pack_metadata", "classes"),
+                            "extend_size", "hist", "on_batch", "pack_metadata", "classes", "integration"),
                            kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
                            group_patches, group_elems, stats, eval_mode=eval_mode, meta_channels=meta_channels,
                            pack_metadata=pack_metadata)
@@ -2299,11 +2472,16 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
 
     def single(eg, sb, meta):            # the per-echogram path
         hook = None if on_batch is None else lambda cen, lab, logits: emit(cen, lab, logits, lambda: [eg] * len(cen))
+        child = None if integration is None else ScoredIntegration(integration.spec)
         evaluate_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, eval_mode=eval_mode,
                                extend_size=extend_size, predict_fn=predict_fn, meta_channels=meta, hist=hist, on_batch=hook,
-                               seabed=sb, classes=classes)
+                               seabed=sb, classes=classes, integration=child)
+        if child is not None:
+            integration.add(eg, child.result())
 
     def done():
+        if integration is not None and own:
+            integration.all_reduce(dev)
         return finish_histograms(hist, classes=classes) if own else hist
 
     if flow.alone:
@@ -2321,13 +2499,41 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
         misc[at + len(off):end] = rows.reshape(-1)
         return end
 
-    record = functools.partial(_MemmEvalRecord, eval_mode=eval_mode, extend_size=extend_size)
-    with flow.staged("memm-eval", record=record, tail=tail if masked else None) as groups:
+    def share_at(group, at):                         # the share table: behind the boxes, on an 8-byte boundary
+        if masked:
+            at += len(group) + 1 + 4 * sum(0 if r.boxes is None else len(r.boxes) for r in group)
+        return at + (at & 1)
+
+    def tail_scored(group, misc, at):                # ... | shares int64 [n][2] = (first word, n_pb)
+        if masked:
+            tail(group, misc, at)
+        at = share_at(group, at)
+        end = at + 4 * len(group)
+        assert end <= len(misc), "memm group staging too small (shares)"
+        misc[at:end].view(np.int64).reshape(-1, 2)[:] = [(first, shape[0]) for first, shape in integration.shares(group)[0]]
+        return end
+
+    def take(group, shares, download):               # the group whose accumulators went into a pinned buffer
+        integration.add_group(group, shares, *_GroupAccumulators.arrays(*download))
+
+    scored = integration is not None
+    record = functools.partial(_MemmEvalRecord, eval_mode=eval_mode, extend_size=extend_size, scored=scored)
+    with flow.staged("memm-eval", record=record, tail=tail_scored if scored else tail if masked else None) as groups:
+        pending = None
         for g in groups:
+            if scored and g.k == 0:                  # (there is a group: the staging exists)
+                ring = _GroupAccumulators(dev)
             if g.offs is None:
+                if pending is not None:              # (results in evaluation order)
+                    take(*pending)
+                    pending = None
                 single(g.group[0].echogram, *flow.solo(g.group[0]))
                 continue
             misc, n, P, cen, src = g.misc, g.n, g.P, g.cen, g.src
+            if scored:
+                shares, total = integration.shares(g.group)
+                acc = ring.zeroed(g.k, total)
+                o_shares = share_at(g.group, g.o_tail)
             cen64 = cen[:2 * P].view(P, 2).long()            # the label kernels take `center_coordinates` as int64
             box_off, boxes = misc[g.o_tail:], misc[g.o_tail + n + 1:]
             if on_batch is not None:
@@ -2359,5 +2565,15 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
                 if on_batch is not None:
                     emit(cen_h[b0:b0 + Pb], labels_t, logits, lambda: egs_h[b0:b0 + Pb])
                 add_pr_histograms(logits, labels_t, hist, classes)
+                if scored:
+                    integration.add_batch(eng, logits, raw, labels_t, cen, src, b0, ptr(misc), n, ptr(misc, o_shares),
+                                          ptr(acc), ptr(acc, total))
             flow.feed.computed()
+            if scored:
+                download = ring.download(g.k, total)
+                if pending is not None:
+                    take(*pending)
+                pending = (g.group, shares, download)
+        if pending is not None:
+            take(*pending)
     return done()

@@ -583,6 +583,12 @@ int crimac_eval_crop_origins(const int* centres, int P, int ph, int pw, int H, i
  *   echogram, and the rule "centre row = H / 2 when H <= ph" goes by that echogram's H. */
 int crimac_gather_eval_crops_multi(const crimac_memm_desc* descs, int n_desc, const int* src, int C, const int* centres,
                                    int P, int ph, int pw, float* data_out, short* labels_out, void* stream);
+/* crimac_eval_crop_origins_multi: where crimac_gather_eval_crops_multi places its crops, by the same device function:
+ *   crimac_eval_crop_origins, flavour 1, with H = the n_range of descs[src[p]] (only n_range is read), so the centre row
+ *   H / 2 of a water column not deeper than the patch goes by the patch's own echogram.  origins [P][2] int32 lie in that
+ *   echogram's coordinates; the row of a patch whose src lies outside [0, n_desc) is not written. */
+int crimac_eval_crop_origins_multi(const crimac_memm_desc* descs, int n_desc, const int* src, const int* centres, int P,
+                                   int ph, int pw, int* origins, void* stream);
 /* crimac_gather_patches_memm_labels without metadata planes (flags 0, db_scaled 0), every storage type: the data crop of
  *   patch p from descs[src[p]], the border rule by patch_labels [P][ph][pw] (the batch's transformed labels). */
 int crimac_gather_patches_memm_labels_multi(int prec, const crimac_memm_desc* descs, int n_desc, const int* src, int C,
@@ -919,6 +925,26 @@ int crimac_integrate_confusion(const float* logits, int ncls, const float* raw, 
                                const int* origins, int P, int ph, int pw, int n_range, long ping_bin, int range_bin,
                                long n_pb_total, float thr_sandeel, float thr_other, int mode, double* acc, long long* cnt,
                                void* scratch, long scratch_bytes, void* stream);
+/* crimac_integrate_confusion for an evaluation batch packed from SEVERAL memmap echograms
+ * (tiled_inference.evaluate_echograms_memm with a ScoredIntegrationSet).  logits, raw, labels, C, channel, P, ph, pw, the
+ * thresholds, mode, ping_bin, range_bin and the scratch as above -- the same pixel rule, softmax and weights, by the same
+ * kernel body -- and instead of n_range / n_pb_total:
+ *   descs [n_desc] (crimac_memm_desc; only n_range is read), src int32 [P]: patch p belongs to echogram src[p]; a patch
+ *     whose src lies outside [0, n_desc) does no work: nothing is read for it, no slot and no output is written.
+ *   origins int32 [P][2]: the (row, ping) of pixel (0, 0) of each patch in ITS OWN echogram, as
+ *     crimac_eval_crop_origins_multi states them.  Two patches of different echograms may have the same origin.
+ *   shares int64 [n_desc][2] = (first, n_pb) per echogram: its accumulators are the [3][3][n_pb][n_rb] block that starts at
+ *     word `first` of acc and of cnt, n_rb = ceil(n_range / range_bin); a pixel counts when its position lies in [0, n_range) x
+ *     [0, n_pb * ping_bin) of its echogram.  The caller lays the blocks out without overlap; nothing is written between them.
+ *   acc fp64 / cnt int64: ONE flat buffer each for the whole group; both accumulate (caller zeroes).
+ * No atomics; the owner of a cell is the first patch of the batch WITH THE SAME src whose window holds it, and it adds the
+ * slots of the patches with that src in patch order.  Hence one launch gives every echogram, bit for bit, what one
+ * crimac_integrate_confusion launch over that echogram's patches of the batch, in batch order, would have given it. */
+int crimac_integrate_confusion_multi(const float* logits, int ncls, const float* raw, int C, int channel,
+                                     const short* labels, const int* origins, const crimac_memm_desc* descs, int n_desc,
+                                     const int* src, const long long* shares, int P, int ph, int pw, long ping_bin,
+                                     int range_bin, float thr_sandeel, float thr_other, int mode, double* acc,
+                                     long long* cnt, void* scratch, long scratch_bytes, void* stream);
 
 /* ---- measurement support (bench.py only, not on the product path) --------------------------- */
 
