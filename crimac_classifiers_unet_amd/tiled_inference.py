@@ -1051,6 +1051,31 @@ def integration_result(sv_sum, pixels, spec, n_pings, n_range):
     return res
 
 
+def group_shares(group, spec, planes):
+    """The layout of a packed group's flat accumulators by a bound ``spec``: ``([(first word, (n_pb, range bins or
+    layers))] per record, words)`` -- the echograms' blocks of ``planes`` cells each (3: ``[3, n_pb, n_rb]``, 9: the scored
+    ``[3, 3, n_pb, n_rb]``) one after the other."""
+    shares, total = [], 0
+    for r in group:
+        shape = spec.bins(r.n_pings, r.n_range)
+        shares.append((total, shape))
+        total += planes * shape[0] * shape[1]
+    return shares, total
+
+
+def group_results(group, shares, sums, counts, spec, planes):
+    """The inverse of ``group_shares``: ``(echogram, integration_result)`` per record from a group's downloaded flat
+    accumulators (numpy; copied, the pinned buffer is used again); 9 planes: with the ``"annotated"`` classes."""
+    lead = (3,) if planes == 3 else (3, 3)
+    for r, (at, shape) in zip(group, shares):
+        n = planes * shape[0] * shape[1]
+        res = integration_result(sums[at:at + n].reshape(*lead, *shape).copy(), counts[at:at + n].reshape(*lead, *shape).copy(),
+                                 spec, r.n_pings, r.n_range)
+        if planes == 9:
+            res["annotated"] = ANNOTATED_CLASSES
+        yield r.echogram, res
+
+
 def integrate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, spec, start_ping=0,
                      labels_available=True, predict_fn=None, stats=None):
     """Echo integration by predicted class over one zarr survey: ``predict_survey``'s chunk feed, staging and upload
@@ -1121,6 +1146,28 @@ class _ScoredHolder:
                              "the annotated classes (background, sandeel, other) are those of a 3-class model")
         return spec.bind(frequencies)
 
+    def _confusion_batches(self, engine, logits, raw, labels_t, hint=""):
+        """The operands of an ``add_batch`` checked at the call, then lazily ``(first patch, patches, origins int32 [n][2],
+        scratch)`` of every sub-batch of at most ``CONFUSION_MAX_PATCHES``: the holder launches its two kernels on each."""
+        name = type(self).__name__
+        P, _, ph, pw = logits.shape
+        C = raw.shape[1]
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or tuple(raw.shape) != (P, C, ph, pw) \
+                or tuple(labels_t.shape) != (P, ph, pw) or labels_t.dtype != torch.int16 or not labels_t.is_contiguous():
+            raise ValueError(f"{name}: logits {logits.dtype} {tuple(logits.shape)}, raw {tuple(raw.shape)}, labels "
+                             f"{labels_t.dtype} {tuple(labels_t.shape)}: contiguous fp32 [P, 3, H, W], fp32 [P, C, H, W], "
+                             "int16 [P, H, W]")
+        spec = self.spec
+        if spec.channel is None or not 0 <= spec.channel < C:
+            raise ValueError(f"{name}: channel {spec.channel} of {C} data planes{hint}")
+
+        def batches():
+            for b0 in range(0, P, CONFUSION_MAX_PATCHES):
+                n = min(CONFUSION_MAX_PATCHES, P - b0)
+                yield b0, n, engine._buf("confusion.origins", (n, 2), torch.int32), engine._buf(
+                    "confusion.scratch", (confusion_scratch_bytes(n, ph, pw, spec.ping_bin, spec.range_bin) // 8,), torch.float64)
+        return batches()
+
     @staticmethod
     def _class(k):
         k = {"sandeel": 1, "other": 2}.get(k, k)
@@ -1178,23 +1225,11 @@ class ScoredIntegration(_ScoredHolder):
         restates.  Launches on the current stream; nothing comes back."""
         if self.acc is None:
             raise ValueError("ScoredIntegration: begin() first (the evaluation flows do)")
-        P, ncls, ph, pw = logits.shape
-        C = raw.shape[1]
-        if logits.dtype != torch.float32 or not logits.is_contiguous() or tuple(raw.shape) != (P, C, ph, pw) \
-                or tuple(labels_t.shape) != (P, ph, pw) or labels_t.dtype != torch.int16 or not labels_t.is_contiguous():
-            raise ValueError(f"ScoredIntegration: logits {logits.dtype} {tuple(logits.shape)}, raw {tuple(raw.shape)}, labels "
-                             f"{labels_t.dtype} {tuple(labels_t.shape)}: contiguous fp32 [P, 3, H, W], fp32 [P, C, H, W], "
-                             "int16 [P, H, W]")
-        if not 0 <= self.spec.channel < C:
-            raise ValueError(f"ScoredIntegration: channel {self.spec.channel} of {C} data planes")
-        spec = self.spec
+        batches = self._confusion_batches(engine, logits, raw, labels_t)
+        (_, ncls, ph, pw), C, spec = logits.shape, raw.shape[1], self.spec
         centres = centres.contiguous()
         with torch.cuda.device(logits.device):
-            for b0 in range(0, P, CONFUSION_MAX_PATCHES):
-                n = min(CONFUSION_MAX_PATCHES, P - b0)
-                origins = engine._buf("confusion.origins", (n, 2), torch.int32)
-                scratch = engine._buf("confusion.scratch",
-                                      (confusion_scratch_bytes(n, ph, pw, spec.ping_bin, spec.range_bin) // 8,), torch.float64)
+            for b0, n, origins, scratch in batches:
                 call("crimac_eval_crop_origins", ptr(centres[b0:b0 + n]), n, ph, pw, n_range, 1 if memm else 0, ptr(origins))
                 call("crimac_integrate_confusion", ptr(logits[b0:b0 + n]), ncls, ptr(raw[b0:b0 + n]), C, spec.channel,
                      ptr(labels_t[b0:b0 + n]), ptr(origins), n, ph, pw, self.n_range, spec.ping_bin, spec.range_bin,
@@ -1259,14 +1294,8 @@ class ScoredIntegrationSet(_ScoredHolder):
         return self
 
     def shares(self, group):
-        """The layout of a packed group's flat accumulators: ``([(first word, (n_pb, n_rb))] per record, words)`` -- the
-        ``[3, 3, n_pb, n_rb]`` blocks of the echograms one after the other."""
-        shares, total = [], 0
-        for r in group:
-            shape = self.spec.bins(r.n_pings, r.n_range)
-            shares.append((total, shape))
-            total += 9 * shape[0] * shape[1]
-        return shares, total
+        """``group_shares`` of a packed group's flat accumulators: the echograms' ``[3, 3, n_pb, n_rb]`` blocks."""
+        return group_shares(group, self.spec, 9)
 
     def add_batch(self, engine, logits, raw, labels_t, cen, src, at, descs, n_desc, shares, acc, cnt):
         """One packed evaluation batch: ``logits`` fp32 [P, 3, ph, pw], ``raw`` fp32 [P, C, ph, pw], ``labels_t`` int16
@@ -1274,21 +1303,9 @@ class ScoredIntegrationSet(_ScoredHolder):
         src int32 [.] on the GPU, of which the batch is patches ``at`` ...; ``descs`` / ``shares`` / ``acc`` / ``cnt``: device
         pointers (``hip.ptr``) of the group's descriptor table, its share table int64 [n_desc][2] and its flat
         accumulators.  Launches on the current stream; nothing comes back."""
-        P, ncls, ph, pw = logits.shape
-        C = raw.shape[1]
-        if logits.dtype != torch.float32 or not logits.is_contiguous() or tuple(raw.shape) != (P, C, ph, pw) \
-                or tuple(labels_t.shape) != (P, ph, pw) or labels_t.dtype != torch.int16 or not labels_t.is_contiguous():
-            raise ValueError(f"ScoredIntegrationSet: logits {logits.dtype} {tuple(logits.shape)}, raw {tuple(raw.shape)}, "
-                             f"labels {labels_t.dtype} {tuple(labels_t.shape)}: contiguous fp32 [P, 3, H, W], fp32 [P, C, H, "
-                             "W], int16 [P, H, W]")
-        spec = self.spec
-        if spec.channel is None or not 0 <= spec.channel < C:
-            raise ValueError(f"ScoredIntegrationSet: channel {spec.channel} of {C} data planes (begin() binds it)")
-        for b0 in range(0, P, CONFUSION_MAX_PATCHES):
-            n = min(CONFUSION_MAX_PATCHES, P - b0)
-            origins = engine._buf("confusion.origins", (n, 2), torch.int32)
-            scratch = engine._buf("confusion.scratch",
-                                  (confusion_scratch_bytes(n, ph, pw, spec.ping_bin, spec.range_bin) // 8,), torch.float64)
+        batches = self._confusion_batches(engine, logits, raw, labels_t, hint=" (begin() binds it)")
+        (_, ncls, ph, pw), C, spec = logits.shape, raw.shape[1], self.spec
+        for b0, n, origins, scratch in batches:
             call("crimac_eval_crop_origins_multi", descs, n_desc, ptr(src, at + b0), ptr(cen, 2 * (at + b0)), n, ph, pw,
                  ptr(origins))
             call("crimac_integrate_confusion_multi", ptr(logits[b0:b0 + n]), ncls, ptr(raw[b0:b0 + n]), C, spec.channel,
@@ -1303,12 +1320,8 @@ class ScoredIntegrationSet(_ScoredHolder):
 
     def add_group(self, group, shares, sums, counts):
         """The downloaded accumulators of a packed group (numpy, flat, laid out by ``shares``): one result per record."""
-        for r, (at, shape) in zip(group, shares):
-            n = 9 * shape[0] * shape[1]
-            res = integration_result(sums[at:at + n].reshape(3, 3, *shape).copy(), counts[at:at + n].reshape(3, 3, *shape).copy(),
-                                     self.spec, r.n_pings, r.n_range)
-            res["annotated"] = ANNOTATED_CLASSES
-            self.add(r.echogram, res)
+        for echogram, res in group_results(group, shares, sums, counts, self.spec, 9):
+            self.add(echogram, res)
 
     def results(self):
         """``[(echogram, result)]`` in evaluation order (with several ranks: this rank's echograms); every ``result`` is
@@ -1355,37 +1368,45 @@ class ScoredIntegrationSet(_ScoredHolder):
         return self._ratio(per[:, 0], per[:, 1]), float(self._ratio(sv[k, k - 1], sv[:, k - 1].sum()))
 
 
-class _GroupAccumulators:
-    """The accumulators of the packed memm flows that reduce on the GPU: ONE flat fp64 buffer on the device, [sums |
-    counts] of the group at work, and a ring of two pinned buffers with events through which a group's few kilobytes leave
-    without blocking the feed."""
+class _DownloadRing:
+    """How the results of a packed group leave the GPU without blocking the feed: ONE flat buffer on the device for the
+    group at work and two pinned buffers with an event each, group ``k`` in slot ``k & 1`` (``_ordered_groups`` awaits a
+    download right after the next group is enqueued).  ``device`` / ``pinned`` given: the caller's buffers, large enough
+    for every group (the float16 predictions, in the feed's staging cache); otherwise they grow on demand (the fp64
+    accumulators [sums | counts] of the flows that reduce on the GPU, a few kilobytes)."""
 
-    def __init__(self, dev):
-        self.dev, self.words, self.acc = dev, 0, None          # fp64 words of ``acc``: the largest group so far
-        self.pinned, self.events = [None, None], [torch.cuda.Event() for _ in range(2)]
+    def __init__(self, dev, dtype, device=None, pinned=None):
+        self.dev, self.dtype, self.device = dev, dtype, device
+        self.pinned, self.events = pinned or [None, None], [torch.cuda.Event() for _ in range(2)]
 
-    def zeroed(self, k, total):
-        """The device buffer, its first ``2 * total`` words zeroed, for group ``k`` (all-zero bits: 0.0 and 0 alike)."""
-        if 2 * total > self.words:
-            self.words = 2 * total
-            self.acc = torch.empty(self.words, dtype=torch.float64, device=self.dev)
-        if self.pinned[k & 1] is None or self.pinned[k & 1].numel() < 2 * total:
-            self.pinned[k & 1] = torch.empty(self.words, dtype=torch.float64).pin_memory()
-        self.acc[:2 * total].zero_()
-        return self.acc
+    def zeroed(self, k, n):
+        """The device buffer, its first ``n`` elements zeroed, for group ``k`` (all-zero bits: 0.0 and 0 alike)."""
+        if self.device is None or n > self.device.numel():
+            self.device = torch.empty(n, dtype=self.dtype, device=self.dev)
+        if self.pinned[k & 1] is None or self.pinned[k & 1].numel() < n:
+            self.pinned[k & 1] = torch.empty(self.device.numel(), dtype=self.dtype).pin_memory()
+        self.device[:n].zero_()
+        return self.device
 
-    def download(self, k, total):
-        """Enqueue the download of group ``k``; returns what ``arrays`` takes once the next group has been enqueued."""
-        host = self.pinned[k & 1]
-        host[:2 * total].copy_(self.acc[:2 * total], non_blocking=True)
-        self.events[k & 1].record()
-        return host, self.events[k & 1], total
+    def download(self, k, n):
+        """Enqueue the download of the first ``n`` elements for group ``k``; returns the ticket that ``wait`` takes."""
+        host, event = self.pinned[k & 1][:n], self.events[k & 1]
+        host.copy_(self.device[:n], non_blocking=True)
+        event.record()
+        return host, event
 
     @staticmethod
-    def arrays(host, event, total):
-        """(sums float64 [total], counts int64 [total]) of a downloaded group: numpy views of its pinned buffer."""
+    def wait(ticket):
+        """The downloaded elements of a ticket: a view of its pinned buffer, valid until the group after next."""
+        host, event = ticket
         event.synchronize()
-        return host[:total].numpy(), host[total:2 * total].view(torch.int64).numpy()
+        return host
+
+    @classmethod
+    def wait_sums_counts(cls, ticket):
+        """(sums float64 [total], counts int64 [total]) of downloaded accumulators: numpy views of the pinned buffer."""
+        sums, counts = cls.wait(ticket).view(2, -1)
+        return sums.numpy(), counts.view(torch.int64).numpy()
 
 
 # ---- seabed line of a memmap echogram without a stored seabed.npy (Echogram.get_seabed, data_reader.py:433-507) ---------
@@ -1794,9 +1815,30 @@ class _MemmGroupStage:
         feed.main.wait_stream(feed.copy_stream)
 
 
+def _ordered_groups(groups, single, enqueue, take):
+    """The ONE loop of the memm survey flows over ``groups`` (namespaces as ``_MemmSurveyFlow`` stages them): results in
+    input order while the download of group k overlaps the enqueue of group k + 1.  A packed group: ``enqueue(g)``
+    launches everything for it (``feed.computed()`` and the start of its download included) and returns the ticket of its
+    results, or None when nothing comes back; only THEN is the previous ticket taken -- ``take(ticket)``: an iterable of
+    results, which waits for the download.  A solo group (``g.offs is None``, ``g.solo`` = seabed and meta_channels): the
+    ticket that is kept is taken first, then ``single(echogram, seabed, meta_channels)`` runs, in its place in the order.
+    The last ticket is taken at the end.  Yields what ``take`` and ``single`` produce."""
+    pending = None
+    for g in groups:
+        ticket = None if g.offs is None else enqueue(g)
+        if pending is not None:
+            yield from take(pending)
+        pending = ticket
+        if g.offs is None:
+            yield single(g.group[0].echogram, *g.solo)
+    if pending is not None:
+        yield from take(pending)
+
+
 class _MemmSurveyFlow:
-    """What ``predict_echograms_memm`` and ``evaluate_echograms_memm`` share: a memm survey -- many small echograms --
-    moved through ONE ``_ChunkFeed``, forward batches packed across echograms.
+    """What ``predict_echograms_memm``, ``integrate_echograms_memm`` and ``evaluate_echograms_memm`` share: a memm survey
+    -- many small echograms -- moved through ONE ``_ChunkFeed``, forward batches packed across echograms.  Each of them is
+    this flow, its closures ``single`` / ``enqueue`` / ``take`` and one ``run``; the ordering rule: ``_ordered_groups``.
 
     ``echograms``: any iterable of the reference's ``Echogram`` API, consumed lazily (a few groups ahead of the group at
     work).  Consecutive echograms form *groups* (``plan_memm_groups``): a group is closed when its patches reach
@@ -1825,10 +1867,11 @@ class _MemmSurveyFlow:
     ``kwargs``: the other keys of the reference's ``config_args``, accepted and ignored as by the sibling calls; a near
     miss of one of the caller's ``own`` keywords (``difflib.get_close_matches``: ``group_patch``, ``seabeds``, ``stat``
     ...) is refused as a misspelling.  The checks come before anything is read."""
+    KNOBS = ("group_patches", "group_elems", "seabed", "stats", "predict_fn", "meta_channels", "pack_metadata")   # + ``own``
 
     def __init__(self, name, own, kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
                  group_patches, group_elems, stats, skip=None, eval_mode=None, meta_channels=None, pack_metadata=False):
-        _refuse_near_misses(name, kwargs, own)
+        _refuse_near_misses(name, kwargs, self.KNOBS + own)
         _check_survey_seabed(name, seabed, name.replace("echograms", "echogram"))
         if eval_mode not in (None, "all", "region", "trace"):
             raise ValueError(f"eval_mode={eval_mode!r}: 'all', 'region' or 'trace' (batch/transforms.py:87)")
@@ -1847,7 +1890,7 @@ class _MemmSurveyFlow:
         self.early = not eng.lmi and eng.in_channels > self.C            # metadata planes as extra input channels
         self.pack = (eng.lmi or self.early) and bool(pack_metadata)     # ... packed across echograms
         self.alone = (eng.lmi or self.early) and not self.pack          # ... or the per-echogram path
-        self.meta_channels, self.flags = meta_channels, 0
+        self.meta_channels, self.flags, self._ring = meta_channels, 0, None
         if self.pack:
             if not meta_channels and self.early:
                 raise ValueError(f"the model takes {eng.in_channels} input channels for {self.C} frequencies "
@@ -1876,12 +1919,31 @@ class _MemmSurveyFlow:
         return out
 
     def each_alone(self):
-        """This rank's echograms, one per "group", each with the ``seabed`` argument of the single-echogram functions."""
+        """This rank's echograms, each a solo "group" with the ``seabed`` argument of the single-echogram functions."""
         given = self.seabed is None or isinstance(self.seabed, str)
         for eg in shard_memm_groups(self.echograms, self.rank, self.world):
             if self.skip is None or not self.skip(eg):
                 self.stats["fallback_echograms"] += 1
-                yield eg, self.seabed if given else _memm_survey_seabed(eg, self.seabed, self.dev)
+                sb = self.seabed if given else _memm_survey_seabed(eg, self.seabed, self.dev)
+                yield types.SimpleNamespace(offs=None, group=[types.SimpleNamespace(echogram=eg)],
+                                            solo=(sb, self.meta_channels))
+
+    def ring(self, dtype, fixed=False):
+        """The flow's ``_DownloadRing``, made when the first packed group asks for it (there is a group: the staging
+        exists).  ``fixed``: around the staged ``out`` and ``pinned`` buffers of the caller's ``extra()``."""
+        if self._ring is None:
+            bufs = self.feed.bufs
+            self._ring = _DownloadRing(self.dev, dtype, *((bufs["out"], bufs["pinned"]) if fixed else ()))
+        return self._ring
+
+    def run(self, tag, single, enqueue=None, take=None, **staging):
+        """The flow: ``_ordered_groups`` over this rank's groups with the caller's three closures.  ``staging``: what
+        ``staged`` takes; a flow that goes ``alone`` stages nothing and every echogram is a solo group."""
+        if self.alone:
+            yield from _ordered_groups(self.each_alone(), single, enqueue, take)
+            return
+        with self.staged(tag, **staging) as groups:
+            yield from _ordered_groups(groups, single, enqueue, take)
 
     def batches(self, P):
         """``(first patch, patches)`` of every forward batch of a group of ``P`` patches."""
@@ -1890,18 +1952,29 @@ class _MemmSurveyFlow:
             self.stats["batches"].append(Pb)
             yield b0, Pb
 
+    def gather_input(self, g, b0, Pb, labels_t=None):
+        """The network input ``tiled.x`` of the batch at ``b0`` of staged group ``g``; ``labels_t`` (int16 [Pb, ph, pw],
+        ``eval_mode`` 'region' / 'trace'): the transformed labels the data are masked by."""
+        eng, C, ph, pw = self.eng, self.C, self.ph, self.pw
+        x = eng._buf("tiled.x", (Pb * ph * pw, 16))
+        lab = None if labels_t is None else ptr(labels_t)
+        if self.pack and self.early:
+            call("crimac_gather_patches_memm_meta_multi", eng.prec, ptr(g.misc), ptr(g.meta), g.n, ptr(g.src, b0), C,
+                 ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16, lab, 1, self.flags)
+        elif labels_t is not None:
+            call("crimac_gather_patches_memm_labels_multi", eng.prec, ptr(g.misc), g.n, ptr(g.src, b0), C,
+                 ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16, lab)
+        else:
+            call("crimac_gather_patches_memm_multi", eng.prec, ptr(g.misc), g.n, ptr(g.src, b0), C,
+                 ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16)
+        return x
+
     def predict_group(self, g, predict_fn):
         """The forward batches of staged group ``g``: gather, predict, scatter into the float16 predictions the group's
         descriptors point at (``staged(out=...)``, zeroed by the caller)."""
-        eng, C, ph, pw = self.eng, self.C, self.ph, self.pw
+        eng, ph, pw = self.eng, self.ph, self.pw
         for b0, Pb in self.batches(g.P):
-            x = eng._buf("tiled.x", (Pb * ph * pw, 16))
-            if self.pack and self.early:
-                call("crimac_gather_patches_memm_meta_multi", eng.prec, ptr(g.misc), ptr(g.meta), g.n, ptr(g.src, b0), C,
-                     ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16, None, 1, self.flags)
-            else:
-                call("crimac_gather_patches_memm_multi", eng.prec, ptr(g.misc), g.n, ptr(g.src, b0), C,
-                     ptr(g.cen, 2 * b0), Pb, ph, pw, ptr(x), 16)
+            x = self.gather_input(g, b0, Pb)
             if predict_fn is not None:
                 probs = predict_fn(x, Pb, ph, pw)
             elif eng.lmi:
@@ -1915,7 +1988,7 @@ class _MemmSurveyFlow:
     def staged(self, tag, record=_MemmRecord, extra=None, out=None, tail=None):
         """Plans this rank's groups; inside ``with``: an iterator that stages them one by one and yields each as a
         namespace -- ``k``, ``group`` (the records), ``offs`` (the pixel offset of every echogram; None: ONE echogram too
-        large for the staging, nothing staged, the caller takes the per-echogram path), ``total`` (pixels), ``n`` / ``P``
+        large for the staging, nothing staged: it takes the per-echogram path with ``solo``), ``total`` (pixels), ``n`` / ``P``
         (echograms / patches), ``misc`` (the int32 staging) with its views ``cen`` [P][2] and ``src`` [P], ``o_tail``
         (where the caller's tail starts), ``meta`` (packed metadata: the 64-bit staging, the table first).  The caller enqueues the group's ``batches(P)`` and then calls
         ``feed.computed()`` (done already for a group too large).  Nothing is allocated for an empty plan.
@@ -1953,6 +2026,7 @@ class _MemmSurveyFlow:
             if offs is None:                         # the per-echogram path, in its place in the order
                 feed.computed()
                 self.stats["solo_echograms"] += 1
+                g.solo = self.solo(group[0])
             else:
                 g.n, g.P = len(group), sum(len(r.grid) for r in group)
                 stage.transpose(feed, k, d, group, offs)         # to the ping-major layout of the gather kernels
@@ -1972,57 +2046,35 @@ def predict_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_
     Groups, batches, ``seabed``, metadata models and ``pack_metadata``, ``skip`` (``save_predictions_memm``'s resume rule),
     ``stats`` and ``kwargs``: ``_MemmSurveyFlow``.  Per batch ``crimac_gather_patches_memm_multi`` (packed metadata input
     channels: ``crimac_gather_patches_memm_meta_multi``) -> forward (packed late injection: with the planes of
-    ``crimac_meta_planes_multi``) -> ``crimac_scatter_patches_multi``; the float16 results of a group leave through a non-blocking download into a ring of
-    two pinned buffers."""
-    flow = _MemmSurveyFlow("predict_echograms_memm",
-                           ("group_patches", "group_elems", "seabed", "skip", "stats", "predict_fn", "meta_channels",
-                            "pack_metadata"),
-                           kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
-                           group_patches, group_elems, stats, skip=skip, meta_channels=meta_channels,
-                           pack_metadata=pack_metadata)
-    cap = flow.cap
+    ``crimac_meta_planes_multi``) -> ``crimac_scatter_patches_multi``; the float16 results of a group leave through the
+    flow's download ring, around buffers of the staging cache."""
+    flow = _MemmSurveyFlow("predict_echograms_memm", ("skip",), kwargs, echograms, segpipe, patch_size, patch_overlap,
+                           batch_size, predict_fn, seabed, group_patches, group_elems, stats, skip=skip,
+                           meta_channels=meta_channels, pack_metadata=pack_metadata)
 
     def single(eg, sb, meta):            # the per-echogram path
         return eg, predict_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, predict_fn=predict_fn,
                                          meta_channels=meta, seabed=sb)
 
-    if flow.alone:
-        for eg, sb in flow.each_alone():
-            yield single(eg, sb, meta_channels)
-        return
+    def extra():            # the group's predictions, the pinned buffers of the download ring
+        return dict(out=torch.empty(2 * flow.cap, dtype=torch.float16, device=flow.dev),
+                    pinned=[torch.empty(2 * flow.cap, dtype=torch.float16).pin_memory() for _ in range(2)])
 
-    def extra():            # the group's predictions, the result ring
-        return dict(out=torch.empty(2 * cap, dtype=torch.float16, device=flow.dev),
-                    pinned=[torch.empty(2 * cap, dtype=torch.float16).pin_memory() for _ in range(2)])
+    def enqueue(g):
+        ring = flow.ring(torch.float16, fixed=True)
+        ring.zeroed(g.k, 2 * g.total)
+        flow.predict_group(g, predict_fn)
+        flow.feed.computed()
+        return g.group, g.offs, ring.download(g.k, 2 * g.total)
 
-    def take(group, offs, ring):            # the group whose download went into pinned[ring]
-        events[ring].synchronize()
+    def take(ticket):
+        group, offs, download = ticket
+        host = _DownloadRing.wait(download)
         for r, off in zip(group, offs):
-            res = pinned[ring][2 * off:2 * (off + r.pixels)].view(2, r.n_range, r.n_pings)
+            res = host[2 * off:2 * (off + r.pixels)].view(2, r.n_range, r.n_pings)
             yield r.echogram, res.numpy().astype(np.float64)
 
-    with flow.staged("memm", extra=extra, out="out") as groups:
-        pending = None
-        for g in groups:
-            if g.k == 0:                             # (there is a group: the staging exists)
-                pinned, out = flow.feed.bufs["pinned"], flow.feed.bufs["out"]
-                events = [torch.cuda.Event() for _ in range(2)]
-            if g.offs is None:
-                if pending is not None:
-                    yield from take(*pending)
-                    pending = None
-                yield single(g.group[0].echogram, *flow.solo(g.group[0]))
-                continue
-            out[:2 * g.total].zero_()
-            flow.predict_group(g, predict_fn)
-            flow.feed.computed()
-            pinned[g.k & 1][:2 * g.total].copy_(out[:2 * g.total], non_blocking=True)
-            events[g.k & 1].record()
-            if pending is not None:
-                yield from take(*pending)
-            pending = (g.group, g.offs, g.k & 1)
-        if pending is not None:
-            yield from take(*pending)
+    yield from flow.run("memm", single, enqueue, take, extra=extra, out="out")
 
 
 def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch_size, spec, predict_fn=None,
@@ -2040,15 +2092,10 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
     scatters one integrate launch per echogram (``crimac_integrate_classes`` / ``crimac_integrate_layers`` by ``spec``)
     reads the echogram's float16 predictions, its plane of the transposed staging and its seabed line inside the group's
     uploaded ``misc``, and accumulates into the echogram's share of ONE flat fp64 / int64 buffer; the group's few
-    kilobytes leave through a ring of two pinned buffers with events, nothing in the feed blocks.  Metadata models
-    without ``pack_metadata`` and echograms larger than ``group_elems`` go through ``integrate_echogram_memm``, in their
-    place in the order."""
-    flow = _MemmSurveyFlow("integrate_echograms_memm",
-                           ("spec", "group_patches", "group_elems", "seabed", "skip", "stats", "predict_fn", "meta_channels",
-                            "pack_metadata"),
-                           kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
-                           group_patches, group_elems, stats, skip=skip, meta_channels=meta_channels,
-                           pack_metadata=pack_metadata)
+    kilobytes leave through the flow's download ring, nothing in the feed blocks."""
+    flow = _MemmSurveyFlow("integrate_echograms_memm", ("spec", "skip"), kwargs, echograms, segpipe, patch_size,
+                           patch_overlap, batch_size, predict_fn, seabed, group_patches, group_elems, stats, skip=skip,
+                           meta_channels=meta_channels, pack_metadata=pack_metadata)
     spec = spec.bind(segpipe.frequencies)
     C, W = flow.C, hip.MEMM_DESC_WORDS
 
@@ -2056,54 +2103,29 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
         return eg, integrate_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, spec, predict_fn=predict_fn,
                                            meta_channels=meta, seabed=sb)
 
-    if flow.alone:
-        for eg, sb in flow.each_alone():
-            yield single(eg, sb, meta_channels)
-        return
+    def enqueue(g):
+        ring, out = flow.ring(torch.float64), flow.feed.bufs["out"]
+        shares, total = group_shares(g.group, spec, 3)
+        acc = ring.zeroed(g.k, 2 * total)            # [sums | counts]
+        out[:2 * g.total].zero_()
+        flow.predict_group(g, predict_fn)
+        scratch = integration_scratch(flow.eng, max(s[0] * s[1] for _, s in shares))
+        data_t = flow.feed.bufs["data_t"][g.k & 1]
+        o_sb = 2 * W * g.n + 3 * g.P              # the seabed lines inside ``misc``, one after the other
+        for r, off, (at, shape) in zip(g.group, g.offs, shares):
+            launch_integration(spec, ptr(out, 2 * off), True, r.n_range, r.n_pings,
+                               ptr(data_t, C * off + spec.channel * r.pixels), r.n_pings, 0, 0, shape[0], ptr(acc, at),
+                               ptr(acc, total + at), scratch, seabed=(ptr(g.misc, o_sb), 0, r.n_pings))
+            o_sb += r.n_pings
+        flow.feed.computed()
+        return g.group, shares, ring.download(g.k, 2 * total)
 
-    def take(group, shares, download):            # the group whose accumulators went into a pinned buffer
-        sums, counts = _GroupAccumulators.arrays(*download)
-        for r, (at, shape) in zip(group, shares):
-            n = 3 * shape[0] * shape[1]
-            yield r.echogram, integration_result(sums[at:at + n].reshape(3, *shape).copy(),
-                                                 counts[at:at + n].reshape(3, *shape).copy(), spec, r.n_pings, r.n_range)
+    def take(ticket):
+        group, shares, download = ticket
+        return group_results(group, shares, *_DownloadRing.wait_sums_counts(download), spec, 3)
 
-    with flow.staged("memm_integrate", extra=lambda: dict(out=torch.empty(2 * flow.cap, dtype=torch.float16, device=flow.dev)),
-                     out="out") as groups:
-        pending = None
-        for g in groups:
-            if g.k == 0:                             # (there is a group: the staging exists)
-                out = flow.feed.bufs["out"]
-                ring = _GroupAccumulators(flow.dev)
-            if g.offs is None:
-                if pending is not None:
-                    yield from take(*pending)
-                    pending = None
-                yield single(g.group[0].echogram, *flow.solo(g.group[0]))
-                continue
-            shares, total = [], 0                    # (first word, (n_pb, range bins or layers)) of every echogram
-            for r in g.group:
-                shape = spec.bins(r.n_pings, r.n_range)
-                shares.append((total, shape))
-                total += 3 * shape[0] * shape[1]
-            acc = ring.zeroed(g.k, total)
-            out[:2 * g.total].zero_()
-            flow.predict_group(g, predict_fn)
-            scratch = integration_scratch(flow.eng, max(s[0] * s[1] for _, s in shares))
-            data_t = flow.feed.bufs["data_t"][g.k & 1]
-            o_sb = 2 * W * g.n + 3 * g.P              # the seabed lines inside ``misc``, one after the other
-            for r, off, (at, shape) in zip(g.group, g.offs, shares):
-                launch_integration(spec, ptr(out, 2 * off), True, r.n_range, r.n_pings,
-                                   ptr(data_t, C * off + spec.channel * r.pixels), r.n_pings, 0, 0, shape[0], ptr(acc, at),
-                                   ptr(acc, total + at), scratch, seabed=(ptr(g.misc, o_sb), 0, r.n_pings))
-                o_sb += r.n_pings
-            flow.feed.computed()
-            download = ring.download(g.k, total)
-            if pending is not None:
-                yield from take(*pending)
-            pending = (g.group, shares, download)
-        if pending is not None:
-            yield from take(*pending)
+    yield from flow.run("memm_integrate", single, enqueue, take, out="out",
+                        extra=lambda: dict(out=torch.empty(2 * flow.cap, dtype=torch.float16, device=flow.dev)))
 
 
 def save_predictions_memm(echograms, segpipe, target_dir, patch_size, patch_overlap, batch_size, resume=True,
@@ -2417,10 +2439,9 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
     echogram's boxes count towards its share of the staging.  Nothing but the two histograms comes back.  Per batch:
     ``crimac_gather_eval_crops_multi`` -> ``crimac_labels_test_transform_multi`` (-> ``crimac_labels_extend_mask_multi``
     with the group's box table, ``eval_boxes`` per echogram, for ``eval_mode`` 'region' / 'trace') -> network input
-    (``crimac_gather_patches_memm_multi`` for 'all', ``crimac_gather_patches_memm_labels_multi`` for 'region' / 'trace',
-    as ``ChunkPredictor.evaluate`` chooses; packed metadata input channels: ``crimac_gather_patches_memm_meta_multi``, without
-    / with the transformed labels) -> ``eval_logits`` (packed late injection: with the planes of
-    ``crimac_meta_planes_multi``) -> ``crimac_pr_histogram``.
+    (``_MemmSurveyFlow.gather_input``, for 'region' / 'trace' with the transformed labels, as ``ChunkPredictor.evaluate``
+    chooses) -> ``eval_logits`` (packed late injection: with the planes of ``crimac_meta_planes_multi``) ->
+    ``crimac_pr_histogram``.
 
     ``hist`` (int32 [2, 16384] on the GPU): accumulate into it and return it, no collective (as
     ``evaluate_echogram_memm``); None: ``finish_histograms`` -- with several ranks the histograms are all-reduced once,
@@ -2435,8 +2456,8 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
     for the echogram: the same pixels, the same fp64 terms added in the order of the packed batches.  Per group ONE flat
     fp64 / int64 buffer holds every echogram's ``[3, 3, n_pb, n_rb]`` share (the share table goes up behind the group's
     ``misc``); every internal batch launches ``crimac_eval_crop_origins_multi`` -> ``crimac_integrate_confusion_multi``
-    right after its histograms, on the same stream, and the group's few kilobytes leave through a ring of two pinned
-    buffers with events: nothing in the feed blocks.  Metadata models without ``pack_metadata`` and echograms larger than
+    right after its histograms, on the same stream, and the group's few kilobytes leave through the flow's download
+    ring: nothing in the feed blocks.  Metadata models without ``pack_metadata`` and echograms larger than
     ``group_elems`` are scored by a ``ScoredIntegration`` of their own, in their place in the order.  With several ranks
     ``results()`` holds the rank's own echograms (no collective) and ``totals()`` is sum-reduced once, where the histograms
     are; with ``hist`` given nothing is reduced.  None: no buffer, no launch.  A ``ScoredIntegration`` has ONE ping axis
@@ -2453,11 +2474,9 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
     if classes is not None:            # (the default path asks nothing new of its arguments)
         classes = check_classes(classes, segpipe.model.n_classes, hist)
     flow = _MemmSurveyFlow("evaluate_echograms_memm",
-                           ("group_patches", "group_elems", "seabed", "stats", "predict_fn", "meta_channels", "eval_mode",
-                            "extend_size", "hist", "on_batch", "pack_metadata", "classes", "integration"),
-                           kwargs, echograms, segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed,
-                           group_patches, group_elems, stats, eval_mode=eval_mode, meta_channels=meta_channels,
-                           pack_metadata=pack_metadata)
+                           ("eval_mode", "extend_size", "hist", "on_batch", "classes", "integration"), kwargs, echograms,
+                           segpipe, patch_size, patch_overlap, batch_size, predict_fn, seabed, group_patches, group_elems,
+                           stats, eval_mode=eval_mode, meta_channels=meta_channels, pack_metadata=pack_metadata)
     eng, dev, C, ph, pw = flow.eng, flow.dev, flow.C, flow.ph, flow.pw
     own = hist is None
     if own:
@@ -2484,12 +2503,7 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
             integration.all_reduce(dev)
         return finish_histograms(hist, classes=classes) if own else hist
 
-    if flow.alone:
-        for eg, sb in flow.each_alone():
-            single(eg, sb, meta_channels)
-        return done()
-
-    masked = eval_mode != "all"
+    masked, scored = eval_mode != "all", integration is not None
 
     def tail(group, misc, at):                       # box_off [n + 1] | boxes [total][4]
         off, rows = memm_box_table([r.boxes for r in group])
@@ -2513,67 +2527,48 @@ def evaluate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batch
         misc[at:end].view(np.int64).reshape(-1, 2)[:] = [(first, shape[0]) for first, shape in integration.shares(group)[0]]
         return end
 
-    def take(group, shares, download):               # the group whose accumulators went into a pinned buffer
-        integration.add_group(group, shares, *_GroupAccumulators.arrays(*download))
-
-    scored = integration is not None
-    record = functools.partial(_MemmEvalRecord, eval_mode=eval_mode, extend_size=extend_size, scored=scored)
-    with flow.staged("memm-eval", record=record, tail=tail_scored if scored else tail if masked else None) as groups:
-        pending = None
-        for g in groups:
-            if scored and g.k == 0:                  # (there is a group: the staging exists)
-                ring = _GroupAccumulators(dev)
-            if g.offs is None:
-                if pending is not None:              # (results in evaluation order)
-                    take(*pending)
-                    pending = None
-                single(g.group[0].echogram, *flow.solo(g.group[0]))
-                continue
-            misc, n, P, cen, src = g.misc, g.n, g.P, g.cen, g.src
-            if scored:
-                shares, total = integration.shares(g.group)
-                acc = ring.zeroed(g.k, total)
-                o_shares = share_at(g.group, g.o_tail)
-            cen64 = cen[:2 * P].view(P, 2).long()            # the label kernels take `center_coordinates` as int64
-            box_off, boxes = misc[g.o_tail:], misc[g.o_tail + n + 1:]
+    def enqueue(g):
+        misc, n, P, cen, src = g.misc, g.n, g.P, g.cen, g.src
+        if scored:
+            ring = flow.ring(torch.float64)
+            shares, total = integration.shares(g.group)
+            acc = ring.zeroed(g.k, 2 * total)        # [sums | counts]
+            o_shares = share_at(g.group, g.o_tail)
+        cen64 = cen[:2 * P].view(P, 2).long()            # the label kernels take `center_coordinates` as int64
+        box_off, boxes = misc[g.o_tail:], misc[g.o_tail + n + 1:]
+        if on_batch is not None:
+            cen_h = np.concatenate([np.asarray(r.grid, dtype=np.int32).reshape(-1, 2) for r in g.group])
+            egs_h = [r.echogram for r in g.group for _ in range(len(r.grid))]
+        for b0, Pb in flow.batches(P):
+            raw = eng._buf("eval.raw", (Pb, C, ph, pw), torch.float32)
+            lab = eng._buf("eval.lab", (Pb, ph, pw), torch.int16)
+            call("crimac_gather_eval_crops_multi", ptr(misc), n, ptr(src, b0), C, ptr(cen, 2 * b0), Pb, ph, pw,
+                 ptr(raw), ptr(lab))
+            labels_t = torch.empty((Pb, ph, pw), dtype=torch.int16, device=dev)
+            call("crimac_labels_test_transform_multi", ptr(lab), lab.element_size(), ptr(raw), C - 1, 1e-7, 1e-4,
+                 ptr(cen64, 2 * b0), ptr(misc), n, ptr(src, b0), SEABED_PAD, flow.overlap, ptr(labels_t), Pb, C, ph, pw)
+            if masked:
+                call("crimac_labels_extend_mask_multi", ptr(labels_t), ptr(raw), C, ptr(cen64, 2 * b0), ptr(boxes),
+                     ptr(box_off), n, ptr(src, b0), -1, Pb, ph, pw)
+            x = flow.gather_input(g, b0, Pb, labels_t if masked else None)
+            meta = flow.meta_planes(g, b0, Pb) if eng.lmi and predict_fn is None else None
+            logits = eval_logits(eng, x, Pb, ph, pw, meta=meta, predict_fn=predict_fn, split=True)
             if on_batch is not None:
-                cen_h = np.concatenate([np.asarray(r.grid, dtype=np.int32).reshape(-1, 2) for r in g.group])
-                egs_h = [r.echogram for r in g.group for _ in range(len(r.grid))]
-            for b0, Pb in flow.batches(P):
-                raw = eng._buf("eval.raw", (Pb, C, ph, pw), torch.float32)
-                lab = eng._buf("eval.lab", (Pb, ph, pw), torch.int16)
-                call("crimac_gather_eval_crops_multi", ptr(misc), n, ptr(src, b0), C, ptr(cen, 2 * b0), Pb, ph, pw,
-                     ptr(raw), ptr(lab))
-                labels_t = torch.empty((Pb, ph, pw), dtype=torch.int16, device=dev)
-                call("crimac_labels_test_transform_multi", ptr(lab), lab.element_size(), ptr(raw), C - 1, 1e-7, 1e-4,
-                     ptr(cen64, 2 * b0), ptr(misc), n, ptr(src, b0), SEABED_PAD, flow.overlap, ptr(labels_t), Pb, C, ph, pw)
-                x = eng._buf("tiled.x", (Pb * ph * pw, 16))
-                if masked:
-                    call("crimac_labels_extend_mask_multi", ptr(labels_t), ptr(raw), C, ptr(cen64, 2 * b0), ptr(boxes),
-                         ptr(box_off), n, ptr(src, b0), -1, Pb, ph, pw)
-                if flow.pack and flow.early:
-                    call("crimac_gather_patches_memm_meta_multi", eng.prec, ptr(misc), ptr(g.meta), n, ptr(src, b0), C,
-                         ptr(cen, 2 * b0), Pb, ph, pw, ptr(x), 16, ptr(labels_t) if masked else None, 1, flow.flags)
-                elif masked:
-                    call("crimac_gather_patches_memm_labels_multi", eng.prec, ptr(misc), n, ptr(src, b0), C,
-                         ptr(cen, 2 * b0), Pb, ph, pw, ptr(x), 16, ptr(labels_t))
-                else:
-                    call("crimac_gather_patches_memm_multi", eng.prec, ptr(misc), n, ptr(src, b0), C, ptr(cen, 2 * b0), Pb,
-                         ph, pw, ptr(x), 16)
-                meta = flow.meta_planes(g, b0, Pb) if eng.lmi and predict_fn is None else None
-                logits = eval_logits(eng, x, Pb, ph, pw, meta=meta, predict_fn=predict_fn, split=True)
-                if on_batch is not None:
-                    emit(cen_h[b0:b0 + Pb], labels_t, logits, lambda: egs_h[b0:b0 + Pb])
-                add_pr_histograms(logits, labels_t, hist, classes)
-                if scored:
-                    integration.add_batch(eng, logits, raw, labels_t, cen, src, b0, ptr(misc), n, ptr(misc, o_shares),
-                                          ptr(acc), ptr(acc, total))
-            flow.feed.computed()
+                emit(cen_h[b0:b0 + Pb], labels_t, logits, lambda: egs_h[b0:b0 + Pb])
+            add_pr_histograms(logits, labels_t, hist, classes)
             if scored:
-                download = ring.download(g.k, total)
-                if pending is not None:
-                    take(*pending)
-                pending = (g.group, shares, download)
-        if pending is not None:
-            take(*pending)
+                integration.add_batch(eng, logits, raw, labels_t, cen, src, b0, ptr(misc), n, ptr(misc, o_shares),
+                                      ptr(acc), ptr(acc, total))
+        flow.feed.computed()
+        return (g.group, shares, ring.download(g.k, 2 * total)) if scored else None
+
+    def take(ticket):
+        group, shares, download = ticket
+        integration.add_group(group, shares, *_DownloadRing.wait_sums_counts(download))
+        return ()
+
+    record = functools.partial(_MemmEvalRecord, eval_mode=eval_mode, extend_size=extend_size, scored=scored)
+    for _ in flow.run("memm-eval", single, enqueue, take, record=record,
+                      tail=tail_scored if scored else tail if masked else None):
+        pass
     return done()

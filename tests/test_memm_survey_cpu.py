@@ -3,6 +3,7 @@ rank sharding of groups, the lazy consumption of the echogram iterator, and the 
 import ctypes
 import os
 import re
+import types
 
 import numpy as np
 import pytest
@@ -139,6 +140,59 @@ def test_ranks_that_see_different_files_still_cover_the_survey_exactly_once():
         assert set(flat) | skipped_by_owner == set(names) and not set(flat) & skipped_by_owner      # complete
     # a group of which nothing is left is dropped, not handed out empty
     assert list(ti.iter_memm_groups(survey(), (32, 32), 4, 30, skip=lambda eg: True)) == []
+
+
+def ordered_run(kinds, ticket=True):
+    """_ordered_groups over fake groups ("packed" / "solo" by position k) -> (the event log, the yielded items)."""
+    log = []
+
+    def fake(k, kind):
+        if kind == "solo":
+            return types.SimpleNamespace(k=k, offs=None, group=[types.SimpleNamespace(echogram=k)], solo=("sb", "meta"))
+        return types.SimpleNamespace(k=k, offs=[0], group=[types.SimpleNamespace(echogram=k)])
+
+    def single(echogram, seabed, meta_channels):
+        assert (seabed, meta_channels) == ("sb", "meta")
+        log.append(("single", echogram))
+        return "single", echogram
+
+    def enqueue(g):
+        log.append(("enqueue", g.k))
+        return g.k if ticket else None
+
+    def take(k):
+        log.append(("take", k))
+        yield "take", k
+    return log, list(ti._ordered_groups((fake(k, kind) for k, kind in enumerate(kinds)), single, enqueue, take))
+
+
+def test_the_ordered_group_loop_overlaps_downloads_and_keeps_input_order():
+    """The one ordering rule of the memm survey flows: group k's download is awaited (take) only after group k + 1 has
+    been enqueued, a solo echogram runs in its place -- after the ticket that is kept -- and the last ticket is taken at
+    the end; the results come out in that take / single order."""
+    log, items = ordered_run(["packed", "packed", "solo", "packed", "packed"])
+    assert log == [("enqueue", 0), ("enqueue", 1), ("take", 0), ("take", 1), ("single", 2), ("enqueue", 3), ("enqueue", 4),
+                   ("take", 3), ("take", 4)]
+    assert items == [("take", 0), ("take", 1), ("single", 2), ("take", 3), ("take", 4)]
+    # the loop is lazy: a group is enqueued only when the consumer asks for more
+    seen = []
+    gen = ti._ordered_groups(iter([types.SimpleNamespace(k=0, offs=[0]), types.SimpleNamespace(k=1, offs=[0])]),
+                             None, lambda g: seen.append(g.k) or g.k, lambda k: [k])
+    assert seen == [] and next(gen) == 0 and seen == [0, 1]
+
+
+def test_the_ordered_group_loop_never_takes_when_nothing_comes_back():
+    log, items = ordered_run(["packed", "packed", "solo", "packed"], ticket=False)
+    assert log == [("enqueue", 0), ("enqueue", 1), ("single", 2), ("enqueue", 3)] and items == [("single", 2)]
+
+
+def test_the_ordered_group_loop_of_an_empty_plan_calls_nothing():
+    assert ordered_run([]) == ([], [])
+
+
+def test_the_ordered_group_loop_of_solo_groups_only_neither_enqueues_nor_takes():
+    log, items = ordered_run(["solo", "solo", "solo"])
+    assert log == items == [("single", 0), ("single", 1), ("single", 2)]
 
 
 def test_a_misspelt_knob_is_refused_and_config_keys_are_ignored():
