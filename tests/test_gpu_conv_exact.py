@@ -7,6 +7,8 @@ and partial sum is an integer below 2^24, so fp32 accumulation is exact in any o
 included); outputs are integers of at most 256 in magnitude (or twice such an integer), exact in the bf16 store.  So no
 assertion here has a tolerance: one dropped, duplicated or misplaced product fails ``torch.equal``.  The norm-wise tests of
 tests/test_gpu_kernels.py / test_gpu_h3p.py cannot see such a term at K = 9 * Cin >= 576 in the 16-bit modes.
+tests/test_gpu_narrow_upsample_exact.py holds narrow.hip, upsample.hip and the weight gradients at the narrow channel counts
+to the same bar, with the helpers of this module.
 
 The preconditions (max|ref| <= 256 and bf16-exact, per-channel sum(ref^2) < 2^24 where statistics are fused, |ref| < 2^24
 for weight gradients, per-channel sum|terms| < 2^24 for the BatchNorm-backward sums) are asserted ON THE REFERENCE by the
@@ -92,9 +94,9 @@ def _seed(*key):
     return s
 
 
-def ternary(shape, g):
-    """{-1, 0, +1} with P(+1) = P(-1) = 1/8, float64."""
-    v = torch.randint(0, 8, shape, generator=g)
+def ternary(shape, g, levels=8):
+    """{-1, 0, +1} with P(+1) = P(-1) = 1 / levels (1/8 unless a case thins its operands), float64."""
+    v = torch.randint(0, levels, shape, generator=g)
     return (v == 0).double() - (v == 1).double()
 
 
@@ -107,10 +109,10 @@ def _check_output(ref, stats):
 
 
 @functools.lru_cache(maxsize=None)
-def fwd_case(B, H, W, Ci, Co, scaled=True, stats=True):
+def fwd_case(B, H, W, Ci, Co, scaled=True, stats=True, levels=8):
     """conv3x3 forward: x, w, power-of-two fold scale s, bias b, ref = conv2d(x, w * s, b) in float64."""
     g = torch.Generator().manual_seed(_seed(1, B, H, W, Ci, Co))
-    x, w = ternary((B, Ci, H, W), g), ternary((Co, Ci, 3, 3), g)
+    x, w = ternary((B, Ci, H, W), g, levels), ternary((Co, Ci, 3, 3), g, levels)
     s = (2.0 ** torch.randint(0, 2, (Co,), generator=g)).double() if scaled else torch.ones(Co, dtype=torch.float64)
     b = torch.randint(-3, 4, (Co,), generator=g).double()
     ref = F.conv2d(x, w * s[:, None, None, None], b, padding=1)
