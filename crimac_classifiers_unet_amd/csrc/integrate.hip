@@ -27,9 +27,16 @@
 // boxes of neighbouring layers overlap and those tiles are read once per layer.  S is bounded by the tiles of the whole
 // column, whatever the seabed values: a workgroup whose split finds no tile writes a zero slot.
 //
+// crimac_integrate_edges (the same kernels once more): the ping extent of cell pb is [edges[pb], edges[pb + 1]) of a device
+// table instead of [pb * ping_bin, (pb + 1) * ping_bin).  The workgroup reads its two edges in the prologue (cell_of), where
+// the index depends on blockIdx alone -- two scalar loads per workgroup, nothing per pixel.  The host reads its own copy of
+// the table for the cells the launch touches and their widest extent, which bounds S as ping_bin does.
+//
 // crimac_integrate_confusion (further down, its own two kernels): the sums of an EVALUATION batch -- logits, raw crops and
 // transformed labels in patch layout -- split by the annotated class as well; crimac_integrate_confusion_multi: the same
 // two kernels for a batch packed from several echograms.
+#include <algorithm>
+
 #include "common.h"
 #include "pr_softmax.h"
 
@@ -48,6 +55,8 @@ struct Geom {
   // crimac_integrate_layers: the seabed line from the launch's ping 0 on, the offset of the limit, 0 surface / 1 seabed
   const int* seabed;
   int seabed_offset, reference;
+  // crimac_integrate_edges: cell pb covers global pings [edges[pb], edges[pb + 1]); null: pb * ping_bin
+  const long long* edges;
 };
 
 // the cell's extent in the launch's coordinates (rows; pings relative to pred column 0), clipped to the launch
@@ -57,7 +66,15 @@ __device__ __forceinline__ Cell cell_of(const Geom& g, long cell) {
   const int rb = (int)(cell % g.n_rb);
   Cell c;
   c.r0 = rb * g.range_bin;
-  const long r1 = (long)c.r0 + g.range_bin, p0 = pb * g.ping_bin - g.ping_origin, p1 = p0 + g.ping_bin;
+  const long r1 = (long)c.r0 + g.range_bin;
+  long p0, p1;
+  if (g.edges) {                                                // (uniform: pb comes from blockIdx)
+    p0 = (long)g.edges[pb] - g.ping_origin;
+    p1 = (long)g.edges[pb + 1] - g.ping_origin;
+  } else {
+    p0 = pb * g.ping_bin - g.ping_origin;
+    p1 = p0 + g.ping_bin;
+  }
   c.r1 = (int)(r1 < g.n_range ? r1 : g.n_range);
   c.p0 = p0 > 0 ? p0 : 0;
   c.p1 = p1 < g.n_pings ? p1 : g.n_pings;
@@ -312,8 +329,22 @@ void launch_cells(bool vec_sv, bool vec_pred, unsigned blocks, hipStream_t st, c
 // what crimac_integrate_layers adds to the arguments of crimac_integrate_classes (null: that entry point)
 struct SeabedArgs { const int* line; long first, len; int offset, reference, n_layers; };
 
-// Both entry points: the argument checks, the geometry, the two launches.  `who` names the caller in the messages.
-int integrate(const char* who, const SeabedArgs* sb, const void* pred, int pred_f16, int n_range, long n_pings,
+// what crimac_integrate_edges gives in place of ping_bin (null: the uniform entry points)
+struct EdgeArgs { const long long* dev; const long long* host; };
+
+// The cells [pb0, pb1] of a checked host table that global pings [a, b) touch (pb1 < pb0: none) and their widest extent.
+void cells_touched(const long long* e, long n_pb, long a, long b, long& pb0, long& pb1, long& widest) {
+  const long long* first = std::upper_bound(e, e + n_pb + 1, (long long)a);     // the first edge > a
+  const long long* last = std::lower_bound(e, e + n_pb + 1, (long long)b);      // the first edge >= b
+  pb0 = first == e ? 0 : (long)(first - e) - 1;
+  pb1 = (long)(last - e) - 1;
+  pb1 = pb1 < n_pb - 1 ? pb1 : n_pb - 1;
+  widest = 0;
+  for (long pb = pb0; pb <= pb1; ++pb) widest = e[pb + 1] - e[pb] > widest ? (long)(e[pb + 1] - e[pb]) : widest;
+}
+
+// All three entry points: the argument checks, the geometry, the two launches.  `who` names the caller in the messages.
+int integrate(const char* who, const SeabedArgs* sb, const EdgeArgs* ed, const void* pred, int pred_f16, int n_range, long n_pings,
               const float* sv, long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode, long ping_bin,
               int range_bin, long ping_origin, long n_pb_total, double* acc, long long* cnt, void* scratch,
               long scratch_bytes, void* stream) {
@@ -323,14 +354,29 @@ int integrate(const char* who, const SeabedArgs* sb, const void* pred, int pred_
   CRIMAC_REQUIRE(mode == 0 || mode == 1, "%s: mode %d (0 threshold, 1 probability)", who, mode);
   CRIMAC_REQUIRE(thr_sandeel > 0.f && thr_other > 0.f, "%s: thr = (%g, %g) must be > 0 (pixels the scatter "
                  "left at 0 belong to no class)", who, (double)thr_sandeel, (double)thr_other);
-  CRIMAC_REQUIRE(ping_bin > 0 && range_bin > 0, "%s: ping_bin=%ld, range_bin=%d must be positive", who, ping_bin, range_bin);
+  CRIMAC_REQUIRE((ed || ping_bin > 0) && range_bin > 0, "%s: ping_bin=%ld, range_bin=%d must be positive", who, ping_bin,
+                 range_bin);
   CRIMAC_REQUIRE(ping_bin <= 2147483647L && n_pb_total <= 2147483647L, "%s: ping_bin=%ld, n_pb_total=%ld "
                  "beyond 2^31 - 1", who, ping_bin, n_pb_total);
   CRIMAC_REQUIRE(sv_ping_off >= 0 && sv_ping_off + n_pings <= data_pings, "%s: sv columns [%ld, %ld) outside "
                  "the sv extent of %ld pings", who, sv_ping_off, sv_ping_off + n_pings, data_pings);
-  CRIMAC_REQUIRE(ping_origin >= 0 && n_pb_total > 0 && ping_origin + n_pings <= n_pb_total * ping_bin,
+  CRIMAC_REQUIRE(ping_origin >= 0 && n_pb_total > 0 && (ed || ping_origin + n_pings <= n_pb_total * ping_bin),
                  "%s: pings [%ld, %ld) outside the accumulator's %ld bins of %ld pings", who, ping_origin,
                  ping_origin + n_pings, n_pb_total, ping_bin);
+  long pb0 = 0, pb1 = 0, widest = ping_bin;
+  if (ed) {
+    CRIMAC_REQUIRE(ed->dev && ed->host, "%s: null edge table", who);
+    CRIMAC_REQUIRE(ed->host[0] >= 0, "%s: edges[0]=%lld is negative", who, ed->host[0]);
+    for (long pb = 0; pb < n_pb_total; ++pb) {
+      const long long w = ed->host[pb + 1] - ed->host[pb];      // (both >= 0 here: no overflow)
+      CRIMAC_REQUIRE(w >= 0 && w <= 2147483647LL, "%s: edges[%ld]=%lld, edges[%ld]=%lld: the table must not decrease and "
+                     "no cell is wider than 2^31 - 1 pings", who, pb, ed->host[pb], pb + 1, ed->host[pb + 1]);
+    }
+    cells_touched(ed->host, n_pb_total, ping_origin, ping_origin + n_pings, pb0, pb1, widest);
+  } else {
+    pb0 = ping_origin / ping_bin;
+    pb1 = (ping_origin + n_pings - 1) / ping_bin;
+  }
   const bool layers = sb && sb->reference == 1;
   if (sb) {
     CRIMAC_REQUIRE(sb->line, "%s: null seabed vector", who);
@@ -351,16 +397,18 @@ int integrate(const char* who, const SeabedArgs* sb, const void* pred, int pred_
   g.ping_bin = ping_bin;
   g.ping_origin = ping_origin;
   g.n_pb_total = n_pb_total;
-  g.pb0 = ping_origin / ping_bin;
+  g.pb0 = pb0;
   g.thr0 = thr_sandeel;
   g.thr1 = thr_other;
   g.seabed = sb ? sb->line + sb->first : nullptr;
   g.seabed_offset = sb ? sb->offset : 0;
   g.reference = sb ? sb->reference : 0;
-  const long cells = ((ping_origin + n_pings - 1) / ping_bin - g.pb0 + 1) * g.n_rb;
+  g.edges = ed ? ed->dev : nullptr;
+  if (pb1 < pb0) return CRIMAC_OK;                             // (an edge table none of whose cells the launch touches)
+  const long cells = (pb1 - pb0 + 1) * g.n_rb;
   // tiles of a full cell (its origin may sit up to 3 short of a multiple of 4 in either direction); the row bounding box
   // of a seabed-referenced layer may be the whole column
-  const long span_r = (range_bin < n_range && !layers ? range_bin : n_range) + 3, span_p = (ping_bin < n_pings ? ping_bin : n_pings) + 3;
+  const long span_r = (range_bin < n_range && !layers ? range_bin : n_range) + 3, span_p = (widest < n_pings ? widest : n_pings) + 3;
   const long tiles = ((span_r + kTile - 1) / kTile) * ((span_p + kTile - 1) / kTile);
   const long want = (CRIMAC_INTEGRATE_SPLIT_WGS + cells - 1) / cells;
   g.splits = (int)(want < tiles ? want : tiles);
@@ -660,7 +708,7 @@ extern "C" int crimac_integrate_classes(const void* pred, int pred_f16, int n_ra
                                         long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode,
                                         long ping_bin, int range_bin, long ping_origin, long n_pb_total, double* acc,
                                         long long* cnt, void* scratch, long scratch_bytes, void* stream) {
-  return integrate("integrate_classes", nullptr, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, thr_sandeel,
+  return integrate("integrate_classes", nullptr, nullptr, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, thr_sandeel,
                    thr_other, mode, ping_bin, range_bin, ping_origin, n_pb_total, acc, cnt, scratch, scratch_bytes, stream);
 }
 
@@ -670,6 +718,19 @@ extern "C" int crimac_integrate_layers(const void* pred, int pred_f16, int n_ran
                                        long seabed_first, long seabed_len, int seabed_offset, int reference, int n_layers,
                                        double* acc, long long* cnt, void* scratch, long scratch_bytes, void* stream) {
   const SeabedArgs sb{seabed, seabed_first, seabed_len, seabed_offset, reference, n_layers};
-  return integrate("integrate_layers", &sb, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, thr_sandeel,
+  return integrate("integrate_layers", &sb, nullptr, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, thr_sandeel,
                    thr_other, mode, ping_bin, range_bin, ping_origin, n_pb_total, acc, cnt, scratch, scratch_bytes, stream);
+}
+
+extern "C" int crimac_integrate_edges(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv,
+                                      long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode,
+                                      const long long* edges_dev, const long long* edges_host, int range_bin,
+                                      long ping_origin, long n_pb_total, const int* seabed, long seabed_first,
+                                      long seabed_len, int seabed_offset, int reference, int n_layers, double* acc,
+                                      long long* cnt, void* scratch, long scratch_bytes, void* stream) {
+  const SeabedArgs sb{seabed, seabed_first, seabed_len, seabed_offset, reference, n_layers};
+  const EdgeArgs ed{edges_dev, edges_host};
+  return integrate("integrate_edges", seabed ? &sb : nullptr, &ed, pred, pred_f16, n_range, n_pings, sv, data_pings,
+                   sv_ping_off, thr_sandeel, thr_other, mode, 0, range_bin, ping_origin, n_pb_total, acc, cnt, scratch,
+                   scratch_bytes, stream);
 }

@@ -33,6 +33,7 @@ summed per class and (ping bin x range bin) cell -- or, with a seabed-aware ``In
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import difflib
 import functools
 import inspect
@@ -234,7 +235,8 @@ class ChunkPredictor:
         ``IntegrationSpec``.  Launches on the current stream, after the scatter; nothing comes back.
         A seabed-aware spec (``seabed_offset`` given) runs ``crimac_integrate_layers`` with the chunk's seabed line
         (``_limit_line``: the vector, or the first masked row per ping of a chunk loaded with a 2-D mask); with the seabed
-        reference the accumulators are ``[3, n_pb_total, layers]``."""
+        reference the accumulators are ``[3, n_pb_total, layers]``.  A spec with ``ping_edges`` (a table: ``resolve`` a
+        callable first) runs ``crimac_integrate_edges``; ``n_pb_total`` is then the table's number of cells exactly."""
         if self.wide or self.out is None:
             raise ValueError("ChunkPredictor.integrate: the chunk was loaded for evaluate() (wide=True) and has no predictions")
         if spec.channel is None:
@@ -244,11 +246,12 @@ class ChunkPredictor:
         n_pb, n_rb = spec.bins(self.end_ping, self.n_range)
         want = (3, acc.shape[1], n_rb)
         if acc.dtype != torch.float64 or cnt.dtype != torch.int64 or tuple(acc.shape) != want or tuple(cnt.shape) != want \
-                or acc.shape[1] < n_pb or not acc.is_contiguous() or not cnt.is_contiguous():
+                or acc.shape[1] < n_pb or (spec.ping_edges is not None and acc.shape[1] != n_pb) \
+                or not acc.is_contiguous() or not cnt.is_contiguous():
             raise ValueError(f"ChunkPredictor.integrate: acc float64 / cnt int64, contiguous [3, >= {n_pb}, {n_rb}]; got "
                              f"{acc.dtype} {tuple(acc.shape)}, {cnt.dtype} {tuple(cnt.shape)}")
         n = self.end_ping - self.start_ping
-        cells = ((self.end_ping - 1) // spec.ping_bin - self.start_ping // spec.ping_bin + 1) * n_rb
+        cells = spec.touched(self.start_ping, self.end_ping) * n_rb
         scratch = integration_scratch(self.engine, cells)
         sv = self.data[spec.channel]
         with torch.cuda.device(self.out.device):
@@ -934,15 +937,37 @@ class IntegrationSpec:
     integer): the range axis of the result is ``layers`` bottom layers -- layer l of ping p covers rows
     ``[L[p] - (l + 1) * range_bin, L[p] - l * range_bin)`` clipped to ``[0, n_range)``.  Layer rows are counted FROM THE
     LIMIT, not from the surface: layer 0 touches it, a layer follows the relief inside a ping bin, and rows above the
-    top layer belong to no layer and are dropped."""
+    top layer belong to no layer and are dropped.
+
+    **EDSU** (``crimac_integrate_edges``).  ``ping_edges`` (with ``ping_bin`` None): the ping axis of the cells as an edge
+    table instead of a width -- cell pb covers global pings ``[ping_edges[pb], ping_edges[pb + 1])``, as many ping bins as
+    the table has intervals, whatever the survey's length.  A 1-D integer array, non-negative and non-decreasing (a
+    zero-width cell is legal and stays 0; pings before the first or from the last edge on count nowhere), or a callable
+    ``source -> array`` asked for every reader / echogram that is integrated (``resolve``): a memm survey has one ping
+    axis per echogram.  ``ping_bin_edges`` builds the table from a log-distance or time vector.  Range bins, seabed limit
+    and layers are as above."""
     MODES = ("threshold", "probability")
     REFERENCES = ("surface", "seabed")
 
+    def __new__(cls, *args, **kwargs):
+        # ``ping_edges=`` is the keyword of the EDSU form, a subclass with that one parameter more: the parameter list of
+        # this ``__init__`` stays the uniform grid's, which callers and tests introspect
+        return object.__new__(EdsuIntegrationSpec if cls is IntegrationSpec and "ping_edges" in kwargs else cls)
+
     def __init__(self, ping_bin, range_bin, frequency=None, thresholds=(0.5, 0.5), mode="threshold", channel=None,
                  seabed_offset=None, reference="surface", layers=None):
+        self._setup(ping_bin, range_bin, frequency, thresholds, mode, channel, seabed_offset, reference, layers, None)
+
+    def _setup(self, ping_bin, range_bin, frequency, thresholds, mode, channel, seabed_offset, reference, layers, ping_edges):
         def integer(v):
             return not isinstance(v, bool) and isinstance(v, (int, np.integer))
-        for name, v in (("ping_bin", ping_bin), ("range_bin", range_bin)):
+        if ping_edges is not None:
+            if ping_bin is not None:
+                raise ValueError(f"IntegrationSpec: ping_bin={ping_bin!r} and ping_edges: the ping axis is one or the other "
+                                 "(ping_bin=None with an edge table)")
+            if not callable(ping_edges):
+                ping_edges = self._checked_edges(ping_edges)
+        for name, v in (("ping_bin", ping_bin), ("range_bin", range_bin))[ping_edges is not None:]:
             if not integer(v) or v < 1:
                 raise ValueError(f"IntegrationSpec: {name}={v!r} must be a positive integer")
         if seabed_offset is not None and not (integer(seabed_offset) and abs(int(seabed_offset)) < 2 ** 30):
@@ -969,10 +994,63 @@ class IntegrationSpec:
         if len(thresholds) != 2 or not all(0.0 < t < float("inf") for t in thresholds):
             raise ValueError(f"IntegrationSpec: thresholds={thresholds!r}: two finite numbers > 0 (pixels the scatter left "
                              "at 0 belong to no class)")
-        self.ping_bin, self.range_bin, self.frequency = int(ping_bin), int(range_bin), frequency
+        self.ping_bin, self.range_bin, self.frequency = None if ping_bin is None else int(ping_bin), int(range_bin), frequency
+        self.ping_edges, self._edges_dev = ping_edges, {}
         self.thresholds, self.mode, self.channel = thresholds, mode, channel
         self.seabed_offset = None if seabed_offset is None else int(seabed_offset)
         self.reference, self.layers = reference, None if layers is None else int(layers)
+
+    @staticmethod
+    def _checked_edges(edges):
+        """``edges`` as the contiguous int64 table of the kernel; ValueError unless it is a 1-D integer array of at least
+        two edges, non-negative, non-decreasing, no cell wider than 2^31 - 1 pings."""
+        e = np.asarray(edges)
+        if e.ndim != 1 or e.size < 2 or e.dtype.kind not in "iu":
+            raise ValueError(f"IntegrationSpec: ping_edges is a 1-D integer array of at least two edges (or a callable "
+                             f"source -> array), got {e.dtype} {e.shape}")
+        if e.dtype.kind == "u" and e.size and int(e.max()) >= 2 ** 63:
+            raise ValueError("IntegrationSpec: ping_edges beyond 2^63 - 1")
+        e = np.array(e, dtype=np.int64)                      # (a copy: it is frozen below)
+        if e[0] < 0 or np.any(e[1:] < e[:-1]) or np.any(e[1:] - e[:-1] >= 2 ** 31):
+            raise ValueError("IntegrationSpec: ping_edges must be non-negative and non-decreasing, no cell wider than "
+                             "2^31 - 1 pings")
+        e.setflags(write=False)
+        return e
+
+    def _with(self, channel, frequency, ping_edges):
+        return IntegrationSpec(self.ping_bin, self.range_bin, frequency, self.thresholds, self.mode, channel,
+                               seabed_offset=self.seabed_offset, reference=self.reference, layers=self.layers,
+                               **({} if ping_edges is None else {"ping_edges": ping_edges}))
+
+    def resolve(self, source):
+        """The spec with ``ping_edges`` as a table: a callable is asked for ``source`` (the reader or echogram that is
+        integrated) and its answer checked; a spec with a table, or with ``ping_bin``, is returned as it is."""
+        if not callable(self.ping_edges):
+            return self
+        return self._with(self.channel, self.frequency, self._checked_edges(self.ping_edges(source)))
+
+    def edges_on(self, dev):
+        """The device copy of the edge table on ``dev``, uploaded at the first call (``new_integration`` makes it, before
+        the feed starts) and kept with the spec: never per launch."""
+        if self.ping_edges is None or callable(self.ping_edges):
+            raise ValueError("IntegrationSpec: no edge table (ping_edges is None, or a callable that resolve(source) has "
+                             "not been asked yet)")
+        dev = torch.device(dev)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if dev not in self._edges_dev:
+            self._edges_dev[dev] = torch.from_numpy(self.ping_edges.copy()).to(dev)
+        return self._edges_dev[dev]
+
+    def touched(self, start_ping, end_ping):
+        """How many ping bins global pings [start_ping, end_ping) touch, as the library counts them for the scratch: with
+        a table the first cell that ends after ``start_ping`` to the last that begins before ``end_ping``."""
+        if self.ping_edges is None:
+            return (end_ping - 1) // self.ping_bin - start_ping // self.ping_bin + 1
+        e = self.ping_edges
+        pb0 = max(int(np.searchsorted(e, start_ping, "right")) - 1, 0)
+        pb1 = min(int(np.searchsorted(e, end_ping, "left")) - 1, len(e) - 2)
+        return max(pb1 - pb0 + 1, 0)
 
     @property
     def seabed_aware(self):
@@ -985,21 +1063,34 @@ class IntegrationSpec:
         wanted = (38, 38000) if self.frequency is None else (self.frequency,)
         for f in wanted:
             if float(f) in freqs:
-                return IntegrationSpec(self.ping_bin, self.range_bin, f, self.thresholds, self.mode, freqs.index(float(f)),
-                                       seabed_offset=self.seabed_offset, reference=self.reference, layers=self.layers)
+                return self._with(freqs.index(float(f)), f, self.ping_edges)
         raise ValueError(f"IntegrationSpec: frequency {' / '.join(str(f) for f in wanted)} is not among the model's "
                          f"frequencies {list(frequencies)}")
 
     def bins(self, n_pings, n_range):
         """(ping bins, range bins) that cover global pings [0, n_pings) and rows [0, n_range); with the seabed reference
-        (ping bins, ``layers``)."""
-        n_pb = -(-int(n_pings) // self.ping_bin)
+        (ping bins, ``layers``).  With ``ping_edges`` the ping bins are the table's, whatever ``n_pings``."""
+        if callable(self.ping_edges):
+            raise ValueError("IntegrationSpec: ping_edges is a callable: resolve(source) it first")
+        n_pb = len(self.ping_edges) - 1 if self.ping_edges is not None else -(-int(n_pings) // self.ping_bin)
         return n_pb, self.layers if self.reference == "seabed" else -(-int(n_range) // self.range_bin)
 
 
+class EdsuIntegrationSpec(IntegrationSpec):
+    """What ``IntegrationSpec(None, range_bin, ..., ping_edges=...)`` constructs: the spec whose ping axis is an edge
+    table (or a callable that gives one per source).  Everything else is ``IntegrationSpec``'s."""
+
+    def __init__(self, ping_bin, range_bin, frequency=None, thresholds=(0.5, 0.5), mode="threshold", channel=None,
+                 seabed_offset=None, reference="surface", layers=None, ping_edges=None):
+        self._setup(ping_bin, range_bin, frequency, thresholds, mode, channel, seabed_offset, reference, layers, ping_edges)
+
+
 def new_integration(dev, spec, n_pings, n_range):
-    """Zeroed accumulators of ``ChunkPredictor.integrate`` on ``dev``: (acc float64, cnt int64), both [3, n_pb, n_rb]."""
+    """Zeroed accumulators of ``ChunkPredictor.integrate`` on ``dev``: (acc float64, cnt int64), both [3, n_pb, n_rb].
+    A spec with an edge table: its device copy goes up here (``IntegrationSpec.edges_on``), once per survey."""
     shape = (3, *spec.bins(n_pings, n_range))
+    if spec.ping_edges is not None:
+        spec.edges_on(dev)
     return torch.zeros(shape, dtype=torch.float64, device=dev), torch.zeros(shape, dtype=torch.int64, device=dev)
 
 
@@ -1010,12 +1101,31 @@ def integration_scratch(engine, cells):
 
 
 def launch_integration(spec, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, ping_origin, n_pb_total, acc,
-                       cnt, scratch, seabed=None):
+                       cnt, scratch, seabed=None, edges=None):
     """One integrate launch by a bound ``spec``: ``crimac_integrate_classes``, or -- a seabed-aware spec --
     ``crimac_integrate_layers`` with ``seabed`` = (pointer to an int32 line, index of pred's column 0 in it, its length).
-    ``pred`` / ``sv`` / ``acc`` / ``cnt``: device pointers (``hip.ptr``); ``scratch``: a float64 tensor."""
+    ``pred`` / ``sv`` / ``acc`` / ``cnt``: device pointers (``hip.ptr``); ``scratch``: a float64 tensor.
+    A spec with an edge table runs ``crimac_integrate_edges`` (with or without ``seabed``); ``edges``: the device pointer
+    of a copy of ``spec.ping_edges`` the caller has uploaded with other tables (default: ``spec.edges_on`` the current
+    device); ``n_pb_total`` must be the table's intervals."""
+    mode = IntegrationSpec.MODES.index(spec.mode)
+    if spec.ping_edges is not None:
+        host = spec.ping_edges
+        if callable(host):
+            raise ValueError("launch_integration: ping_edges is a callable: IntegrationSpec.resolve(source) it first")
+        if n_pb_total != len(host) - 1:
+            raise ValueError(f"launch_integration: n_pb_total={n_pb_total} for an edge table of {len(host) - 1} cells")
+        if edges is None:
+            edges = ptr(spec.edges_on(torch.device("cuda", torch.cuda.current_device())))
+        sb = seabed if spec.seabed_aware else (None, 0, 0)
+        tail = (acc, cnt, ptr(scratch), scratch.numel() * 8)
+        call("crimac_integrate_edges", pred, 1 if pred_f16 else 0, n_range, n_pings, sv, data_pings, sv_ping_off,
+             spec.thresholds[0], spec.thresholds[1], mode, edges, ctypes.c_void_p(host.ctypes.data), spec.range_bin,
+             ping_origin, n_pb_total, *sb, spec.seabed_offset or 0, IntegrationSpec.REFERENCES.index(spec.reference),
+             spec.layers or 0, *tail)
+        return
     head = (pred, 1 if pred_f16 else 0, n_range, n_pings, sv, data_pings, sv_ping_off, spec.thresholds[0],
-            spec.thresholds[1], IntegrationSpec.MODES.index(spec.mode), spec.ping_bin, spec.range_bin, ping_origin, n_pb_total)
+            spec.thresholds[1], mode, spec.ping_bin, spec.range_bin, ping_origin, n_pb_total)
     tail = (acc, cnt, ptr(scratch), scratch.numel() * 8)
     if not spec.seabed_aware:
         call("crimac_integrate_classes", *head, *tail)
@@ -1039,11 +1149,12 @@ def finish_integration(acc, cnt, spec, n_pings, n_range, all_reduce=True):
 
 
 def integration_result(sv_sum, pixels, spec, n_pings, n_range):
-    """The result dict of ``finish_integration`` around downloaded accumulators (numpy ``[3, n_pb, n_rb]``)."""
+    """The result dict of ``finish_integration`` around downloaded accumulators (numpy ``[3, n_pb, n_rb]``).  With
+    ``spec.ping_edges`` the result's ``ping_edges`` are the table clipped to ``n_pings``."""
     n_pb, n_rb = spec.bins(n_pings, n_range)
     edges = np.arange(n_rb + 1, dtype=np.int64) * spec.range_bin
-    res = {"sv_sum": sv_sum, "pixels": pixels,
-           "ping_edges": np.minimum(np.arange(n_pb + 1, dtype=np.int64) * spec.ping_bin, int(n_pings)),
+    ping_edges = np.arange(n_pb + 1, dtype=np.int64) * spec.ping_bin if spec.ping_edges is None else spec.ping_edges
+    res = {"sv_sum": sv_sum, "pixels": pixels, "ping_edges": np.minimum(ping_edges, int(n_pings)),
            "range_edges": edges if spec.reference == "seabed" else np.minimum(edges, int(n_range)),
            "classes": INTEGRATION_CLASSES}
     if spec.seabed_aware:
@@ -1054,10 +1165,11 @@ def integration_result(sv_sum, pixels, spec, n_pings, n_range):
 def group_shares(group, spec, planes):
     """The layout of a packed group's flat accumulators by a bound ``spec``: ``([(first word, (n_pb, range bins or
     layers))] per record, words)`` -- the echograms' blocks of ``planes`` cells each (3: ``[3, n_pb, n_rb]``, 9: the scored
-    ``[3, 3, n_pb, n_rb]``) one after the other."""
+    ``[3, 3, n_pb, n_rb]``) one after the other.  A record that carries its own spec (``_MemmEdgeRecord``: the spec with
+    the echogram's edge table) goes by that one."""
     shares, total = [], 0
     for r in group:
-        shape = spec.bins(r.n_pings, r.n_range)
+        shape = getattr(r, "spec", spec).bins(r.n_pings, r.n_range)
         shares.append((total, shape))
         total += planes * shape[0] * shape[1]
     return shares, total
@@ -1070,7 +1182,7 @@ def group_results(group, shares, sums, counts, spec, planes):
     for r, (at, shape) in zip(group, shares):
         n = planes * shape[0] * shape[1]
         res = integration_result(sums[at:at + n].reshape(*lead, *shape).copy(), counts[at:at + n].reshape(*lead, *shape).copy(),
-                                 spec, r.n_pings, r.n_range)
+                                 getattr(r, "spec", spec), r.n_pings, r.n_range)
         if planes == 9:
             res["annotated"] = ANNOTATED_CLASSES
         yield r.echogram, res
@@ -1088,12 +1200,14 @@ def integrate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, pre
     plane; pings before ``start_ping`` are not visited and count nowhere.  Returns ``{"sv_sum": float64 [3, n_pb, n_rb] (sum of linear sv: sandeel, other, all
     counted pixels), "pixels": int64 [3, n_pb, n_rb], "ping_edges", "range_edges", "classes"}`` (``finish_integration``);
     ``nasc`` turns ``sv_sum`` into area backscattering.  Bins count global pings from 0 whatever ``start_ping``.
+    A spec with ``ping_edges`` (EDSU cells; a callable is asked for ``reader``) integrates on the table's cells: its device
+    copy is uploaded once, before the feed starts, and ``"ping_edges"`` of the result is the table clipped to the survey.
     With torch.distributed initialised the chunks are dealt to the ranks as in ``predict_survey(shard="chunk")`` and the
     accumulators all-reduced once at the end: every rank must call it and every rank returns the survey's result.  Sums
     are fp64 in a fixed order: bit-reproducible for a given chunking and rank count, whatever ``batch_size``."""
     flow = _SurveyChunks("integrate_survey", reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings,
                          start_ping, labels_available, True, stats, predict_fn, share_patches=False)
-    spec = spec.bind(segpipe.frequencies)
+    spec = spec.bind(segpipe.frequencies).resolve(reader)
     acc, cnt = new_integration(flow.dev, spec, flow.n_pings, flow.n_range)
     rank, world = parallel.rank_world()
     if world > 1:
@@ -1109,8 +1223,40 @@ def integrate_survey(reader, segpipe, patch_size, patch_overlap, batch_size, pre
 def nasc(result, range_step_m):
     """Nautical area scattering coefficient per cell and class from an integration result: ``4 pi 1852^2 * range_step_m *
     sv_sum`` (m^2 nmi^-2 summed over the cell's pings; divide by the pings of a cell, ``np.diff(result["ping_edges"])``,
-    for the cell's mean NASC).  Assumes a UNIFORM range grid: every sample is ``range_step_m`` metres thick."""
+    for the cell's mean NASC: ``mean_nasc``).  Assumes a UNIFORM range grid: every sample is ``range_step_m`` metres thick."""
     return 4.0 * np.pi * 1852.0 ** 2 * float(range_step_m) * np.asarray(result["sv_sum"], dtype=np.float64)
+
+
+def mean_nasc(result, range_step_m):
+    """The cell's MEAN NASC, what a survey reports per EDSU: ``nasc`` divided by the pings of the cell,
+    ``np.diff(result["ping_edges"])``; NaN for a cell without pings (a zero-width cell of an edge table)."""
+    pings = np.diff(np.asarray(result["ping_edges"])).astype(np.float64)[:, None]
+    total = nasc(result, range_step_m)
+    return np.divide(total, pings, out=np.full(total.shape, np.nan), where=pings > 0)
+
+
+def ping_bin_edges(track, step, origin=None):
+    """The edge table of EDSU cells (``IntegrationSpec(ping_edges=...)``) from a per-ping ``track`` -- the log distance in
+    nmi, the reader's ``time_vector``, anything finite and non-decreasing: cell k holds the pings whose track value lies
+    in ``[origin + k * step, origin + (k + 1) * step)``, ``origin`` defaulting to ``track[0]``.  ``edges[k] =
+    searchsorted(track, origin + k * step, 'left')`` for k = 0 .. K with K = floor((track[-1] - origin) / step) + 1; the
+    last edge is ``len(track)``.  A gap in the track gives zero-width cells, repeated values stay in one cell, pings
+    before a later ``origin`` lie before the first edge and count nowhere.  ValueError: an empty, non-finite or
+    decreasing track, ``step`` not > 0, an ``origin`` that is not finite or lies beyond the track's end."""
+    t = np.asarray(track, dtype=np.float64)
+    if t.ndim != 1 or t.size == 0 or not np.all(np.isfinite(t)) or np.any(t[1:] < t[:-1]):
+        raise ValueError(f"ping_bin_edges: track is a finite, non-decreasing vector with at least one ping, got shape {t.shape}"
+                         + ("" if t.ndim != 1 or t.size == 0 else " with non-finite or decreasing values"))
+    step = float(step)
+    if not (step > 0.0 and np.isfinite(step)):
+        raise ValueError(f"ping_bin_edges: step={step!r} must be a finite number > 0")
+    origin = float(t[0] if origin is None else origin)
+    if not np.isfinite(origin) or origin > t[-1]:
+        raise ValueError(f"ping_bin_edges: origin={origin!r} must be finite and not beyond the track's end {t[-1]!r}")
+    K = int(np.floor((t[-1] - origin) / step)) + 1
+    edges = np.searchsorted(t, origin + np.arange(K + 1, dtype=np.float64) * step, "left").astype(np.int64)
+    edges[-1] = len(t)                                   # (whatever the rounding of origin + K * step)
+    return edges
 
 
 # ---- echo integration scored against the annotations (the evaluation flows) --------------------------------------------
@@ -1133,6 +1279,9 @@ class _ScoredHolder:
         """``spec`` if a scored holder takes it (``ScoredIntegrationSet`` makes the same checks)."""
         if not isinstance(spec, IntegrationSpec):
             raise TypeError(f"{cls.__name__}: spec is an IntegrationSpec, got {type(spec).__name__}")
+        if spec.ping_edges is not None:
+            raise NotImplementedError(f"{cls.__name__}: a spec with ping_edges (EDSU cells) is not scored: the confusion "
+                                      "kernels size a patch's window of cells from a uniform ping_bin")
         if spec.seabed_aware or spec.reference != "surface":
             raise NotImplementedError(f"{cls.__name__}: a seabed-aware spec (seabed_offset / reference='seabed') is not "
                                       "scored: the transformed labels already exclude the pixels below the seabed")
@@ -1588,11 +1737,12 @@ def integrate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_
     """``integrate_survey`` for ONE memmap echogram: ``predict_echogram_memm``'s prediction (same arguments, the float16
     values it would return) reduced on the GPU against the resident sv plane; same pixel rule, same return value; the
     accumulators are not all-reduced (every rank that calls it returns the echogram's whole result).  A seabed-aware
-    ``spec`` goes by the line the prediction used (``seabed``: None, an array or "estimate").  For a whole memm survey
+    ``spec`` goes by the line the prediction used (``seabed``: None, an array or "estimate"); a callable
+    ``spec.ping_edges`` is asked for ``echogram``.  For a whole memm survey
     ``integrate_echograms_memm`` is the integrating form of the packed flow (``predict_echograms_memm``)."""
     cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
                                      out_f16=True, wide=False, seabed=seabed)
-    spec = spec.bind(segpipe.frequencies)
+    spec = spec.bind(segpipe.frequencies).resolve(echogram)
     grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
     cp.predict(grid, predict_fn=predict_fn)
     acc, cnt = new_integration(segpipe.device, spec, cp.end_ping, cp.n_range)
@@ -1664,6 +1814,18 @@ class _MemmRecord:
 
     def key(self):
         return len(self.grid), self.elems
+
+
+class _MemmEdgeRecord(_MemmRecord):
+    """A record of ``integrate_echograms_memm`` with EDSU cells: + ``spec``, the flow's bound spec with THIS echogram's
+    edge table (``IntegrationSpec.resolve``).  The table travels as int64 words in the tail of the group's ``misc`` and
+    counts towards the echogram's share of the staging."""
+
+    def __init__(self, echogram, seabed, patch_size, patch_overlap, spec=None, **meta):
+        super().__init__(echogram, seabed, patch_size, patch_overlap, **meta)
+        self.spec = spec.resolve(echogram)
+        words = 2 * hip.MEMM_DESC_WORDS + 3 * len(self.grid) + self.n_pings + 2 * len(self.spec.ping_edges) + 2
+        self.elems = max(self.elems, MEMM_MISC_SHARE * words)
 
 
 def _memm_survey_seabed(echogram, seabed, device):
@@ -2092,20 +2254,34 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
     scatters one integrate launch per echogram (``crimac_integrate_classes`` / ``crimac_integrate_layers`` by ``spec``)
     reads the echogram's float16 predictions, its plane of the transposed staging and its seabed line inside the group's
     uploaded ``misc``, and accumulates into the echogram's share of ONE flat fp64 / int64 buffer; the group's few
-    kilobytes leave through the flow's download ring, nothing in the feed blocks."""
+    kilobytes leave through the flow's download ring, nothing in the feed blocks.
+    A spec with ``ping_edges`` (EDSU cells, ``crimac_integrate_edges``): every echogram has its own table -- a callable is
+    asked per echogram while the groups are planned (``_MemmEdgeRecord``), a table given as an array serves them all --
+    and the tables of a group go up in the tail of its ``misc``, in the group's one pinned copy."""
     flow = _MemmSurveyFlow("integrate_echograms_memm", ("spec", "skip"), kwargs, echograms, segpipe, patch_size,
                            patch_overlap, batch_size, predict_fn, seabed, group_patches, group_elems, stats, skip=skip,
                            meta_channels=meta_channels, pack_metadata=pack_metadata)
     spec = spec.bind(segpipe.frequencies)
+    edsu = spec.ping_edges is not None
     C, W = flow.C, hip.MEMM_DESC_WORDS
 
     def single(eg, sb, meta):            # the per-echogram path
         return eg, integrate_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, spec, predict_fn=predict_fn,
                                            meta_channels=meta, seabed=sb)
 
+    def tail(group, misc, at):                           # the edge tables int64, one after the other, 8-byte aligned
+        at += at & 1
+        for r in group:
+            n = 2 * len(r.spec.ping_edges)
+            assert at + n <= len(misc), "memm group staging too small (edge tables)"
+            misc[at:at + n].view(np.int64)[:] = r.spec.ping_edges
+            at += n
+        return at
+
     def enqueue(g):
         ring, out = flow.ring(torch.float64), flow.feed.bufs["out"]
         shares, total = group_shares(g.group, spec, 3)
+        o_edges = g.o_tail + (g.o_tail & 1)
         acc = ring.zeroed(g.k, 2 * total)            # [sums | counts]
         out[:2 * g.total].zero_()
         flow.predict_group(g, predict_fn)
@@ -2113,10 +2289,12 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
         data_t = flow.feed.bufs["data_t"][g.k & 1]
         o_sb = 2 * W * g.n + 3 * g.P              # the seabed lines inside ``misc``, one after the other
         for r, off, (at, shape) in zip(g.group, g.offs, shares):
-            launch_integration(spec, ptr(out, 2 * off), True, r.n_range, r.n_pings,
+            launch_integration(r.spec if edsu else spec, ptr(out, 2 * off), True, r.n_range, r.n_pings,
                                ptr(data_t, C * off + spec.channel * r.pixels), r.n_pings, 0, 0, shape[0], ptr(acc, at),
-                               ptr(acc, total + at), scratch, seabed=(ptr(g.misc, o_sb), 0, r.n_pings))
+                               ptr(acc, total + at), scratch, seabed=(ptr(g.misc, o_sb), 0, r.n_pings),
+                               edges=ptr(g.misc, o_edges) if edsu else None)
             o_sb += r.n_pings
+            o_edges += 2 * (shape[0] + 1) if edsu else 0
         flow.feed.computed()
         return g.group, shares, ring.download(g.k, 2 * total)
 
@@ -2124,7 +2302,8 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
         group, shares, download = ticket
         return group_results(group, shares, *_DownloadRing.wait_sums_counts(download), spec, 3)
 
-    yield from flow.run("memm_integrate", single, enqueue, take, out="out",
+    staging = dict(record=functools.partial(_MemmEdgeRecord, spec=spec), tail=tail) if edsu else {}
+    yield from flow.run("memm_integrate", single, enqueue, take, out="out", **staging,
                         extra=lambda: dict(out=torch.empty(2 * flow.cap, dtype=torch.float16, device=flow.dev)))
 
 

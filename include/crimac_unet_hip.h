@@ -129,7 +129,7 @@ extern "C" {
  * struct passed by pointer (crimac_layer_desc), the meaning of an argument, the set of precisions or the set of entry
  * points changes, and a binding must refuse a library whose version differs from the header it was written against (an
  * older build that happens to export every symbol would walk a descriptor array with the wrong stride).  An ADDITIVE
- * entry point (crimac_integrate_layers) does not bump it: nothing an older caller uses has changed, and a binding that
+ * entry point (crimac_integrate_layers, crimac_integrate_edges) does not bump it: nothing an older caller uses has changed, and a binding that
  * needs the new symbol refuses a build without it by looking the symbol up.
  * crimac_layer_desc_size() is sizeof(crimac_layer_desc) as the library was compiled. */
 #define CRIMAC_ABI_VERSION 17
@@ -891,6 +891,29 @@ int crimac_integrate_layers(const void* pred, int pred_f16, int n_range, long n_
                             long ping_origin, long n_pb_total, const int* seabed, long seabed_first, long seabed_len,
                             int seabed_offset, int reference, int n_layers, double* acc, long long* cnt, void* scratch,
                             long scratch_bytes, void* stream);
+
+/* Both reductions with the ping axis of the cells given by an EDGE TABLE (echo integration per EDSU: cells of a sailed
+ * distance or a time span hold a varying number of pings).  The arguments of crimac_integrate_layers without ping_bin;
+ * seabed == NULL: the reduction of crimac_integrate_classes (seabed_first .. n_layers are not read).  The same two
+ * kernels, pixel rule, planes, range bins / layers, ordering and reproducibility; only the ping extent of a cell differs:
+ *   edges_dev int64 [n_pb_total + 1] (device) and edges_host, the same values on the host (read during the call only):
+ *     cell pb covers GLOBAL pings [edges[pb], edges[pb + 1]).  Edges are non-negative and non-decreasing, no cell wider
+ *     than 2^31 - 1 pings; the host table is checked at every call and a bad one is refused (CRIMAC_ERR_INVALID, nothing
+ *     is launched).  A zero-width cell is legal and receives nothing; pings of the launch before edges[0] or at or after
+ *     edges[n_pb_total] count in no plane (ping_origin + n_pings is not bounded by the table).  A launch that touches no
+ *     cell launches nothing and returns CRIMAC_OK.
+ *   The library derives from the host table the cells the launch touches -- pb0 = the first cell with edges[pb0 + 1] >
+ *     ping_origin to the last cell with edges[pb] < ping_origin + n_pings, zero-width cells in between included -- and
+ *     their widest extent, which takes the place of ping_bin in the split count.  With edges[pb] = pb * ping_bin it
+ *     launches what the uniform entry point launches: the same bits in acc and cnt.
+ *   scratch: (cells touched + CRIMAC_INTEGRATE_SPLIT_WGS) * CRIMAC_INTEGRATE_SLOT_BYTES always suffices, cells touched =
+ *     (pb1 - pb0 + 1) * (n_rb or n_layers).
+ *   A cell cut by a launch boundary accumulates over two launches, which must be ordered (one stream), as above. */
+int crimac_integrate_edges(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv, long data_pings,
+                           long sv_ping_off, float thr_sandeel, float thr_other, int mode, const long long* edges_dev,
+                           const long long* edges_host, int range_bin, long ping_origin, long n_pb_total,
+                           const int* seabed, long seabed_first, long seabed_len, int seabed_offset, int reference,
+                           int n_layers, double* acc, long long* cnt, void* scratch, long scratch_bytes, void* stream);
 
 /* Echo integration SCORED AGAINST THE ANNOTATIONS: the sums of crimac_integrate_classes split by the annotated class as
  * well, from one evaluation batch while it is resident (ChunkPredictor.evaluate).  The reference has no counterpart.

@@ -20,7 +20,17 @@ median of its rounds.  Leg B is checked against leg A: counts equal, every sum w
   LH host_layers -- predict_survey float16 followed by the numpy bottom-layer integration of every downloaded chunk.
 
 Leg L is checked against leg LH with the same bound, and the JSON line gains layers_over_device (B / L) and
-layers_over_host (LH / L)."""
+layers_over_host (LH / L).
+
+--edsu adds the EDSU leg to every round, same survey, same process, alternating with leg B:
+
+  E  edsu -- integrate_survey with IntegrationSpec(ping_edges=table): crimac_integrate_edges.  The table is drawn with a
+             fixed seed (--edsu-seed): as many cells as leg B has ping bins, widths from 0 to 4 x their mean, the mean equal
+             to --ping-bin, a few cells of width 0.  Its yardstick is leg B of the same run: the JSON line gains
+             edsu_over_device (B / E, medians) next to device_spread ((max - min) / median of leg B's own passes) -- the
+             ratio is not fixed in advance.  After the rounds leg E is checked against one untimed host pass (predict_survey
+             float16, numpy binning by the table) with the same bound.  Wall times of whole survey passes: the kernels' own
+             time is not measured here."""
 import argparse
 import json
 import os
@@ -87,6 +97,44 @@ def host_chunk_layers(acc, cnt, geo, out, sv, line, spec, s):
     geo += np.bincount(at[inside], minlength=n).reshape(geo.shape)
 
 
+def host_chunk_edges(acc, cnt, geo, out, sv, spec, s):
+    """``host_chunk`` for a spec with an edge table: ping s + p lies in the cell pb with edges[pb] <= s + p < edges[pb + 1]."""
+    R, P = out.shape[1:]
+    edges = spec.ping_edges
+    sv_t = np.ascontiguousarray(sv.T)
+    g = s + np.arange(P)
+    inside = np.broadcast_to(((g >= edges[0]) & (g < edges[-1]))[None, :], (R, P))
+    ok = np.isfinite(sv_t) & (sv_t > 0) & inside
+    s64 = np.where(ok, sv_t, 0).astype(np.float64)
+    p32 = out.astype(np.float32)
+    if spec.mode == "threshold":
+        member = p32 >= np.asarray(spec.thresholds, dtype=np.float32)[:, None, None]
+        weight = member.astype(np.float64)
+    else:
+        member = p32 > 0
+        weight = np.where(member, p32, 0).astype(np.float64)
+    n, n_rb = acc[0].size, acc.shape[2]
+    pb = np.clip(np.searchsorted(edges, g, "right") - 1, 0, len(edges) - 2)
+    at = pb[None, :] * n_rb + (np.arange(R) // spec.range_bin)[:, None]
+    for k, (terms, counted) in enumerate(((s64 * weight[0], ok & member[0]), (s64 * weight[1], ok & member[1]), (s64, ok))):
+        acc[k] += np.bincount(at[counted], weights=terms[counted], minlength=n).reshape(acc[k].shape)
+        cnt[k] += np.bincount(at[counted], minlength=n).reshape(acc[k].shape)
+    geo += np.bincount(at[inside], minlength=n).reshape(geo.shape)
+
+
+def edsu_table(n_pings, ping_bin, seed):
+    """An edge table over [0, n_pings) with ceil(n_pings / ping_bin) cells: widths ~ 4 x Beta(1, 3) x the mean (0 .. 4 x the
+    mean, mean = n_pings / cells), every 16th cell of width 0."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = -(-n_pings // ping_bin)
+    u = rng.beta(1.0, 3.0, size=n)
+    u[::16] = 0
+    w = np.minimum(u / u.sum() * n_pings, 4.0 * n_pings / n)
+    edges = np.rint(np.concatenate([[0.0], np.cumsum(w)])).astype(np.int64)
+    edges[-1] = n_pings
+    return np.maximum.accumulate(edges)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pings", type=int, default=16384)
@@ -100,6 +148,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--layers", type=int, default=0, help="> 0: add the seabed-reference legs with this many layers")
     ap.add_argument("--seabed-offset", type=int, default=-5)
+    ap.add_argument("--edsu", action="store_true", help="add the EDSU leg: integrate_survey with an edge table")
+    ap.add_argument("--edsu-seed", type=int, default=20)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     reader = synth.SyntheticSurveyReader(n_pings=a.pings, n_range=a.range, seabed_index=900, block=4096, schools=40,
@@ -147,6 +197,9 @@ def main():
                 host_chunk_layers(acc, cnt, geo, out, sv, reader.get_seabed(s, e - s, return_numpy=True), lspec, s)
             return acc, cnt, geo
         legs.update(layers=leg_layers, host_layers=leg_host_layers)
+    if a.edsu:
+        espec = ti.IntegrationSpec(None, a.range_bin, mode=a.mode, ping_edges=edsu_table(a.pings, a.ping_bin, a.edsu_seed))
+        legs["edsu"] = lambda: ti.integrate_survey(reader, pipe, patch, overlap, a.batch, a.preload, espec)
     times, last = {k: [] for k in legs}, {}
     for rnd in range(-1, a.rounds):                                       # round -1: warm-up (staging, packed weights)
         for name, fn in legs.items():
@@ -183,6 +236,24 @@ def main():
                     layers_over_device=round(med["device"] / med["layers"], 4),
                     layers_over_host=round(med["host_layers"] / med["layers"], 4),
                     layer_pixels=[int(lcnt[0].sum()), int(lcnt[1].sum()), int(lcnt[2].sum())])
+    if a.edsu:
+        eacc, ecnt, egeo = np.zeros((3, n_pb, n_rb)), np.zeros((3, n_pb, n_rb), dtype=np.int64), np.zeros((n_pb, n_rb), dtype=np.int64)
+        for s, e, out in ti.predict_survey(reader, pipe, patch, overlap, a.batch, a.preload, out_dtype=np.float16):   # untimed
+            sv = reader.get_data_slice(idx_ping=s, n_pings=e - s, frequencies=pipe.frequencies)[channel]
+            host_chunk_edges(eacc, ecnt, egeo, out, sv, espec, s)
+        egot = last["edsu"]
+        eerr, ebound = np.abs(egot["sv_sum"] - eacc), (egeo[None] + 2) * 2.0 ** -52 * eacc
+        counts_equal = counts_equal and bool(np.array_equal(egot["pixels"], ecnt))
+        within = within and bool((eerr <= ebound).all() and (egot["sv_sum"][eacc == 0] == 0).all())
+        widths = np.diff(espec.ping_edges)
+        dev = times["device"]
+        line.update(counts_equal=counts_equal, sums_within_bound=within, edsu_seed=a.edsu_seed,
+                    edsu_widths={"cells": int(len(widths)), "min": int(widths.min()), "max": int(widths.max()),
+                                 "mean": round(float(widths.mean()), 2), "empty": int((widths == 0).sum())},
+                    edsu_over_device=round(med["device"] / med["edsu"], 4),
+                    device_spread=round((max(dev) - min(dev)) / med["device"], 4),
+                    edsu_pixels=[int(ecnt[0].sum()), int(ecnt[1].sum()), int(ecnt[2].sum())],
+                    kernel_time_measured=False)
     for k in legs:
         print(f"{k:8s}: {patches} patches, median {med[k]:.3f} s -> {patches / med[k]:.0f} patches/s", flush=True)
     text = json.dumps(line)
