@@ -108,6 +108,126 @@ __device__ __forceinline__ void load_pred(const TP* __restrict__ row, long p, lo
   }
 }
 
+// The steps of integrate_cells_kernel as functions, for integrate_freqs_kernel further down (the single-frequency kernel
+// keeps its own text: its code generation is not to change).
+// SEABED prologue of a workgroup: min and max of L over the cell's ping span cut the cell's rows to the box that can hold
+// a counted pixel.  Returns `top`: with the seabed reference the layer ends `top` rows above the limit (0 otherwise).
+__device__ __forceinline__ long seabed_box(const Geom& g, Cell& c, long cell, int t) {
+  __shared__ int span_min[kThreads / 64], span_max[kThreads / 64];
+  const int lane = t & 63, wave = t >> 6;
+  long top = 0;
+  int lmin = g.n_range, lmax = 0;                               // (every limit lies in [0, n_range])
+  for (long p = c.p0 + t; p < c.p1; p += kThreads) {
+    const int L = row_limit(g, p);
+    lmin = L < lmin ? L : lmin;
+    lmax = L > lmax ? L : lmax;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int a = __shfl_xor(lmin, o, 64), b = __shfl_xor(lmax, o, 64);
+    lmin = a < lmin ? a : lmin;
+    lmax = b > lmax ? b : lmax;
+  }
+  if (lane == 0) span_min[wave] = lmin, span_max[wave] = lmax;
+  __syncthreads();
+  for (int w = 0; w < kThreads / 64; ++w) {
+    lmin = span_min[w] < lmin ? span_min[w] : lmin;
+    lmax = span_max[w] > lmax ? span_max[w] : lmax;
+  }
+  if (g.reference == 1) {                                       // the row bounding box of the layer over the ping span
+    top = (cell % g.n_rb) * g.range_bin;
+    const long b0 = lmin - top - g.range_bin, b1 = lmax - top;
+    c.r0 = (int)(b0 > 0 ? b0 : 0);
+    c.r1 = (int)(b1 > 0 ? b1 : 0);
+  } else {
+    c.r1 = c.r1 < lmax ? c.r1 : lmax;                           // no ping of the span counts a row below
+  }
+  return top;
+}
+
+// SEABED: the rows [lo, hi) of ping p that count in the workgroup's cell (cell_r0, cell_r1: its rows before seabed_box)
+__device__ __forceinline__ void row_interval(const Geom& g, long p, long top, int cell_r0, int cell_r1, int& lo, int& hi) {
+  const long L = row_limit(g, p);
+  if (g.reference == 1) {
+    lo = (int)(L - top - g.range_bin > 0 ? L - top - g.range_bin : 0);
+    hi = (int)(L - top > 0 ? L - top : 0);
+  } else {
+    lo = cell_r0;
+    hi = (int)(L < cell_r1 ? L : cell_r1);
+  }
+}
+
+// sv of the tile at (row tr, ping tp): global (along the range) -> registers; 0 outside the cell and outside the array
+template <bool VEC_SV>
+__device__ __forceinline__ void load_sv_tile(const float* __restrict__ sv, const Geom& g, const Cell& c, int tr, long tp, int t,
+                                             float (&svr)[16]) {
+  if constexpr (VEC_SV) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = t + kThreads * k, r = tr + 4 * (i & 15);
+      const long p = tp + (i >> 4);
+      f32x4 x = {0.f, 0.f, 0.f, 0.f};
+      if (r < c.r1 && p >= c.p0 && p < c.p1)                  // (r, n_range multiples of 4: r < r1 <= n_range -> r + 3 < n_range)
+        x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(sv + (g.sv_ping_off + p) * g.n_range + r));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) svr[4 * k + j] = (r + j >= c.r0 && r + j < c.r1) ? x[j] : 0.f;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int i = t + kThreads * k, r = tr + (i & 63);
+      const long p = tp + (i >> 6);
+      svr[k] = (r >= c.r0 && r < c.r1 && p >= c.p0 && p < c.p1)
+                   ? __builtin_nontemporal_load(sv + (g.sv_ping_off + p) * g.n_range + r) : 0.f;
+    }
+  }
+}
+
+// ... registers -> LDS tile [ping][row]
+template <bool VEC_SV>
+__device__ __forceinline__ void stage_sv_tile(float* tile, int t, const float (&svr)[16]) {
+  if constexpr (VEC_SV) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = t + kThreads * k;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tile[(i >> 4) * kPitch + 4 * (i & 15) + j] = svr[4 * k + j];
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int i = t + kThreads * k;
+      tile[(i >> 6) * kPitch + (i & 63)] = svr[k];
+    }
+  }
+}
+
+// a thread's six results: lanes by a butterfly, the waves in wave order by thread 0, into one slot of the scratch
+__device__ __forceinline__ void reduce_to_slot(double s0, double s1, double s2, long long n0, long long n1, long long n2,
+                                               Slot* wave_part, int t, Slot* __restrict__ out_slot) {
+  const int lane = t & 63, wave = t >> 6;
+  s0 = wave_sum_d(s0);
+  s1 = wave_sum_d(s1);
+  s2 = wave_sum_d(s2);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    n0 += __shfl_xor(n0, o, 64);
+    n1 += __shfl_xor(n1, o, 64);
+    n2 += __shfl_xor(n2, o, 64);
+  }
+  if (lane == 0) wave_part[wave] = Slot{{s0, s1, s2}, {n0, n1, n2}};
+  __syncthreads();
+  if (t == 0) {
+    Slot out = wave_part[0];
+    for (int w = 1; w < kThreads / 64; ++w)
+      for (int k = 0; k < 3; ++k) {
+        out.sum[k] += wave_part[w].sum[k];
+        out.cnt[k] += wave_part[w].cnt[k];
+      }
+    *out_slot = out;
+  }
+}
+
 template <typename TP, bool VEC_SV, bool VEC_PRED, bool SEABED>
 __global__ __launch_bounds__(kThreads) void integrate_cells_kernel(const TP* __restrict__ pred, const float* __restrict__ sv,
                                                                    Geom g, Slot* __restrict__ scratch) {
@@ -316,6 +436,173 @@ __global__ __launch_bounds__(kThreads) void integrate_finish_kernel(const Slot* 
   }
 }
 
+// ---- crimac_integrate_freqs: the same reduction for SEVERAL frequency planes in one pass over the predictions -----------
+// The workgroup is still (cell, split) and walks the same tiles in the same order.  Per tile the predictions are read once
+// and turned into the two class weights of each of the thread's 16 pixels (threshold mode: 1 or 0; probability mode: the
+// stored value, 0 for a NaN or negative one), the seabed forms read their pings' row intervals once; then the sv tile of each
+// frequency goes through LDS in turn and lands in that frequency's own six accumulators.  Two LDS tile buffers, used
+// alternately, leave ONE barrier per frequency: a thread that writes buffer b again has passed the barrier of the stage in
+// between, which every thread reaches only after it has read b; where registers allow it (kPrefetch) the global loads of the
+// next frequency are issued right after the barrier and fly while the tile is consumed.  The accumulators are indexed by the unrolled frequency loop only,
+// so they stay in registers.  A pixel adds `in ? sv * w : 0` to a class sum, which has the bits of the single-frequency
+// kernel's term in both modes (w = 1 gives sv exactly), in the same tile, pixel, lane, wave and split order: frequency i
+// gets the bits crimac_integrate_classes / _layers / _edges give on its plane.  Its slots are scratch[i * slots + blockIdx.x].
+constexpr int kMaxFreqs = CRIMAC_INTEGRATE_MAX_FREQS;
+struct Planes {
+  int n;                   // frequencies of the launch
+  long slots;              // cells * splits: the slots of one frequency
+  long off[kMaxFreqs];     // elements from sv (plane 0) to the plane of frequency i
+};
+
+template <typename TP, bool VEC_SV, bool VEC_PRED, bool SEABED, int NF>
+__global__ __launch_bounds__(kThreads) void integrate_freqs_kernel(const TP* __restrict__ pred, const float* __restrict__ sv,
+                                                                   Geom g, Planes fq, Slot* __restrict__ scratch) {
+  __shared__ float tile[2][kTile * kPitch];
+  __shared__ Slot wave_part[kThreads / 64];
+  __shared__ int row_lo[2][SEABED ? kTile : 1], row_hi[2][SEABED ? kTile : 1];
+  const int t = threadIdx.x;
+  const long cell = blockIdx.x / g.splits;
+  const int split = (int)(blockIdx.x - cell * g.splits);
+  Cell c = cell_of(g, cell);
+  const int cell_r0 = c.r0, cell_r1 = c.r1;
+  long top = 0;
+  if constexpr (SEABED) top = seabed_box(g, c, cell, t);
+  const int ra = c.r0 & ~3;
+  const long pa = c.p0 & ~3L;
+  const int nrt = c.r1 > c.r0 ? (c.r1 - ra + kTile - 1) / kTile : 0;
+  const long npt = c.p1 > c.p0 ? (c.p1 - pa + kTile - 1) / kTile : 0;
+  const long tiles = nrt * npt;
+  const TP* pred0 = pred;
+  const TP* pred1 = pred + (long)g.n_range * g.n_pings;
+  const int row_in_group = t >> 4, l16 = t & 15;
+  double s0[NF], s1[NF], s2[NF];
+  long long n0[NF], n1[NF], n2[NF];
+#pragma unroll
+  for (int f = 0; f < NF; ++f) s0[f] = s1[f] = s2[f] = 0.0, n0[f] = n1[f] = n2[f] = 0;
+  int stage = 0;                                              // LDS buffer of the next (tile, frequency): stage & 1
+
+  for (long tl = split; tl < tiles; tl += g.splits) {
+    const int tr = ra + (int)(tl / npt) * kTile;
+    const long tp = pa + (tl % npt) * kTile;
+    float svr[16];
+    load_sv_tile<VEC_SV>(sv + fq.off[0], g, c, tr, tp, t, svr);
+    // ---- pred -> the class weights of the 4 rows x 4 pings this thread consumes, once for all frequencies
+    float w0[4][4], w1[4][4];
+    const long pp = tp + (VEC_PRED ? 4 * l16 : l16);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int r = tr + row_in_group + 16 * k;
+      if (r < c.r1) {
+        load_pred<TP, VEC_PRED>(pred0 + (long)r * g.n_pings, pp, g.n_pings, w0[k]);
+        load_pred<TP, VEC_PRED>(pred1 + (long)r * g.n_pings, pp, g.n_pings, w1[k]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w0[k][j] = w1[k][j] = 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float a = w0[k][j], b = w1[k][j];
+        if (g.mode == 0) {
+          w0[k][j] = a >= g.thr0 ? 1.f : 0.f;
+          w1[k][j] = b >= g.thr1 ? 1.f : 0.f;
+        } else {
+          w0[k][j] = a > 0.f ? a : 0.f;                       // (a NaN or negative weight counts as 0)
+          w1[k][j] = b > 0.f ? b : 0.f;
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    int lo = 0, hi = 0;                                       // SEABED: the rows of ping tp + t that count here
+    if constexpr (SEABED) {
+      if (t < kTile && tp + t >= c.p0 && tp + t < c.p1) row_interval(g, tp + t, top, cell_r0, cell_r1, lo, hi);
+    }
+    int plo[4], phi[4];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+      if (f < fq.n) {                                         // (uniform)
+        const int b = stage & 1;
+        ++stage;
+        if constexpr (SEABED) {
+          if (f == 0 && t < kTile) row_lo[b][t] = lo, row_hi[b][t] = hi;
+        }
+        // the 16-byte form with few accumulators has registers to spare: the next plane's loads fly while this tile is consumed
+        constexpr bool kPrefetch = VEC_SV && NF <= 4;
+        if (!kPrefetch && f > 0) load_sv_tile<VEC_SV>(sv + fq.off[f], g, c, tr, tp, t, svr);
+        stage_sv_tile<VEC_SV>(tile[b], t, svr);
+        __syncthreads();
+        if (kPrefetch && f + 1 < NF && f + 1 < fq.n) load_sv_tile<VEC_SV>(sv + fq.off[f + 1 < NF ? f + 1 : f], g, c, tr, tp, t, svr);
+        if constexpr (SEABED) {
+          if (f == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int pl = VEC_PRED ? 4 * l16 + j : l16 + 16 * j;
+              plo[j] = row_lo[b][pl] - tr;                    // (relative to the tile's first row)
+              phi[j] = row_hi[b][pl] - tr;
+            }
+          }
+        }
+        // ---- the pixel rule on this frequency's own sv
+        int m0 = 0, m1 = 0, m2 = 0;                           // (counted pixels of the tile: 16 at most)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int rl = row_in_group + 16 * k;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int pl = VEC_PRED ? 4 * l16 + j : l16 + 16 * j;
+            const float s = tile[b][pl * kPitch + rl];
+            bool ok = s > 0.f && s < __builtin_inff();        // finite and > 0 (NaN fails both)
+            if constexpr (SEABED) ok = ok && rl >= plo[j] && rl < phi[j];
+            const float a = w0[k][j], b1 = w1[k][j];
+            const double sd = ok ? (double)s : 0.0;
+            const bool in0 = ok && a > 0.f, in1 = ok && b1 > 0.f;
+            s0[f] += in0 ? sd * (double)a : 0.0;
+            s1[f] += in1 ? sd * (double)b1 : 0.0;
+            s2[f] += sd;
+            m0 += in0;
+            m1 += in1;
+            m2 += ok;
+          }
+          __builtin_amdgcn_sched_barrier(0);                  // (four pixels at a time: their compare masks live in SGPRs)
+        }
+        n0[f] += m0;
+        n1[f] += m1;
+        n2[f] += m2;
+      }
+    }
+  }
+  // ---- lane -> wave -> workgroup per frequency, each in a fixed order
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    if (f < fq.n) {
+      if (f > 0) __syncthreads();                             // (thread 0 has read wave_part)
+      reduce_to_slot(s0[f], s1[f], s2[f], n0[f], n1[f], n2[f], wave_part, t, scratch + f * fq.slots + blockIdx.x);
+    }
+  }
+}
+
+// one thread per (frequency, cell): the slots of that frequency in split order, then the plain read-add-write into its
+// [3][n_pb_total][n_rb] slice
+__global__ __launch_bounds__(kThreads) void integrate_freqs_finish_kernel(const Slot* __restrict__ scratch, Geom g, Planes fq,
+                                                                          long cells, double* __restrict__ acc,
+                                                                          long long* __restrict__ cnt) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= cells * fq.n) return;
+  const long f = i / cells, cell = i - f * cells;
+  const Slot* __restrict__ slots = scratch + f * fq.slots + cell * g.splits;
+  Slot out = slots[0];
+  for (int s = 1; s < g.splits; ++s)
+    for (int k = 0; k < 3; ++k) {
+      out.sum[k] += slots[s].sum[k];
+      out.cnt[k] += slots[s].cnt[k];
+    }
+  const long pb = g.pb0 + cell / g.n_rb, rb = cell % g.n_rb;
+  for (int k = 0; k < 3; ++k) {
+    const long at = (((long)f * 3 + k) * g.n_pb_total + pb) * g.n_rb + rb;
+    acc[at] += out.sum[k];
+    cnt[at] += out.cnt[k];
+  }
+}
+
 template <typename TP, bool SEABED>
 void launch_cells(bool vec_sv, bool vec_pred, unsigned blocks, hipStream_t st, const void* pred, const float* sv,
                   const Geom& g, Slot* scratch) {
@@ -332,6 +619,27 @@ struct SeabedArgs { const int* line; long first, len; int offset, reference, n_l
 // what crimac_integrate_edges gives in place of ping_bin (null: the uniform entry points)
 struct EdgeArgs { const long long* dev; const long long* host; };
 
+// what crimac_integrate_freqs adds: the planes of the source and the selected ones (null: one plane, the other entry points)
+struct FreqArgs { long plane_stride; int n_planes; const int* channels; int n_freqs; };
+
+template <typename TP, bool SEABED, int NF>
+void launch_freqs(bool vec_sv, bool vec_pred, unsigned blocks, hipStream_t st, const void* pred, const float* sv, const Geom& g,
+                  const Planes& fq, Slot* scratch) {
+  const TP* p = static_cast<const TP*>(pred);
+  if (vec_sv && vec_pred) hipLaunchKernelGGL((integrate_freqs_kernel<TP, true, true, SEABED, NF>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, fq, scratch);
+  else if (vec_sv) hipLaunchKernelGGL((integrate_freqs_kernel<TP, true, false, SEABED, NF>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, fq, scratch);
+  else if (vec_pred) hipLaunchKernelGGL((integrate_freqs_kernel<TP, false, true, SEABED, NF>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, fq, scratch);
+  else hipLaunchKernelGGL((integrate_freqs_kernel<TP, false, false, SEABED, NF>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, fq, scratch);
+}
+
+// the instantiation by the accumulators it holds: 4 frequencies (the models' four) or CRIMAC_INTEGRATE_MAX_FREQS
+template <typename TP, bool SEABED>
+void launch_freqs(bool vec_sv, bool vec_pred, unsigned blocks, hipStream_t st, const void* pred, const float* sv, const Geom& g,
+                  const Planes& fq, Slot* scratch) {
+  if (fq.n <= 4) launch_freqs<TP, SEABED, 4>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, scratch);
+  else launch_freqs<TP, SEABED, kMaxFreqs>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, scratch);
+}
+
 // The cells [pb0, pb1] of a checked host table that global pings [a, b) touch (pb1 < pb0: none) and their widest extent.
 void cells_touched(const long long* e, long n_pb, long a, long b, long& pb0, long& pb1, long& widest) {
   const long long* first = std::upper_bound(e, e + n_pb + 1, (long long)a);     // the first edge > a
@@ -343,12 +651,20 @@ void cells_touched(const long long* e, long n_pb, long a, long b, long& pb0, lon
   for (long pb = pb0; pb <= pb1; ++pb) widest = e[pb + 1] - e[pb] > widest ? (long)(e[pb + 1] - e[pb]) : widest;
 }
 
-// All three entry points: the argument checks, the geometry, the two launches.  `who` names the caller in the messages.
-int integrate(const char* who, const SeabedArgs* sb, const EdgeArgs* ed, const void* pred, int pred_f16, int n_range, long n_pings,
+// All four entry points: the argument checks, the geometry, the two launches.  `who` names the caller in the messages.
+int integrate(const char* who, const SeabedArgs* sb, const EdgeArgs* ed, const FreqArgs* fa, const void* pred, int pred_f16, int n_range, long n_pings,
               const float* sv, long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode, long ping_bin,
               int range_bin, long ping_origin, long n_pb_total, double* acc, long long* cnt, void* scratch,
               long scratch_bytes, void* stream) {
-  CRIMAC_REQUIRE(pred && sv && acc && cnt && scratch, "%s: null pointer", who);
+  CRIMAC_REQUIRE(pred && sv && acc && cnt && scratch && (!fa || fa->channels), "%s: null pointer", who);
+  if (fa) {
+    CRIMAC_REQUIRE(fa->n_freqs >= 1 && fa->n_freqs <= kMaxFreqs, "%s: n_freqs=%d (1 .. CRIMAC_INTEGRATE_MAX_FREQS = %d)", who,
+                   fa->n_freqs, kMaxFreqs);
+    CRIMAC_REQUIRE(fa->n_planes >= 1, "%s: n_planes=%d", who, fa->n_planes);
+    for (int i = 0; i < fa->n_freqs; ++i)
+      CRIMAC_REQUIRE(fa->channels[i] >= 0 && fa->channels[i] < fa->n_planes, "%s: channels[%d]=%d of %d sv planes", who, i,
+                     fa->channels[i], fa->n_planes);
+  }
   CRIMAC_REQUIRE(pred_f16 == 0 || pred_f16 == 1, "%s: pred_f16 is 0 or 1", who);
   CRIMAC_REQUIRE(n_range > 0 && n_pings > 0, "%s: empty prediction array (%d x %ld)", who, n_range, n_pings);
   CRIMAC_REQUIRE(mode == 0 || mode == 1, "%s: mode %d (0 threshold, 1 probability)", who, mode);
@@ -363,6 +679,10 @@ int integrate(const char* who, const SeabedArgs* sb, const EdgeArgs* ed, const v
   CRIMAC_REQUIRE(ping_origin >= 0 && n_pb_total > 0 && (ed || ping_origin + n_pings <= n_pb_total * ping_bin),
                  "%s: pings [%ld, %ld) outside the accumulator's %ld bins of %ld pings", who, ping_origin,
                  ping_origin + n_pings, n_pb_total, ping_bin);
+  // the source is n_planes planes of plane_stride elements: a plane [data_pings][n_range] must end inside its own stride
+  CRIMAC_REQUIRE(!fa || (data_pings <= 9223372036854775807L / n_range && fa->plane_stride >= data_pings * n_range),
+                 "%s: plane_stride=%ld: a plane of %ld pings x %d rows would leave the sv extent of %d planes", who,
+                 fa ? fa->plane_stride : 0L, data_pings, n_range, fa ? fa->n_planes : 0);
   long pb0 = 0, pb1 = 0, widest = ping_bin;
   if (ed) {
     CRIMAC_REQUIRE(ed->dev && ed->host, "%s: null edge table", who);
@@ -413,14 +733,36 @@ int integrate(const char* who, const SeabedArgs* sb, const EdgeArgs* ed, const v
   const long want = (CRIMAC_INTEGRATE_SPLIT_WGS + cells - 1) / cells;
   g.splits = (int)(want < tiles ? want : tiles);
   CRIMAC_REQUIRE(cells * g.splits <= 2147483647L, "%s: %ld cells in one launch", who, cells);
-  CRIMAC_REQUIRE(scratch_bytes >= cells * g.splits * (long)sizeof(Slot) && (uintptr_t)scratch % 8 == 0,
+  const long n_freqs = fa ? fa->n_freqs : 1;
+  CRIMAC_REQUIRE(scratch_bytes >= n_freqs * cells * g.splits * (long)sizeof(Slot) && (uintptr_t)scratch % 8 == 0,
                  "%s: scratch of %ld bytes, this launch needs %ld (8-byte aligned; (cells + "
-                 "CRIMAC_INTEGRATE_SPLIT_WGS) * CRIMAC_INTEGRATE_SLOT_BYTES always suffices)", who, scratch_bytes,
-                 cells * g.splits * (long)sizeof(Slot));
-  const bool vec_sv = n_range % 4 == 0 && (uintptr_t)sv % 16 == 0;
+                 "CRIMAC_INTEGRATE_SPLIT_WGS) * CRIMAC_INTEGRATE_SLOT_BYTES%s always suffices)", who, scratch_bytes,
+                 n_freqs * cells * g.splits * (long)sizeof(Slot), fa ? " * n_freqs" : "");
+  bool vec_sv = n_range % 4 == 0 && (uintptr_t)sv % 16 == 0;
   const bool vec_pred = n_pings % 4 == 0 && (uintptr_t)pred % (pred_f16 ? 8 : 16) == 0;
   const hipStream_t st = (hipStream_t)stream;
   const unsigned blocks = (unsigned)(cells * g.splits);
+  if (fa) {
+    Planes fq{};
+    fq.n = fa->n_freqs;
+    fq.slots = cells * g.splits;
+    for (int i = 0; i < fq.n; ++i) {
+      fq.off[i] = fa->channels[i] * fa->plane_stride;
+      vec_sv = vec_sv && (uintptr_t)(sv + fq.off[i]) % 16 == 0;    // the 16-byte reads only if EVERY selected plane allows them
+    }
+    if (sb) {
+      if (pred_f16) launch_freqs<half_t, true>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, (Slot*)scratch);
+      else launch_freqs<float, true>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, (Slot*)scratch);
+    } else {
+      if (pred_f16) launch_freqs<half_t, false>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, (Slot*)scratch);
+      else launch_freqs<float, false>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, (Slot*)scratch);
+    }
+    CRIMAC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(integrate_freqs_finish_kernel, dim3((unsigned)((cells * fq.n + kThreads - 1) / kThreads)), dim3(kThreads),
+                       0, st, (const Slot*)scratch, g, fq, cells, acc, cnt);
+    CRIMAC_LAUNCH_CHECK();
+    return CRIMAC_OK;
+  }
   if (sb) {
     if (pred_f16) launch_cells<half_t, true>(vec_sv, vec_pred, blocks, st, pred, sv, g, (Slot*)scratch);
     else launch_cells<float, true>(vec_sv, vec_pred, blocks, st, pred, sv, g, (Slot*)scratch);
@@ -708,7 +1050,7 @@ extern "C" int crimac_integrate_classes(const void* pred, int pred_f16, int n_ra
                                         long data_pings, long sv_ping_off, float thr_sandeel, float thr_other, int mode,
                                         long ping_bin, int range_bin, long ping_origin, long n_pb_total, double* acc,
                                         long long* cnt, void* scratch, long scratch_bytes, void* stream) {
-  return integrate("integrate_classes", nullptr, nullptr, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, thr_sandeel,
+  return integrate("integrate_classes", nullptr, nullptr, nullptr, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, thr_sandeel,
                    thr_other, mode, ping_bin, range_bin, ping_origin, n_pb_total, acc, cnt, scratch, scratch_bytes, stream);
 }
 
@@ -718,7 +1060,7 @@ extern "C" int crimac_integrate_layers(const void* pred, int pred_f16, int n_ran
                                        long seabed_first, long seabed_len, int seabed_offset, int reference, int n_layers,
                                        double* acc, long long* cnt, void* scratch, long scratch_bytes, void* stream) {
   const SeabedArgs sb{seabed, seabed_first, seabed_len, seabed_offset, reference, n_layers};
-  return integrate("integrate_layers", &sb, nullptr, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, thr_sandeel,
+  return integrate("integrate_layers", &sb, nullptr, nullptr, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, thr_sandeel,
                    thr_other, mode, ping_bin, range_bin, ping_origin, n_pb_total, acc, cnt, scratch, scratch_bytes, stream);
 }
 
@@ -730,7 +1072,22 @@ extern "C" int crimac_integrate_edges(const void* pred, int pred_f16, int n_rang
                                       long long* cnt, void* scratch, long scratch_bytes, void* stream) {
   const SeabedArgs sb{seabed, seabed_first, seabed_len, seabed_offset, reference, n_layers};
   const EdgeArgs ed{edges_dev, edges_host};
-  return integrate("integrate_edges", seabed ? &sb : nullptr, &ed, pred, pred_f16, n_range, n_pings, sv, data_pings,
+  return integrate("integrate_edges", seabed ? &sb : nullptr, &ed, nullptr, pred, pred_f16, n_range, n_pings, sv, data_pings,
                    sv_ping_off, thr_sandeel, thr_other, mode, 0, range_bin, ping_origin, n_pb_total, acc, cnt, scratch,
                    scratch_bytes, stream);
+}
+
+extern "C" int crimac_integrate_freqs(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv,
+                                      long plane_stride, int n_planes, const int* channels, int n_freqs, long data_pings,
+                                      long sv_ping_off, float thr_sandeel, float thr_other, int mode, long ping_bin,
+                                      const long long* edges_dev, const long long* edges_host, int range_bin,
+                                      long ping_origin, long n_pb_total, const int* seabed, long seabed_first,
+                                      long seabed_len, int seabed_offset, int reference, int n_layers, double* acc,
+                                      long long* cnt, void* scratch, long scratch_bytes, void* stream) {
+  const SeabedArgs sb{seabed, seabed_first, seabed_len, seabed_offset, reference, n_layers};
+  const EdgeArgs ed{edges_dev, edges_host};
+  const FreqArgs fa{plane_stride, n_planes, channels, n_freqs};
+  return integrate("integrate_freqs", seabed ? &sb : nullptr, edges_dev ? &ed : nullptr, &fa, pred, pred_f16, n_range, n_pings, sv,
+                   data_pings, sv_ping_off, thr_sandeel, thr_other, mode, edges_dev ? 0 : ping_bin, range_bin, ping_origin,
+                   n_pb_total, acc, cnt, scratch, scratch_bytes, stream);
 }

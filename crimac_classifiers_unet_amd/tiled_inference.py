@@ -232,32 +232,41 @@ class ChunkPredictor:
         """Echo integration of the chunk ``predict`` has just filled (``crimac_integrate_classes``): the linear sv of
         ``self.data[spec.channel]`` summed per class and cell into ``acc`` float64 / ``cnt`` int64
         ``[3, n_pb_total, n_rb]`` on the GPU (``new_integration``), which cover global pings from 0.  ``spec``: a bound
-        ``IntegrationSpec``.  Launches on the current stream, after the scatter; nothing comes back.
+        ``IntegrationSpec``; with a sequence of F frequencies ``acc`` / ``cnt`` are ``[F, 3, n_pb_total, n_rb]`` and ONE
+        launch (``crimac_integrate_freqs``) reads the predictions once for all of them.  Launches on the current stream,
+        after the scatter; nothing comes back.
         A seabed-aware spec (``seabed_offset`` given) runs ``crimac_integrate_layers`` with the chunk's seabed line
         (``_limit_line``: the vector, or the first masked row per ping of a chunk loaded with a 2-D mask); with the seabed
         reference the accumulators are ``[3, n_pb_total, layers]``.  A spec with ``ping_edges`` (a table: ``resolve`` a
         callable first) runs ``crimac_integrate_edges``; ``n_pb_total`` is then the table's number of cells exactly."""
         if self.wide or self.out is None:
             raise ValueError("ChunkPredictor.integrate: the chunk was loaded for evaluate() (wide=True) and has no predictions")
-        if spec.channel is None:
+        if spec.channels is None or spec.channels[0] is None:
             raise ValueError("ChunkPredictor.integrate: bind the spec to the model's frequencies first (IntegrationSpec.bind)")
-        if not 0 <= spec.channel < self.data.shape[0]:
-            raise ValueError(f"ChunkPredictor.integrate: channel {spec.channel} of {self.data.shape[0]} data planes")
+        for ch in spec.channels:
+            if not 0 <= ch < self.data.shape[0]:
+                raise ValueError(f"ChunkPredictor.integrate: channel {ch} of {self.data.shape[0]} data planes")
         n_pb, n_rb = spec.bins(self.end_ping, self.n_range)
-        want = (3, acc.shape[1], n_rb)
+        lead = (spec.n_freqs, 3) if spec.multi else (3,)
+        n_acc = int(acc.shape[-2]) if acc.dim() == len(lead) + 2 else -1
+        want = (*lead, n_acc, n_rb)
         if acc.dtype != torch.float64 or cnt.dtype != torch.int64 or tuple(acc.shape) != want or tuple(cnt.shape) != want \
-                or acc.shape[1] < n_pb or (spec.ping_edges is not None and acc.shape[1] != n_pb) \
+                or n_acc < n_pb or (spec.ping_edges is not None and n_acc != n_pb) \
                 or not acc.is_contiguous() or not cnt.is_contiguous():
-            raise ValueError(f"ChunkPredictor.integrate: acc float64 / cnt int64, contiguous [3, >= {n_pb}, {n_rb}]; got "
-                             f"{acc.dtype} {tuple(acc.shape)}, {cnt.dtype} {tuple(cnt.shape)}")
+            raise ValueError(f"ChunkPredictor.integrate: acc float64 / cnt int64, contiguous {list(lead)} + [>= {n_pb}, {n_rb}]; "
+                             f"got {acc.dtype} {tuple(acc.shape)}, {cnt.dtype} {tuple(cnt.shape)}")
         n = self.end_ping - self.start_ping
         cells = spec.touched(self.start_ping, self.end_ping) * n_rb
-        scratch = integration_scratch(self.engine, cells)
-        sv = self.data[spec.channel]
+        scratch = integration_scratch(self.engine, cells, spec.n_freqs)
+        data = self.data
+        if spec.multi and not data.is_contiguous():
+            raise ValueError("ChunkPredictor.integrate: several frequencies need the chunk's data contiguous [C, pings, range]")
+        sv = data[0] if spec.multi else data[spec.channel]           # (several frequencies: plane 0 and the plane stride)
         with torch.cuda.device(self.out.device):
             launch_integration(spec, ptr(self.out), self.out_f16, self.n_range, n, ptr(sv), int(sv.shape[0]),
-                               self.start_ping - self.data_ping0, self.start_ping, int(acc.shape[1]), ptr(acc), ptr(cnt),
-                               scratch, seabed=self._limit_line() if spec.seabed_aware else None)
+                               self.start_ping - self.data_ping0, self.start_ping, n_acc, ptr(acc), ptr(cnt),
+                               scratch, seabed=self._limit_line() if spec.seabed_aware else None,
+                               plane_stride=int(data.stride(0)), n_planes=int(data.shape[0]))
 
     def _limit_line(self):
         """The seabed line of a seabed-aware integration, as ``(pointer, index of ping start_ping, length)``: the chunk's
@@ -918,6 +927,7 @@ def predict_survey(reader, segpipe, patch_size, patch_overlap, batch_size, prelo
 
 # ---- echo integration by predicted class: the reduction of the prediction flows (csrc/integrate.hip) ---------------------
 INTEGRATION_CLASSES = ("sandeel", "other", "all")
+INTEGRATE_MAX_FREQS = hip.DEFINES["CRIMAC_INTEGRATE_MAX_FREQS"]      # frequencies of one crimac_integrate_freqs launch
 
 
 class IntegrationSpec:
@@ -928,6 +938,12 @@ class IntegrationSpec:
     readers).  ``mode`` "threshold": a pixel belongs to class k when its stored probability >= ``thresholds[k]``
     (sandeel, other; it may belong to both); "probability": its sv counts with weight = the stored probability.
     ``thresholds`` must be > 0 in both modes.  ``bind(frequencies)`` returns the spec with ``channel`` looked up.
+
+    **Several frequencies** (``crimac_integrate_freqs``).  ``frequency`` as a tuple or list of distinct values, at most
+    ``INTEGRATE_MAX_FREQS``: all of them are integrated in ONE pass over the predictions, and every result has a leading
+    frequency axis in the order given (``sv_sum`` / ``pixels`` ``[F, 3, n_pb, n_rb]``, ``"frequencies"``), also for a
+    sequence of one.  ``bind`` looks up ``channels``; ``n_freqs`` is their number.  A scalar ``frequency`` is the form
+    above: ``channels == (channel,)``, ``n_freqs == 1``, no frequency axis.
 
     **Seabed** (``crimac_integrate_layers``).  ``seabed_offset`` = an integer k (it may be negative): ping p has the row
     limit ``L[p] = clamp(seabed[p] + k, 0, n_range)`` and rows ``r >= L[p]`` count in NO plane, neither sums nor pixels;
@@ -994,6 +1010,18 @@ class IntegrationSpec:
         if len(thresholds) != 2 or not all(0.0 < t < float("inf") for t in thresholds):
             raise ValueError(f"IntegrationSpec: thresholds={thresholds!r}: two finite numbers > 0 (pixels the scatter left "
                              "at 0 belong to no class)")
+        if isinstance(frequency, (tuple, list)):
+            frequency = tuple(frequency)
+            if not frequency:
+                raise ValueError("IntegrationSpec: frequency is an empty sequence: name at least one frequency")
+            if len({float(f) for f in frequency}) != len(frequency):
+                raise ValueError(f"IntegrationSpec: frequency={list(frequency)} names a frequency twice")
+            if len(frequency) > INTEGRATE_MAX_FREQS:
+                raise ValueError(f"IntegrationSpec: {len(frequency)} frequencies, one pass takes {INTEGRATE_MAX_FREQS} at most")
+            if channel is not None:
+                channel = tuple(int(c) for c in channel)
+                if len(channel) != len(frequency):
+                    raise ValueError(f"IntegrationSpec: channel={channel} for {len(frequency)} frequencies")
         self.ping_bin, self.range_bin, self.frequency = None if ping_bin is None else int(ping_bin), int(range_bin), frequency
         self.ping_edges, self._edges_dev = ping_edges, {}
         self.thresholds, self.mode, self.channel = thresholds, mode, channel
@@ -1053,13 +1081,34 @@ class IntegrationSpec:
         return max(pb1 - pb0 + 1, 0)
 
     @property
+    def multi(self):
+        """Whether ``frequency`` is a sequence: results carry a leading frequency axis (``crimac_integrate_freqs``)."""
+        return isinstance(self.frequency, tuple)
+
+    @property
+    def channels(self):
+        """The data planes that are integrated, in the order of ``frequency``: ``(channel,)`` for the scalar form; None for
+        a sequence that ``bind`` has not looked up yet."""
+        return self.channel if self.multi else (self.channel,)
+
+    @property
+    def n_freqs(self):
+        return len(self.frequency) if self.multi else 1
+
+    @property
     def seabed_aware(self):
         """Whether the spec needs the seabed line (``crimac_integrate_layers``) or not (``crimac_integrate_classes``)."""
         return self.seabed_offset is not None
 
     def bind(self, frequencies):
-        """The spec with ``channel`` = the index of its frequency in ``frequencies``; ValueError if it is not there."""
+        """The spec with ``channel`` = the index of its frequency in ``frequencies`` (a sequence: the tuple of indices, in
+        the order given); ValueError if one is not there."""
         freqs = [float(f) for f in frequencies]
+        if self.multi:
+            for f in self.frequency:
+                if float(f) not in freqs:
+                    raise ValueError(f"IntegrationSpec: frequency {f} is not among the model's frequencies {list(frequencies)}")
+            return self._with(tuple(freqs.index(float(f)) for f in self.frequency), self.frequency, self.ping_edges)
         wanted = (38, 38000) if self.frequency is None else (self.frequency,)
         for f in wanted:
             if float(f) in freqs:
@@ -1086,29 +1135,36 @@ class EdsuIntegrationSpec(IntegrationSpec):
 
 
 def new_integration(dev, spec, n_pings, n_range):
-    """Zeroed accumulators of ``ChunkPredictor.integrate`` on ``dev``: (acc float64, cnt int64), both [3, n_pb, n_rb].
+    """Zeroed accumulators of ``ChunkPredictor.integrate`` on ``dev``: (acc float64, cnt int64), both [3, n_pb, n_rb]
+    ([F, 3, n_pb, n_rb] for a spec with a sequence of F frequencies).
     A spec with an edge table: its device copy goes up here (``IntegrationSpec.edges_on``), once per survey."""
-    shape = (3, *spec.bins(n_pings, n_range))
+    shape = ((spec.n_freqs,) if spec.multi else ()) + (3, *spec.bins(n_pings, n_range))
     if spec.ping_edges is not None:
         spec.edges_on(dev)
     return torch.zeros(shape, dtype=torch.float64, device=dev), torch.zeros(shape, dtype=torch.int64, device=dev)
 
 
-def integration_scratch(engine, cells):
+def integration_scratch(engine, cells, n_freqs=1):
     """The scratch of an integrate launch of ``cells`` = (ping bins it touches) x (range bins or layers), from the
-    engine's buffer cache: (cells + INTEGRATE_SPLIT_WGS) slots always suffice."""
-    return engine._buf("integrate.scratch", ((cells + hip.INTEGRATE_SPLIT_WGS) * hip.INTEGRATE_SLOT_BYTES // 8,), torch.float64)
+    engine's buffer cache: (cells + INTEGRATE_SPLIT_WGS) slots always suffice, ``n_freqs`` times that for a launch over
+    several frequencies."""
+    return engine._buf("integrate.scratch", (n_freqs * (cells + hip.INTEGRATE_SPLIT_WGS) * hip.INTEGRATE_SLOT_BYTES // 8,),
+                       torch.float64)
 
 
 def launch_integration(spec, pred, pred_f16, n_range, n_pings, sv, data_pings, sv_ping_off, ping_origin, n_pb_total, acc,
-                       cnt, scratch, seabed=None, edges=None):
+                       cnt, scratch, seabed=None, edges=None, plane_stride=None, n_planes=None):
     """One integrate launch by a bound ``spec``: ``crimac_integrate_classes``, or -- a seabed-aware spec --
     ``crimac_integrate_layers`` with ``seabed`` = (pointer to an int32 line, index of pred's column 0 in it, its length).
     ``pred`` / ``sv`` / ``acc`` / ``cnt``: device pointers (``hip.ptr``); ``scratch``: a float64 tensor.
     A spec with an edge table runs ``crimac_integrate_edges`` (with or without ``seabed``); ``edges``: the device pointer
     of a copy of ``spec.ping_edges`` the caller has uploaded with other tables (default: ``spec.edges_on`` the current
-    device); ``n_pb_total`` must be the table's intervals."""
+    device); ``n_pb_total`` must be the table's intervals.
+    A spec with a sequence of frequencies runs ``crimac_integrate_freqs`` whatever its grid: ``sv`` is then PLANE 0 of the
+    source, ``plane_stride`` the elements between its ``n_planes`` planes, and ``acc`` / ``cnt`` are ``[F, 3, ...]``."""
     mode = IntegrationSpec.MODES.index(spec.mode)
+    if spec.multi and (plane_stride is None or n_planes is None):
+        raise ValueError("launch_integration: a spec with several frequencies needs plane_stride and n_planes (sv: plane 0)")
     if spec.ping_edges is not None:
         host = spec.ping_edges
         if callable(host):
@@ -1119,6 +1175,10 @@ def launch_integration(spec, pred, pred_f16, n_range, n_pings, sv, data_pings, s
             edges = ptr(spec.edges_on(torch.device("cuda", torch.cuda.current_device())))
         sb = seabed if spec.seabed_aware else (None, 0, 0)
         tail = (acc, cnt, ptr(scratch), scratch.numel() * 8)
+        if spec.multi:
+            _launch_freqs(spec, pred, pred_f16, n_range, n_pings, sv, plane_stride, n_planes, data_pings, sv_ping_off, mode,
+                          edges, ctypes.c_void_p(host.ctypes.data), ping_origin, n_pb_total, sb, tail)
+            return
         call("crimac_integrate_edges", pred, 1 if pred_f16 else 0, n_range, n_pings, sv, data_pings, sv_ping_off,
              spec.thresholds[0], spec.thresholds[1], mode, edges, ctypes.c_void_p(host.ctypes.data), spec.range_bin,
              ping_origin, n_pb_total, *sb, spec.seabed_offset or 0, IntegrationSpec.REFERENCES.index(spec.reference),
@@ -1127,11 +1187,26 @@ def launch_integration(spec, pred, pred_f16, n_range, n_pings, sv, data_pings, s
     head = (pred, 1 if pred_f16 else 0, n_range, n_pings, sv, data_pings, sv_ping_off, spec.thresholds[0],
             spec.thresholds[1], mode, spec.ping_bin, spec.range_bin, ping_origin, n_pb_total)
     tail = (acc, cnt, ptr(scratch), scratch.numel() * 8)
-    if not spec.seabed_aware:
+    if spec.multi:
+        _launch_freqs(spec, pred, pred_f16, n_range, n_pings, sv, plane_stride, n_planes, data_pings, sv_ping_off, mode, None,
+                      None, ping_origin, n_pb_total, seabed if spec.seabed_aware else (None, 0, 0), tail)
+    elif not spec.seabed_aware:
         call("crimac_integrate_classes", *head, *tail)
     else:
         call("crimac_integrate_layers", *head, *seabed, spec.seabed_offset, IntegrationSpec.REFERENCES.index(spec.reference),
              spec.layers or 0, *tail)
+
+
+def _launch_freqs(spec, pred, pred_f16, n_range, n_pings, sv, plane_stride, n_planes, data_pings, sv_ping_off, mode, edges_dev,
+                  edges_host, ping_origin, n_pb_total, sb, tail):
+    """``crimac_integrate_freqs`` for ``launch_integration``: the channels go as a host array that lives for the call."""
+    if spec.channels is None:
+        raise ValueError("launch_integration: bind the spec to the model's frequencies first (IntegrationSpec.bind)")
+    channels = (ctypes.c_int * spec.n_freqs)(*spec.channels)
+    call("crimac_integrate_freqs", pred, 1 if pred_f16 else 0, n_range, n_pings, sv, plane_stride, n_planes, channels,
+         spec.n_freqs, data_pings, sv_ping_off, spec.thresholds[0], spec.thresholds[1], mode, spec.ping_bin or 0, edges_dev,
+         edges_host, spec.range_bin, ping_origin, n_pb_total, *sb, spec.seabed_offset or 0,
+         IntegrationSpec.REFERENCES.index(spec.reference), spec.layers or 0, *tail)
 
 
 def finish_integration(acc, cnt, spec, n_pings, n_range, all_reduce=True):
@@ -1149,7 +1224,8 @@ def finish_integration(acc, cnt, spec, n_pings, n_range, all_reduce=True):
 
 
 def integration_result(sv_sum, pixels, spec, n_pings, n_range):
-    """The result dict of ``finish_integration`` around downloaded accumulators (numpy ``[3, n_pb, n_rb]``).  With
+    """The result dict of ``finish_integration`` around downloaded accumulators (numpy ``[3, n_pb, n_rb]``; a spec with a
+    sequence of frequencies: ``[F, 3, n_pb, n_rb]``, and the result names them as ``"frequencies"``).  With
     ``spec.ping_edges`` the result's ``ping_edges`` are the table clipped to ``n_pings``."""
     n_pb, n_rb = spec.bins(n_pings, n_range)
     edges = np.arange(n_rb + 1, dtype=np.int64) * spec.range_bin
@@ -1159,13 +1235,15 @@ def integration_result(sv_sum, pixels, spec, n_pings, n_range):
            "classes": INTEGRATION_CLASSES}
     if spec.seabed_aware:
         res.update(reference=spec.reference, seabed_offset=spec.seabed_offset)
+    if spec.multi:                                           # (sv_sum / pixels [F, 3, n_pb, n_rb], in this order)
+        res["frequencies"] = spec.frequency
     return res
 
 
 def group_shares(group, spec, planes):
     """The layout of a packed group's flat accumulators by a bound ``spec``: ``([(first word, (n_pb, range bins or
     layers))] per record, words)`` -- the echograms' blocks of ``planes`` cells each (3: ``[3, n_pb, n_rb]``, 9: the scored
-    ``[3, 3, n_pb, n_rb]``) one after the other.  A record that carries its own spec (``_MemmEdgeRecord``: the spec with
+    ``[3, 3, n_pb, n_rb]``, 3 F with a spec of F frequencies: ``[F, 3, n_pb, n_rb]``) one after the other.  A record that carries its own spec (``_MemmEdgeRecord``: the spec with
     the echogram's edge table) goes by that one."""
     shares, total = [], 0
     for r in group:
@@ -1178,12 +1256,12 @@ def group_shares(group, spec, planes):
 def group_results(group, shares, sums, counts, spec, planes):
     """The inverse of ``group_shares``: ``(echogram, integration_result)`` per record from a group's downloaded flat
     accumulators (numpy; copied, the pinned buffer is used again); 9 planes: with the ``"annotated"`` classes."""
-    lead = (3,) if planes == 3 else (3, 3)
+    lead = (planes // 3, 3) if spec.multi else (3,) if planes == 3 else (3, 3)       # (scored holders take no multi spec)
     for r, (at, shape) in zip(group, shares):
         n = planes * shape[0] * shape[1]
         res = integration_result(sums[at:at + n].reshape(*lead, *shape).copy(), counts[at:at + n].reshape(*lead, *shape).copy(),
                                  getattr(r, "spec", spec), r.n_pings, r.n_range)
-        if planes == 9:
+        if planes == 9 and not spec.multi:
             res["annotated"] = ANNOTATED_CLASSES
         yield r.echogram, res
 
@@ -1235,6 +1313,25 @@ def mean_nasc(result, range_step_m):
     return np.divide(total, pings, out=np.full(total.shape, np.nan), where=pings > 0)
 
 
+def frequency_response(result, reference=None):
+    """The frequency response r(f) = s_A(f) / s_A(reference) per class and cell of a result with a frequency axis (a spec
+    with a sequence of frequencies): ``sv_sum[f] / sv_sum[reference]``, float64 of ``sv_sum``'s shape ``[F, 3, n_pb, n_rb]``,
+    NaN where the reference sum is 0.  ``reference``: one of ``result["frequencies"]``; None takes 38 or, failing that,
+    38000 (as ``IntegrationSpec.bind``).  ValueError: a result without a frequency axis, a reference that is not there."""
+    if "frequencies" not in result:
+        raise ValueError("frequency_response: the result has no frequency axis (integrate with IntegrationSpec(frequency="
+                         "(f1, f2, ...)))")
+    freqs = [float(f) for f in result["frequencies"]]
+    wanted = (38, 38000) if reference is None else (reference,)
+    at = next((freqs.index(float(f)) for f in wanted if float(f) in freqs), None)
+    if at is None:
+        raise ValueError(f"frequency_response: reference {' / '.join(str(f) for f in wanted)} is not among the result's "
+                         f"frequencies {list(result['frequencies'])}")
+    sums = np.asarray(result["sv_sum"], dtype=np.float64)
+    ref = np.broadcast_to(sums[at], sums.shape)
+    return np.divide(sums, ref, out=np.full(sums.shape, np.nan), where=ref > 0)
+
+
 def ping_bin_edges(track, step, origin=None):
     """The edge table of EDSU cells (``IntegrationSpec(ping_edges=...)``) from a per-ping ``track`` -- the log distance in
     nmi, the reader's ``time_vector``, anything finite and non-decreasing: cell k holds the pings whose track value lies
@@ -1279,6 +1376,9 @@ class _ScoredHolder:
         """``spec`` if a scored holder takes it (``ScoredIntegrationSet`` makes the same checks)."""
         if not isinstance(spec, IntegrationSpec):
             raise TypeError(f"{cls.__name__}: spec is an IntegrationSpec, got {type(spec).__name__}")
+        if spec.multi:
+            raise NotImplementedError(f"{cls.__name__}: a spec with several frequencies is not scored: the confusion kernels "
+                                      "sum one sv plane (score one frequency per holder)")
         if spec.ping_edges is not None:
             raise NotImplementedError(f"{cls.__name__}: a spec with ping_edges (EDSU cells) is not scored: the confusion "
                                       "kernels size a patch's window of cells from a uniform ping_bin")
@@ -2264,6 +2364,7 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
     spec = spec.bind(segpipe.frequencies)
     edsu = spec.ping_edges is not None
     C, W = flow.C, hip.MEMM_DESC_WORDS
+    planes = 3 * spec.n_freqs                # per echogram [3, n_pb, n_rb], or [F, 3, n_pb, n_rb] (crimac_integrate_freqs)
 
     def single(eg, sb, meta):            # the per-echogram path
         return eg, integrate_echogram_memm(eg, segpipe, patch_size, patch_overlap, batch_size, spec, predict_fn=predict_fn,
@@ -2280,19 +2381,19 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
 
     def enqueue(g):
         ring, out = flow.ring(torch.float64), flow.feed.bufs["out"]
-        shares, total = group_shares(g.group, spec, 3)
+        shares, total = group_shares(g.group, spec, planes)
         o_edges = g.o_tail + (g.o_tail & 1)
         acc = ring.zeroed(g.k, 2 * total)            # [sums | counts]
         out[:2 * g.total].zero_()
         flow.predict_group(g, predict_fn)
-        scratch = integration_scratch(flow.eng, max(s[0] * s[1] for _, s in shares))
+        scratch = integration_scratch(flow.eng, max(s[0] * s[1] for _, s in shares), spec.n_freqs)
         data_t = flow.feed.bufs["data_t"][g.k & 1]
         o_sb = 2 * W * g.n + 3 * g.P              # the seabed lines inside ``misc``, one after the other
         for r, off, (at, shape) in zip(g.group, g.offs, shares):
             launch_integration(r.spec if edsu else spec, ptr(out, 2 * off), True, r.n_range, r.n_pings,
-                               ptr(data_t, C * off + spec.channel * r.pixels), r.n_pings, 0, 0, shape[0], ptr(acc, at),
-                               ptr(acc, total + at), scratch, seabed=(ptr(g.misc, o_sb), 0, r.n_pings),
-                               edges=ptr(g.misc, o_edges) if edsu else None)
+                               ptr(data_t, C * off + (0 if spec.multi else spec.channel) * r.pixels), r.n_pings, 0, 0,
+                               shape[0], ptr(acc, at), ptr(acc, total + at), scratch, seabed=(ptr(g.misc, o_sb), 0, r.n_pings),
+                               edges=ptr(g.misc, o_edges) if edsu else None, plane_stride=r.pixels, n_planes=C)
             o_sb += r.n_pings
             o_edges += 2 * (shape[0] + 1) if edsu else 0
         flow.feed.computed()
@@ -2300,7 +2401,7 @@ def integrate_echograms_memm(echograms, segpipe, patch_size, patch_overlap, batc
 
     def take(ticket):
         group, shares, download = ticket
-        return group_results(group, shares, *_DownloadRing.wait_sums_counts(download), spec, 3)
+        return group_results(group, shares, *_DownloadRing.wait_sums_counts(download), spec, planes)
 
     staging = dict(record=functools.partial(_MemmEdgeRecord, spec=spec), tail=tail) if edsu else {}
     yield from flow.run("memm_integrate", single, enqueue, take, out="out", **staging,

@@ -129,7 +129,7 @@ extern "C" {
  * struct passed by pointer (crimac_layer_desc), the meaning of an argument, the set of precisions or the set of entry
  * points changes, and a binding must refuse a library whose version differs from the header it was written against (an
  * older build that happens to export every symbol would walk a descriptor array with the wrong stride).  An ADDITIVE
- * entry point (crimac_integrate_layers, crimac_integrate_edges) does not bump it: nothing an older caller uses has changed, and a binding that
+ * entry point (crimac_integrate_layers, crimac_integrate_edges, crimac_integrate_freqs) does not bump it: nothing an older caller uses has changed, and a binding that
  * needs the new symbol refuses a build without it by looking the symbol up.
  * crimac_layer_desc_size() is sizeof(crimac_layer_desc) as the library was compiled. */
 #define CRIMAC_ABI_VERSION 17
@@ -914,6 +914,31 @@ int crimac_integrate_edges(const void* pred, int pred_f16, int n_range, long n_p
                            const long long* edges_host, int range_bin, long ping_origin, long n_pb_total,
                            const int* seabed, long seabed_first, long seabed_len, int seabed_offset, int reference,
                            int n_layers, double* acc, long long* cnt, void* scratch, long scratch_bytes, void* stream);
+
+/* All of the above for SEVERAL FREQUENCIES in one pass over the predictions (the frequency response of a class needs the
+ * same cells at every frequency, and the predictions do not depend on it).  The arguments of crimac_integrate_edges plus
+ * ping_bin: edges_dev == NULL gives the uniform grid of crimac_integrate_classes / crimac_integrate_layers (edges_host is
+ * not read), otherwise the edge table (ping_bin is not read); seabed == NULL: no row limit.  In place of one sv plane:
+ *   sv points at plane 0 of a source of n_planes planes [data_pings][n_range], plane_stride elements apart (plane_stride >=
+ *     data_pings * n_range: a plane stays inside its stride); channels int32 [n_freqs] on the HOST, read during the call
+ *     only: frequency i is plane channels[i], 0 <= channels[i] < n_planes; 1 <= n_freqs <= CRIMAC_INTEGRATE_MAX_FREQS.
+ *   acc fp64 / cnt int64 [n_freqs][3][n_pb_total][n_rb or n_layers]: slice i accumulates what the single-frequency entry
+ *     point of the same geometry accumulates on plane channels[i].  The pixel rule (sv finite and > 0) goes by that
+ *     frequency's own sv, so the counts of two frequencies may differ.
+ *   The workgroups, the split count and every order of summation are those of the single-frequency launch, whatever
+ *     n_freqs: slice i has THE BITS crimac_integrate_classes / _layers / _edges give on plane channels[i].  (The 16-byte sv
+ *     reads are taken only when every selected plane is 16-byte aligned; the order of the sums does not depend on them.)
+ *   scratch: n_freqs times that of the single-frequency launch; (cells touched + CRIMAC_INTEGRATE_SPLIT_WGS) *
+ *     CRIMAC_INTEGRATE_SLOT_BYTES * n_freqs always suffices.
+ *   A null pointer, n_freqs or a channel out of range, a plane_stride below a plane's size and a scratch too small for
+ *   n_freqs are refused (CRIMAC_ERR_INVALID) before anything is launched, like every error of the other three. */
+#define CRIMAC_INTEGRATE_MAX_FREQS 8
+int crimac_integrate_freqs(const void* pred, int pred_f16, int n_range, long n_pings, const float* sv, long plane_stride,
+                           int n_planes, const int* channels, int n_freqs, long data_pings, long sv_ping_off,
+                           float thr_sandeel, float thr_other, int mode, long ping_bin, const long long* edges_dev,
+                           const long long* edges_host, int range_bin, long ping_origin, long n_pb_total, const int* seabed,
+                           long seabed_first, long seabed_len, int seabed_offset, int reference, int n_layers, double* acc,
+                           long long* cnt, void* scratch, long scratch_bytes, void* stream);
 
 /* Echo integration SCORED AGAINST THE ANNOTATIONS: the sums of crimac_integrate_classes split by the annotated class as
  * well, from one evaluation batch while it is resident (ChunkPredictor.evaluate).  The reference has no counterpart.

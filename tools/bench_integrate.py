@@ -30,7 +30,19 @@ layers_over_host (LH / L).
              edsu_over_device (B / E, medians) next to device_spread ((max - min) / median of leg B's own passes) -- the
              ratio is not fixed in advance.  After the rounds leg E is checked against one untimed host pass (predict_survey
              float16, numpy binning by the table) with the same bound.  Wall times of whole survey passes: the kernels' own
-             time is not measured here."""
+             time is not measured here.
+
+--freqs 18,38,120,200 adds two legs to every round, same survey, same process, alternating:
+
+  F  freqs      -- integrate_survey with IntegrationSpec(frequency=(18, 38, 120, 200)): ONE pass, crimac_integrate_freqs;
+  FL freqs_loop -- the loop of single-frequency integrate_survey calls, one whole pass per frequency: what a user runs
+                   today, on the code path of leg B.
+
+After the rounds every frequency slice of leg F is checked against the loop's result for that frequency: counts equal,
+every sum BIT-equal.  The JSON line gains freqs_over_loop (FL / F, medians: the claim is > 1 by more than the legs' own
+spreads, freqs_spread and freqs_loop_spread = (max - min) / median of each leg's passes) and freqs_over_device (F / B:
+what the extra planes cost next to one single-frequency pass).  Wall times of whole survey passes: the kernels' own time
+is not measured here."""
 import argparse
 import json
 import os
@@ -150,6 +162,7 @@ def main():
     ap.add_argument("--seabed-offset", type=int, default=-5)
     ap.add_argument("--edsu", action="store_true", help="add the EDSU leg: integrate_survey with an edge table")
     ap.add_argument("--edsu-seed", type=int, default=20)
+    ap.add_argument("--freqs", default=None, help="comma-separated frequencies: add the one-pass leg and the loop of passes")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     reader = synth.SyntheticSurveyReader(n_pings=a.pings, n_range=a.range, seabed_index=900, block=4096, schools=40,
@@ -200,6 +213,13 @@ def main():
     if a.edsu:
         espec = ti.IntegrationSpec(None, a.range_bin, mode=a.mode, ping_edges=edsu_table(a.pings, a.ping_bin, a.edsu_seed))
         legs["edsu"] = lambda: ti.integrate_survey(reader, pipe, patch, overlap, a.batch, a.preload, espec)
+    if a.freqs:
+        freqs = tuple(int(f) for f in a.freqs.split(","))
+        fspec = ti.IntegrationSpec(a.ping_bin, a.range_bin, frequency=freqs, mode=a.mode)
+        legs["freqs"] = lambda: ti.integrate_survey(reader, pipe, patch, overlap, a.batch, a.preload, fspec)
+        legs["freqs_loop"] = lambda: [ti.integrate_survey(reader, pipe, patch, overlap, a.batch, a.preload,
+                                                          ti.IntegrationSpec(a.ping_bin, a.range_bin, frequency=f, mode=a.mode))
+                                      for f in freqs]
     times, last = {k: [] for k in legs}, {}
     for rnd in range(-1, a.rounds):                                       # round -1: warm-up (staging, packed weights)
         for name, fn in legs.items():
@@ -254,6 +274,18 @@ def main():
                     device_spread=round((max(dev) - min(dev)) / med["device"], 4),
                     edsu_pixels=[int(ecnt[0].sum()), int(ecnt[1].sum()), int(ecnt[2].sum())],
                     kernel_time_measured=False)
+    if a.freqs:
+        fgot, floop = last["freqs"], last["freqs_loop"]
+        f_counts = all(np.array_equal(fgot["pixels"][i], floop[i]["pixels"]) for i in range(len(freqs)))
+        f_bits = all(fgot["sv_sum"][i].tobytes() == floop[i]["sv_sum"].tobytes() for i in range(len(freqs)))
+        counts_equal, within = counts_equal and f_counts, within and f_bits
+        spread = {k: round((max(times[k]) - min(times[k])) / med[k], 4) for k in ("freqs", "freqs_loop", "device")}
+        line.update(freqs=list(freqs), freqs_counts_equal=f_counts, freqs_sums_bit_equal=f_bits,
+                    freqs_over_loop=round(med["freqs_loop"] / med["freqs"], 4),
+                    freqs_over_device=round(med["freqs"] / med["device"], 4), freqs_spread=spread["freqs"],
+                    freqs_loop_spread=spread["freqs_loop"], device_spread=spread["device"],
+                    freqs_pixels=[int(fgot["pixels"][i, 2].sum()) for i in range(len(freqs))],
+                    counts_equal=counts_equal, sums_within_bound=within, kernel_time_measured=False)
     for k in legs:
         print(f"{k:8s}: {patches} patches, median {med[k]:.3f} s -> {patches / med[k]:.0f} patches/s", flush=True)
     text = json.dumps(line)
