@@ -6,16 +6,19 @@
 // crimac_scatter_patches_ex wrote, ping contiguous) and one frequency plane sv [data_pings][n_range] of the chunk's data
 // (range contiguous).
 //
-// A stream of 8-12 bytes per pixel with one transposed operand.  Pass 1: a workgroup owns (cell, split): it walks tiles
-// split, split + S, ... of the cell's 64 x 64 tiles (pings fastest).  Per tile the sv rows go through an LDS tile
-// [64 pings][64 rows + 1] -- read from global along the range, read back along the pings -- while pred is read from global
-// along the pings by the thread that consumes it, so both global reads are coalesced (16 bytes per lane when the extents
-// and the base addresses allow it, 4 bytes otherwise).  sv outside the cell is staged as 0, which the pixel rule (finite
-// and > 0) then drops like any other empty sample.  Each thread keeps fp64 sums and 64-bit counts over its tiles in tile
-// order; lanes are combined by a butterfly, the four waves in wave order by thread 0, and the six results go to the
-// (cell, split) slot of the scratch.  Pass 2: one thread per cell adds its S slots in split order and does a plain
-// read-add-write of the cell's six outputs.  No atomics anywhere: launches that touch the same cell are ordered by the
-// stream, S depends on the shapes alone, so the result is bit-reproducible for a given chunking.
+// A stream of 8-12 bytes per pixel with one transposed operand.  ONE kernel body and one finish kernel serve every entry
+// point: integrate_freqs_kernel<TP, VEC_SV, VEC_PRED, SEABED, NF> holds the accumulators of NF frequency planes, and
+// crimac_integrate_classes / _layers / _edges are its NF = 1 instantiations on one plane (launch_pass1 is the one place
+// that turns (pred_f16, seabed, vec_sv, vec_pred, n_freqs) into an instantiation).  Pass 1: a workgroup owns (cell, split):
+// it walks tiles split, split + S, ... of the cell's 64 x 64 tiles (pings fastest).  Per tile the sv rows go through an LDS
+// tile [64 pings][64 rows + 1] -- read from global along the range, read back along the pings -- while pred is read from
+// global along the pings by the thread that consumes it, so both global reads are coalesced (16 bytes per lane when the
+// extents and the base addresses allow it, 4 bytes otherwise).  sv outside the cell is staged as 0, which the pixel rule
+// (finite and > 0) then drops like any other empty sample.  Each thread keeps fp64 sums and 64-bit counts over its tiles in
+// tile order; lanes are combined by a butterfly, the four waves in wave order by thread 0, and the six results go to the
+// (cell, split) slot of the scratch.  Pass 2 (integrate_finish_kernel): one thread per (frequency, cell) adds its S slots in
+// split order and does a plain read-add-write of the cell's six outputs.  No atomics anywhere: launches that touch the same
+// cell are ordered by the stream, S depends on the shapes alone, so the result is bit-reproducible for a given chunking.
 //
 // crimac_integrate_layers (the SEABED instantiations of the same kernel): ping p of the launch has a row limit
 // L[p] = clamp(seabed[p] + seabed_offset, 0, n_range) and rows >= L[p] count nowhere.  Surface reference: the cells above,
@@ -27,6 +30,9 @@
 // boxes of neighbouring layers overlap and those tiles are read once per layer.  S is bounded by the tiles of the whole
 // column, whatever the seabed values: a workgroup whose split finds no tile writes a zero slot.
 //
+// crimac_integrate_freqs (NF = 1, 4 or CRIMAC_INTEGRATE_MAX_FREQS by n_freqs): several planes of one source in one pass over
+// the predictions; see the kernel.
+//
 // crimac_integrate_edges (the same kernels once more): the ping extent of cell pb is [edges[pb], edges[pb + 1]) of a device
 // table instead of [pb * ping_bin, (pb + 1) * ping_bin).  The workgroup reads its two edges in the prologue (cell_of), where
 // the index depends on blockIdx alone -- two scalar loads per workgroup, nothing per pixel.  The host reads its own copy of
@@ -36,6 +42,7 @@
 // transformed labels in patch layout -- split by the annotated class as well; crimac_integrate_confusion_multi: the same
 // two kernels for a batch packed from several echograms.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "pr_softmax.h"
@@ -108,8 +115,7 @@ __device__ __forceinline__ void load_pred(const TP* __restrict__ row, long p, lo
   }
 }
 
-// The steps of integrate_cells_kernel as functions, for integrate_freqs_kernel further down (the single-frequency kernel
-// keeps its own text: its code generation is not to change).
+// ---- the steps of a workgroup of integrate_freqs_kernel -------------------------------------------------------------------
 // SEABED prologue of a workgroup: min and max of L over the cell's ping span cut the cell's rows to the box that can hold
 // a counted pixel.  Returns `top`: with the seabed reference the layer ends `top` rows above the limit (0 otherwise).
 __device__ __forceinline__ long seabed_box(const Geom& g, Cell& c, long cell, int t) {
@@ -228,225 +234,17 @@ __device__ __forceinline__ void reduce_to_slot(double s0, double s1, double s2, 
   }
 }
 
-template <typename TP, bool VEC_SV, bool VEC_PRED, bool SEABED>
-__global__ __launch_bounds__(kThreads) void integrate_cells_kernel(const TP* __restrict__ pred, const float* __restrict__ sv,
-                                                                   Geom g, Slot* __restrict__ scratch) {
-  __shared__ float tile[kTile * kPitch];
-  __shared__ Slot wave_part[kThreads / 64];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const long cell = blockIdx.x / g.splits;
-  const int split = (int)(blockIdx.x - cell * g.splits);
-  Cell c = cell_of(g, cell);
-  // SEABED: rows [lo, hi) of a tile's 64 pings; seabed reference: the layer ends `top` rows above the limit
-  __shared__ int row_lo[SEABED ? kTile : 1], row_hi[SEABED ? kTile : 1];
-  const int cell_r0 = c.r0, cell_r1 = c.r1;
-  long top = 0;
-  if constexpr (SEABED) {
-    __shared__ int span_min[kThreads / 64], span_max[kThreads / 64];
-    int lmin = g.n_range, lmax = 0;                             // (every limit lies in [0, n_range])
-    for (long p = c.p0 + t; p < c.p1; p += kThreads) {
-      const int L = row_limit(g, p);
-      lmin = L < lmin ? L : lmin;
-      lmax = L > lmax ? L : lmax;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int a = __shfl_xor(lmin, o, 64), b = __shfl_xor(lmax, o, 64);
-      lmin = a < lmin ? a : lmin;
-      lmax = b > lmax ? b : lmax;
-    }
-    if (lane == 0) span_min[wave] = lmin, span_max[wave] = lmax;
-    __syncthreads();
-    for (int w = 0; w < kThreads / 64; ++w) {
-      lmin = span_min[w] < lmin ? span_min[w] : lmin;
-      lmax = span_max[w] > lmax ? span_max[w] : lmax;
-    }
-    if (g.reference == 1) {                                     // the row bounding box of the layer over the ping span
-      top = (cell % g.n_rb) * g.range_bin;
-      const long b0 = lmin - top - g.range_bin, b1 = lmax - top;
-      c.r0 = (int)(b0 > 0 ? b0 : 0);
-      c.r1 = (int)(b1 > 0 ? b1 : 0);
-    } else {
-      c.r1 = c.r1 < lmax ? c.r1 : lmax;                         // no ping of the span counts a row below
-    }
-  }
-  // tile origins are multiples of 4 in both directions, so that a 16-byte access never straddles an edge it may not cross
-  const int ra = c.r0 & ~3;
-  const long pa = c.p0 & ~3L;
-  const int nrt = c.r1 > c.r0 ? (c.r1 - ra + kTile - 1) / kTile : 0;
-  const long npt = c.p1 > c.p0 ? (c.p1 - pa + kTile - 1) / kTile : 0;
-  const long tiles = nrt * npt;
-  const TP* pred0 = pred;
-  const TP* pred1 = pred + (long)g.n_range * g.n_pings;
-  const int row_in_group = t >> 4, l16 = t & 15;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  long long n0 = 0, n1 = 0, n2 = 0;
-
-  for (long tl = split; tl < tiles; tl += g.splits) {
-    const int tr = ra + (int)(tl / npt) * kTile;             // first row of the tile
-    const long tp = pa + (tl % npt) * kTile;                 // its first ping
-    // ---- sv: global (along the range) -> registers; 0 outside the cell and outside the array
-    float svr[16];
-    if constexpr (VEC_SV) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int i = t + kThreads * k, r = tr + 4 * (i & 15);
-        const long p = tp + (i >> 4);
-        f32x4 x = {0.f, 0.f, 0.f, 0.f};
-        if (r < c.r1 && p >= c.p0 && p < c.p1)                // (r, n_range multiples of 4: r < r1 <= n_range -> r + 3 < n_range)
-          x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(sv + (g.sv_ping_off + p) * g.n_range + r));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) svr[4 * k + j] = (r + j >= c.r0 && r + j < c.r1) ? x[j] : 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const int i = t + kThreads * k, r = tr + (i & 63);
-        const long p = tp + (i >> 6);
-        svr[k] = (r >= c.r0 && r < c.r1 && p >= c.p0 && p < c.p1)
-                     ? __builtin_nontemporal_load(sv + (g.sv_ping_off + p) * g.n_range + r) : 0.f;
-      }
-    }
-    // ---- pred: global (along the pings) -> registers, for the 4 rows x 4 pings this thread consumes
-    float pr0[4][4], pr1[4][4];
-    const long pp = tp + (VEC_PRED ? 4 * l16 : l16);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int r = tr + row_in_group + 16 * k;
-      if (r < c.r1) {
-        load_pred<TP, VEC_PRED>(pred0 + (long)r * g.n_pings, pp, g.n_pings, pr0[k]);
-        load_pred<TP, VEC_PRED>(pred1 + (long)r * g.n_pings, pp, g.n_pings, pr1[k]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pr0[k][j] = pr1[k][j] = 0.f;
-      }
-    }
-    int lo = 0, hi = 0;                                       // SEABED: the rows of ping tp + t that count here
-    if constexpr (SEABED) {
-      if (t < kTile && tp + t >= c.p0 && tp + t < c.p1) {
-        const long L = row_limit(g, tp + t);
-        if (g.reference == 1) {
-          lo = (int)(L - top - g.range_bin > 0 ? L - top - g.range_bin : 0);
-          hi = (int)(L - top > 0 ? L - top : 0);
-        } else {
-          lo = cell_r0;
-          hi = (int)(L < cell_r1 ? L : cell_r1);
-        }
-      }
-    }
-    // ---- sv registers -> LDS tile [ping][row]
-    __syncthreads();                                          // (the previous tile has been consumed)
-    if constexpr (SEABED) {
-      if (t < kTile) row_lo[t] = lo, row_hi[t] = hi;
-    }
-    if constexpr (VEC_SV) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int i = t + kThreads * k;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tile[(i >> 4) * kPitch + 4 * (i & 15) + j] = svr[4 * k + j];
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const int i = t + kThreads * k;
-        tile[(i >> 6) * kPitch + (i & 63)] = svr[k];
-      }
-    }
-    __syncthreads();
-    // ---- the pixel rule
-    int plo[4], phi[4];
-    if constexpr (SEABED) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int pl = VEC_PRED ? 4 * l16 + j : l16 + 16 * j;
-        plo[j] = row_lo[pl] - tr;                               // (relative to the tile's first row)
-        phi[j] = row_hi[pl] - tr;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int rl = row_in_group + 16 * k;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int pl = VEC_PRED ? 4 * l16 + j : l16 + 16 * j;
-        const float s = tile[pl * kPitch + rl];
-        bool ok = s > 0.f && s < __builtin_inff();            // finite and > 0 (NaN fails both)
-        if constexpr (SEABED) ok = ok && rl >= plo[j] && rl < phi[j];
-        const float a = pr0[k][j], b = pr1[k][j];
-        const double sd = ok ? (double)s : 0.0;
-        if (g.mode == 0) {
-          const bool in0 = ok && a >= g.thr0, in1 = ok && b >= g.thr1;
-          s0 += in0 ? sd : 0.0;
-          s1 += in1 ? sd : 0.0;
-          n0 += in0;
-          n1 += in1;
-        } else {
-          const bool in0 = ok && a > 0.f, in1 = ok && b > 0.f;        // (a NaN or negative weight counts as 0)
-          s0 += in0 ? sd * (double)a : 0.0;
-          s1 += in1 ? sd * (double)b : 0.0;
-          n0 += in0;
-          n1 += in1;
-        }
-        s2 += sd;
-        n2 += ok;
-      }
-    }
-  }
-  // ---- lane -> wave -> workgroup, each in a fixed order
-  s0 = wave_sum_d(s0);
-  s1 = wave_sum_d(s1);
-  s2 = wave_sum_d(s2);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    n0 += __shfl_xor(n0, o, 64);
-    n1 += __shfl_xor(n1, o, 64);
-    n2 += __shfl_xor(n2, o, 64);
-  }
-  if (lane == 0) wave_part[wave] = Slot{{s0, s1, s2}, {n0, n1, n2}};
-  __syncthreads();
-  if (t == 0) {
-    Slot out = wave_part[0];
-    for (int w = 1; w < kThreads / 64; ++w)
-      for (int k = 0; k < 3; ++k) {
-        out.sum[k] += wave_part[w].sum[k];
-        out.cnt[k] += wave_part[w].cnt[k];
-      }
-    scratch[blockIdx.x] = out;
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void integrate_finish_kernel(const Slot* __restrict__ scratch, Geom g, long cells,
-                                                                    double* __restrict__ acc, long long* __restrict__ cnt) {
-  const long cell = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (cell >= cells) return;
-  Slot out = scratch[cell * g.splits];
-  for (int s = 1; s < g.splits; ++s) {
-    const Slot& x = scratch[cell * g.splits + s];
-    for (int k = 0; k < 3; ++k) {
-      out.sum[k] += x.sum[k];
-      out.cnt[k] += x.cnt[k];
-    }
-  }
-  const long pb = g.pb0 + cell / g.n_rb, rb = cell % g.n_rb;
-  for (int k = 0; k < 3; ++k) {
-    const long at = ((long)k * g.n_pb_total + pb) * g.n_rb + rb;
-    acc[at] += out.sum[k];
-    cnt[at] += out.cnt[k];
-  }
-}
-
-// ---- crimac_integrate_freqs: the same reduction for SEVERAL frequency planes in one pass over the predictions -----------
-// The workgroup is still (cell, split) and walks the same tiles in the same order.  Per tile the predictions are read once
-// and turned into the two class weights of each of the thread's 16 pixels (threshold mode: 1 or 0; probability mode: the
-// stored value, 0 for a NaN or negative one), the seabed forms read their pings' row intervals once; then the sv tile of each
-// frequency goes through LDS in turn and lands in that frequency's own six accumulators.  Two LDS tile buffers, used
-// alternately, leave ONE barrier per frequency: a thread that writes buffer b again has passed the barrier of the stage in
-// between, which every thread reaches only after it has read b; where registers allow it (kPrefetch) the global loads of the
-// next frequency are issued right after the barrier and fly while the tile is consumed.  The accumulators are indexed by the unrolled frequency loop only,
-// so they stay in registers.  A pixel adds `in ? sv * w : 0` to a class sum, which has the bits of the single-frequency
-// kernel's term in both modes (w = 1 gives sv exactly), in the same tile, pixel, lane, wave and split order: frequency i
-// gets the bits crimac_integrate_classes / _layers / _edges give on its plane.  Its slots are scratch[i * slots + blockIdx.x].
+// ---- pass 1 of every entry point: the reduction for the launch's 1 .. NF frequency planes in one pass over the predictions
+// The workgroup is (cell, split).  Per tile the predictions are read once and turned into the two class weights of each of
+// the thread's 16 pixels (threshold mode: 1 or 0; probability mode: the stored value, 0 for a NaN or negative one), the
+// seabed forms read their pings' row intervals once; then the sv tile of each frequency goes through LDS in turn and lands
+// in that frequency's own six accumulators.  Two LDS tile buffers, used alternately, leave ONE barrier per (tile,
+// frequency): a thread that writes buffer b again has passed the barrier of the stage in between, which every thread
+// reaches only after it has read b; where registers allow it (kPrefetch) the global loads of the next frequency are issued
+// right after the barrier and fly while the tile is consumed.  The accumulators are indexed by the unrolled frequency loop
+// only, so they stay in registers.  A pixel adds `in ? sv * w : 0` to a class sum (w = 1 gives sv exactly), in tile, pixel,
+// lane, wave and split order, whatever NF: frequency i of crimac_integrate_freqs gets the bits crimac_integrate_classes /
+// _layers / _edges (NF = 1, plane offset 0) give on its plane.  Its slots are scratch[i * slots + blockIdx.x].
 constexpr int kMaxFreqs = CRIMAC_INTEGRATE_MAX_FREQS;
 struct Planes {
   int n;                   // frequencies of the launch
@@ -580,15 +378,14 @@ __global__ __launch_bounds__(kThreads) void integrate_freqs_kernel(const TP* __r
   }
 }
 
-// one thread per (frequency, cell): the slots of that frequency in split order, then the plain read-add-write into its
-// [3][n_pb_total][n_rb] slice
-__global__ __launch_bounds__(kThreads) void integrate_freqs_finish_kernel(const Slot* __restrict__ scratch, Geom g, Planes fq,
-                                                                          long cells, double* __restrict__ acc,
-                                                                          long long* __restrict__ cnt) {
+// Pass 2 of every entry point, one thread per (frequency, cell): the slots of that frequency in split order, then the plain
+// read-add-write into its [3][n_pb_total][n_rb] slice.  One frequency: n = 1, f = 0 and the grid is ceil(cells / 256).
+__global__ __launch_bounds__(kThreads) void integrate_finish_kernel(const Slot* __restrict__ scratch, Geom g, int n, long cells,
+                                                                    double* __restrict__ acc, long long* __restrict__ cnt) {
   const long i = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= cells * fq.n) return;
+  if (i >= cells * n) return;
   const long f = i / cells, cell = i - f * cells;
-  const Slot* __restrict__ slots = scratch + f * fq.slots + cell * g.splits;
+  const Slot* __restrict__ slots = scratch + (f * cells + cell) * g.splits;      // (a frequency's slots: cells * splits)
   Slot out = slots[0];
   for (int s = 1; s < g.splits; ++s)
     for (int k = 0; k < 3; ++k) {
@@ -603,16 +400,6 @@ __global__ __launch_bounds__(kThreads) void integrate_freqs_finish_kernel(const 
   }
 }
 
-template <typename TP, bool SEABED>
-void launch_cells(bool vec_sv, bool vec_pred, unsigned blocks, hipStream_t st, const void* pred, const float* sv,
-                  const Geom& g, Slot* scratch) {
-  const TP* p = static_cast<const TP*>(pred);
-  if (vec_sv && vec_pred) hipLaunchKernelGGL((integrate_cells_kernel<TP, true, true, SEABED>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
-  else if (vec_sv) hipLaunchKernelGGL((integrate_cells_kernel<TP, true, false, SEABED>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
-  else if (vec_pred) hipLaunchKernelGGL((integrate_cells_kernel<TP, false, true, SEABED>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
-  else hipLaunchKernelGGL((integrate_cells_kernel<TP, false, false, SEABED>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, scratch);
-}
-
 // what crimac_integrate_layers adds to the arguments of crimac_integrate_classes (null: that entry point)
 struct SeabedArgs { const int* line; long first, len; int offset, reference, n_layers; };
 
@@ -622,22 +409,22 @@ struct EdgeArgs { const long long* dev; const long long* host; };
 // what crimac_integrate_freqs adds: the planes of the source and the selected ones (null: one plane, the other entry points)
 struct FreqArgs { long plane_stride; int n_planes; const int* channels; int n_freqs; };
 
-template <typename TP, bool SEABED, int NF>
-void launch_freqs(bool vec_sv, bool vec_pred, unsigned blocks, hipStream_t st, const void* pred, const float* sv, const Geom& g,
-                  const Planes& fq, Slot* scratch) {
-  const TP* p = static_cast<const TP*>(pred);
-  if (vec_sv && vec_pred) hipLaunchKernelGGL((integrate_freqs_kernel<TP, true, true, SEABED, NF>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, fq, scratch);
-  else if (vec_sv) hipLaunchKernelGGL((integrate_freqs_kernel<TP, true, false, SEABED, NF>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, fq, scratch);
-  else if (vec_pred) hipLaunchKernelGGL((integrate_freqs_kernel<TP, false, true, SEABED, NF>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, fq, scratch);
-  else hipLaunchKernelGGL((integrate_freqs_kernel<TP, false, false, SEABED, NF>), dim3(blocks), dim3(kThreads), 0, st, p, sv, g, fq, scratch);
-}
+// a run-time flag as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <typename F> void with_flag(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
 
-// the instantiation by the accumulators it holds: 4 frequencies (the models' four) or CRIMAC_INTEGRATE_MAX_FREQS
-template <typename TP, bool SEABED>
-void launch_freqs(bool vec_sv, bool vec_pred, unsigned blocks, hipStream_t st, const void* pred, const float* sv, const Geom& g,
-                  const Planes& fq, Slot* scratch) {
-  if (fq.n <= 4) launch_freqs<TP, SEABED, 4>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, scratch);
-  else launch_freqs<TP, SEABED, kMaxFreqs>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, scratch);
+// Pass 1 of every entry point: (pred_f16, seabed, vec_sv, vec_pred) -> the instantiation of integrate_freqs_kernel, and NF by
+// the accumulators it holds: 1 (the single-frequency entry points), 4 (the models' four) or CRIMAC_INTEGRATE_MAX_FREQS.
+void launch_pass1(bool pred_f16, bool seabed, bool vec_sv, bool vec_pred, unsigned blocks, hipStream_t st, const void* pred,
+                  const float* sv, const Geom& g, const Planes& fq, Slot* scratch) {
+  with_flag(pred_f16, [&](auto f16) { with_flag(seabed, [&](auto sb) { with_flag(vec_sv, [&](auto vs) { with_flag(vec_pred, [&](auto vp) {
+    using TP = std::conditional_t<decltype(f16)::value, half_t, float>;
+    constexpr bool SB = decltype(sb)::value, VS = decltype(vs)::value, VP = decltype(vp)::value;
+    const TP* p = static_cast<const TP*>(pred);
+    const dim3 grid(blocks), block(kThreads);
+    if (fq.n == 1) hipLaunchKernelGGL((integrate_freqs_kernel<TP, VS, VP, SB, 1>), grid, block, 0, st, p, sv, g, fq, scratch);
+    else if (fq.n <= 4) hipLaunchKernelGGL((integrate_freqs_kernel<TP, VS, VP, SB, 4>), grid, block, 0, st, p, sv, g, fq, scratch);
+    else hipLaunchKernelGGL((integrate_freqs_kernel<TP, VS, VP, SB, kMaxFreqs>), grid, block, 0, st, p, sv, g, fq, scratch);
+  }); }); }); });
 }
 
 // The cells [pb0, pb1] of a checked host table that global pings [a, b) touch (pb1 < pb0: none) and their widest extent.
@@ -742,37 +529,17 @@ int integrate(const char* who, const SeabedArgs* sb, const EdgeArgs* ed, const F
   const bool vec_pred = n_pings % 4 == 0 && (uintptr_t)pred % (pred_f16 ? 8 : 16) == 0;
   const hipStream_t st = (hipStream_t)stream;
   const unsigned blocks = (unsigned)(cells * g.splits);
-  if (fa) {
-    Planes fq{};
-    fq.n = fa->n_freqs;
-    fq.slots = cells * g.splits;
-    for (int i = 0; i < fq.n; ++i) {
-      fq.off[i] = fa->channels[i] * fa->plane_stride;
-      vec_sv = vec_sv && (uintptr_t)(sv + fq.off[i]) % 16 == 0;    // the 16-byte reads only if EVERY selected plane allows them
-    }
-    if (sb) {
-      if (pred_f16) launch_freqs<half_t, true>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, (Slot*)scratch);
-      else launch_freqs<float, true>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, (Slot*)scratch);
-    } else {
-      if (pred_f16) launch_freqs<half_t, false>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, (Slot*)scratch);
-      else launch_freqs<float, false>(vec_sv, vec_pred, blocks, st, pred, sv, g, fq, (Slot*)scratch);
-    }
-    CRIMAC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(integrate_freqs_finish_kernel, dim3((unsigned)((cells * fq.n + kThreads - 1) / kThreads)), dim3(kThreads),
-                       0, st, (const Slot*)scratch, g, fq, cells, acc, cnt);
-    CRIMAC_LAUNCH_CHECK();
-    return CRIMAC_OK;
+  Planes fq{};
+  fq.n = (int)n_freqs;
+  fq.slots = cells * g.splits;
+  for (int i = 0; fa && i < fq.n; ++i) {
+    fq.off[i] = fa->channels[i] * fa->plane_stride;
+    vec_sv = vec_sv && (uintptr_t)(sv + fq.off[i]) % 16 == 0;      // the 16-byte reads only if EVERY selected plane allows them
   }
-  if (sb) {
-    if (pred_f16) launch_cells<half_t, true>(vec_sv, vec_pred, blocks, st, pred, sv, g, (Slot*)scratch);
-    else launch_cells<float, true>(vec_sv, vec_pred, blocks, st, pred, sv, g, (Slot*)scratch);
-  } else {
-    if (pred_f16) launch_cells<half_t, false>(vec_sv, vec_pred, blocks, st, pred, sv, g, (Slot*)scratch);
-    else launch_cells<float, false>(vec_sv, vec_pred, blocks, st, pred, sv, g, (Slot*)scratch);
-  }
+  launch_pass1(pred_f16, sb, vec_sv, vec_pred, blocks, st, pred, sv, g, fq, (Slot*)scratch);
   CRIMAC_LAUNCH_CHECK();
-  hipLaunchKernelGGL(integrate_finish_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                     (const Slot*)scratch, g, cells, acc, cnt);
+  hipLaunchKernelGGL(integrate_finish_kernel, dim3((unsigned)((cells * fq.n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                     (const Slot*)scratch, g, fq.n, cells, acc, cnt);
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
 }

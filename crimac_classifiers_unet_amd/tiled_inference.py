@@ -1165,48 +1165,34 @@ def launch_integration(spec, pred, pred_f16, n_range, n_pings, sv, data_pings, s
     mode = IntegrationSpec.MODES.index(spec.mode)
     if spec.multi and (plane_stride is None or n_planes is None):
         raise ValueError("launch_integration: a spec with several frequencies needs plane_stride and n_planes (sv: plane 0)")
-    if spec.ping_edges is not None:
-        host = spec.ping_edges
-        if callable(host):
+    table = spec.ping_edges
+    if table is not None:
+        if callable(table):
             raise ValueError("launch_integration: ping_edges is a callable: IntegrationSpec.resolve(source) it first")
-        if n_pb_total != len(host) - 1:
-            raise ValueError(f"launch_integration: n_pb_total={n_pb_total} for an edge table of {len(host) - 1} cells")
+        if n_pb_total != len(table) - 1:
+            raise ValueError(f"launch_integration: n_pb_total={n_pb_total} for an edge table of {len(table) - 1} cells")
         if edges is None:
             edges = ptr(spec.edges_on(torch.device("cuda", torch.cuda.current_device())))
-        sb = seabed if spec.seabed_aware else (None, 0, 0)
-        tail = (acc, cnt, ptr(scratch), scratch.numel() * 8)
-        if spec.multi:
-            _launch_freqs(spec, pred, pred_f16, n_range, n_pings, sv, plane_stride, n_planes, data_pings, sv_ping_off, mode,
-                          edges, ctypes.c_void_p(host.ctypes.data), ping_origin, n_pb_total, sb, tail)
-            return
-        call("crimac_integrate_edges", pred, 1 if pred_f16 else 0, n_range, n_pings, sv, data_pings, sv_ping_off,
-             spec.thresholds[0], spec.thresholds[1], mode, edges, ctypes.c_void_p(host.ctypes.data), spec.range_bin,
-             ping_origin, n_pb_total, *sb, spec.seabed_offset or 0, IntegrationSpec.REFERENCES.index(spec.reference),
-             spec.layers or 0, *tail)
-        return
-    head = (pred, 1 if pred_f16 else 0, n_range, n_pings, sv, data_pings, sv_ping_off, spec.thresholds[0],
-            spec.thresholds[1], mode, spec.ping_bin, spec.range_bin, ping_origin, n_pb_total)
+    if spec.multi and spec.channels is None:
+        raise ValueError("launch_integration: bind the spec to the model's frequencies first (IntegrationSpec.bind)")
+    # the argument groups of the four entry points, each built once
+    head = (pred, 1 if pred_f16 else 0, n_range, n_pings, sv)
+    rule = (data_pings, sv_ping_off, spec.thresholds[0], spec.thresholds[1], mode)
+    grid = (spec.range_bin, ping_origin, n_pb_total)
+    edge_pair = (None, None) if table is None else (edges, ctypes.c_void_p(table.ctypes.data))
+    sb = (*(seabed if spec.seabed_aware else (None, 0, 0)), spec.seabed_offset or 0,
+          IntegrationSpec.REFERENCES.index(spec.reference), spec.layers or 0)
     tail = (acc, cnt, ptr(scratch), scratch.numel() * 8)
     if spec.multi:
-        _launch_freqs(spec, pred, pred_f16, n_range, n_pings, sv, plane_stride, n_planes, data_pings, sv_ping_off, mode, None,
-                      None, ping_origin, n_pb_total, seabed if spec.seabed_aware else (None, 0, 0), tail)
-    elif not spec.seabed_aware:
-        call("crimac_integrate_classes", *head, *tail)
+        channels = (ctypes.c_int * spec.n_freqs)(*spec.channels)      # a host array: it lives until the call returns
+        call("crimac_integrate_freqs", *head, plane_stride, n_planes, channels, spec.n_freqs, *rule, spec.ping_bin or 0,
+             *edge_pair, *grid, *sb, *tail)
+    elif table is not None:
+        call("crimac_integrate_edges", *head, *rule, *edge_pair, *grid, *sb, *tail)
+    elif spec.seabed_aware:
+        call("crimac_integrate_layers", *head, *rule, spec.ping_bin, *grid, *sb, *tail)
     else:
-        call("crimac_integrate_layers", *head, *seabed, spec.seabed_offset, IntegrationSpec.REFERENCES.index(spec.reference),
-             spec.layers or 0, *tail)
-
-
-def _launch_freqs(spec, pred, pred_f16, n_range, n_pings, sv, plane_stride, n_planes, data_pings, sv_ping_off, mode, edges_dev,
-                  edges_host, ping_origin, n_pb_total, sb, tail):
-    """``crimac_integrate_freqs`` for ``launch_integration``: the channels go as a host array that lives for the call."""
-    if spec.channels is None:
-        raise ValueError("launch_integration: bind the spec to the model's frequencies first (IntegrationSpec.bind)")
-    channels = (ctypes.c_int * spec.n_freqs)(*spec.channels)
-    call("crimac_integrate_freqs", pred, 1 if pred_f16 else 0, n_range, n_pings, sv, plane_stride, n_planes, channels,
-         spec.n_freqs, data_pings, sv_ping_off, spec.thresholds[0], spec.thresholds[1], mode, spec.ping_bin or 0, edges_dev,
-         edges_host, spec.range_bin, ping_origin, n_pb_total, *sb, spec.seabed_offset or 0,
-         IntegrationSpec.REFERENCES.index(spec.reference), spec.layers or 0, *tail)
+        call("crimac_integrate_classes", *head, *rule, spec.ping_bin, *grid, *tail)
 
 
 def finish_integration(acc, cnt, spec, n_pings, n_range, all_reduce=True):
