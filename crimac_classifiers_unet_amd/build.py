@@ -16,7 +16,7 @@ LIB_NAME = "libcrimac_unet_hip.so"
 LIB_PATH = os.path.join(PKG_DIR, LIB_NAME)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "crimac_unet_hip.h")      # the C ABI: compiled from, and read by hip.py
 MEMM_META_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "crimac_memm_meta.h")      # crimac_memm_meta_desc: likewise
-SOURCES = ["conv3x3.hip", "conv3x3_glds.hip", "igemm.hip", "upconv.hip", "wgrad.hip", "elementwise.hip", "pack.hip", "upsample.hip", "narrow.hip", "tiling.hip", "augment.hip", "labels.hip", "meta.hip", "seabed.hip", "calib.hip", "integrate.hip"]
+SOURCES = ["conv3x3.hip", "conv3x3_glds.hip", "igemm.hip", "upconv.hip", "wgrad.hip", "elementwise.hip", "pack.hip", "upsample.hip", "narrow.hip", "tiling.hip", "augment.hip", "labels.hip", "meta.hip", "seabed.hip", "calib.hip", "integrate.hip", "schools.hip"]
 def _headers():
     """Every header a source may include: csrc/*.h plus the public C-ABI headers."""
     import glob

@@ -268,6 +268,23 @@ class ChunkPredictor:
                                scratch, seabed=self._limit_line() if spec.seabed_aware else None,
                                plane_stride=int(data.stride(0)), n_planes=int(data.shape[0]))
 
+    def detect_schools(self, spec, keep_left=False, keep_right=False):
+        """The schools of the chunk ``predict`` has just filled: per class of ``spec`` (a bound ``SchoolSpec``) one
+        ``crimac_schools_label`` of its plane of ``self.out`` and one ``crimac_schools_stats`` against the resident sv
+        planes, on the current stream.  Returns a list of ``SchoolTable`` (device tensors, nothing has been waited for);
+        ``SchoolTable.numpy()`` downloads one.  ``keep_left`` / ``keep_right``: keep every school that touches the first /
+        last ping column whatever its size (the chunk has a neighbour there: ``merge_school_chunks``)."""
+        if self.wide or self.out is None:
+            raise ValueError("ChunkPredictor.detect_schools: the chunk was loaded for evaluate() (wide=True) and has no predictions")
+        if spec.channels is None:
+            raise ValueError("ChunkPredictor.detect_schools: bind the spec to the model's frequencies first (SchoolSpec.bind)")
+        for ch in spec.channels:
+            if not 0 <= ch < self.data.shape[0]:
+                raise ValueError(f"ChunkPredictor.detect_schools: channel {ch} of {self.data.shape[0]} data planes")
+        if not self.data.is_contiguous():
+            raise ValueError("ChunkPredictor.detect_schools: the chunk's data must be contiguous [C, pings, range]")
+        return [SchoolTable(self, spec, k, bool(keep_left), bool(keep_right)) for k in spec.classes]
+
     def _limit_line(self):
         """The seabed line of a seabed-aware integration, as ``(pointer, index of ping start_ping, length)``: the chunk's
         seabed vector; for a chunk that holds a 2-D mask instead -- a zarr block the vector could not express
@@ -1834,6 +1851,293 @@ def integrate_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_
     acc, cnt = new_integration(segpipe.device, spec, cp.end_ping, cp.n_range)
     cp.integrate(acc, cnt, spec)
     return finish_integration(acc, cnt, spec, cp.end_ping, cp.n_range, all_reduce=False)
+
+
+# ---- schools from the predictions: connected regions of a class (csrc/schools.hip) ----------------------------------------
+SCHOOL_CLASSES = {1: "sandeel", 2: "other"}          # class k reads plane k - 1 of the predictions
+SCHOOLS_MAX_FREQS = hip.DEFINES["CRIMAC_SCHOOLS_MAX_FREQS"]
+SCHOOL_FIELDS = ("anchor", "pixels", "bbox", "row_sum", "ping_sum", "sv_sum", "sv_pixels")
+
+
+class SchoolSpec:
+    """What a school is.  ``classes``: a subset of (1, 2) = (sandeel, other); class k is detected on plane k - 1 of the
+    predictions with ``thresholds[k - 1]``: a pixel is foreground when its stored probability >= the threshold (> 0, so
+    that pixels the scatter never wrote are background).  ``connectivity`` 4 or 8.  ``min_pixels``: schools with fewer
+    pixels are dropped (after the chunks of a survey have been merged).  ``frequency``: the frequencies whose linear sv
+    is summed per school, a value of ``segpipe.frequencies`` or a sequence of distinct ones (at most ``SCHOOLS_MAX_FREQS``);
+    None takes 38 (kHz) or, failing that, 38000 (Hz), as ``IntegrationSpec``.  Results always carry a frequency axis
+    (``sv_sum`` ``[F, K]``), F = 1 for a scalar.  ``max_schools``: the rows of the device table of one chunk and class; a
+    chunk with more schools is reduced a second time with the count it reported.  ``bind(frequencies)`` returns the spec
+    with ``channels`` looked up."""
+
+    def __init__(self, classes=(1,), thresholds=(0.5, 0.5), connectivity=8, min_pixels=1, frequency=None, max_schools=65536):
+        def integer(v):
+            return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        try:
+            classes = tuple(classes)
+        except TypeError:
+            raise ValueError(f"SchoolSpec: classes={classes!r}: a sequence out of (1, 2) = (sandeel, other)") from None
+        if not classes or len(set(classes)) != len(classes) or not all(integer(k) and k in SCHOOL_CLASSES for k in classes):
+            raise ValueError(f"SchoolSpec: classes={classes!r}: a non-empty sequence of distinct classes out of (1, 2) = "
+                             "(sandeel, other)")
+        try:
+            thresholds = tuple(float(t) for t in thresholds)
+        except TypeError:
+            raise ValueError(f"SchoolSpec: thresholds={thresholds!r}: two numbers (sandeel, other)") from None
+        if len(thresholds) != 2 or not all(0.0 < t < float("inf") for t in thresholds):
+            raise ValueError(f"SchoolSpec: thresholds={thresholds!r}: two finite numbers > 0 (pixels the scatter left at 0 "
+                             "are background)")
+        if connectivity not in (4, 8) or not integer(connectivity):
+            raise ValueError(f"SchoolSpec: connectivity={connectivity!r}: 4 or 8")
+        if not integer(min_pixels) or min_pixels < 1:
+            raise ValueError(f"SchoolSpec: min_pixels={min_pixels!r} must be a positive integer")
+        if not integer(max_schools) or not 1 <= max_schools < 2 ** 31:
+            raise ValueError(f"SchoolSpec: max_schools={max_schools!r} must be a positive integer below 2^31")
+        if isinstance(frequency, (tuple, list)):
+            frequency = tuple(frequency)
+            if not frequency:
+                raise ValueError("SchoolSpec: frequency is an empty sequence: name at least one frequency")
+            if len({float(f) for f in frequency}) != len(frequency):
+                raise ValueError(f"SchoolSpec: frequency={list(frequency)} names a frequency twice")
+            if len(frequency) > SCHOOLS_MAX_FREQS:
+                raise ValueError(f"SchoolSpec: {len(frequency)} frequencies, one pass takes {SCHOOLS_MAX_FREQS} at most")
+        self.classes = tuple(int(k) for k in classes)
+        self.thresholds, self.connectivity, self.min_pixels = thresholds, int(connectivity), int(min_pixels)
+        self.frequency, self.max_schools = frequency, int(max_schools)
+        self.channels = None               # the data planes of ``frequencies``, looked up by ``bind``
+
+    @property
+    def frequencies(self):
+        """The frequencies as a tuple; None for a scalar spec that ``bind`` has not resolved (None: 38 or 38000)."""
+        if isinstance(self.frequency, tuple):
+            return self.frequency
+        return None if self.frequency is None else (self.frequency,)
+
+    def bind(self, frequencies):
+        """The spec with ``channels`` = the indices of its frequencies in ``frequencies``; ValueError if one is not there."""
+        freqs = [float(f) for f in frequencies]
+        wanted = self.frequencies
+        if wanted is None:
+            wanted = next(((f,) for f in (38, 38000) if float(f) in freqs), None)
+            if wanted is None:
+                raise ValueError(f"SchoolSpec: frequency 38 / 38000 is not among the model's frequencies {list(frequencies)}")
+        for f in wanted:
+            if float(f) not in freqs:
+                raise ValueError(f"SchoolSpec: frequency {f} is not among the model's frequencies {list(frequencies)}")
+        bound = SchoolSpec(self.classes, self.thresholds, self.connectivity, self.min_pixels,
+                           wanted if isinstance(self.frequency, tuple) else wanted[0], self.max_schools)
+        bound.channels = tuple(freqs.index(float(f)) for f in wanted)
+        return bound
+
+
+class SchoolTable:
+    """The schools of one class of one resident chunk, on the GPU (``ChunkPredictor.detect_schools``): ``labels`` int32
+    ``[n_range, n_pings]`` (-1 background, otherwise the linear index of the school's first pixel in raster order, its
+    anchor), the table ``anchor`` / ``pixels`` / ``bbox`` / ``row_sum`` / ``ping_sum`` ``[capacity]``, ``sv_sum`` /
+    ``sv_pixels`` ``[F, capacity]`` in ascending anchor order, ``found`` int64 [1] (the true count), ``edges`` int32
+    ``[2, n_range]`` (the first and last ping column as school indices) and ``status`` int32 [1].  Everything is enqueued
+    on the stream that was current; nothing has been waited for."""
+
+    def __init__(self, cp, spec, klass, keep_left, keep_right):
+        self.cp, self.spec, self.klass, self.keep = cp, spec, klass, (keep_left, keep_right)
+        self.n_range, self.n_pings, self.start_ping = cp.n_range, cp.end_ping - cp.start_ping, cp.start_ping
+        dev = cp.out.device
+        eng = cp.engine
+        self.labels = eng._buf(f"schools.labels.{klass}", (self.n_range, self.n_pings), torch.int32)
+        self.status = torch.empty(1, dtype=torch.int32, device=dev)
+        self.found = torch.empty(1, dtype=torch.int64, device=dev)
+        self.edges = torch.empty((2, self.n_range), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            call("crimac_schools_label", ptr(cp.out[klass - 1]), 1 if cp.out_f16 else 0, self.n_range, self.n_pings,
+                 spec.thresholds[klass - 1], spec.connectivity, ptr(self.labels), ptr(self.status))
+        self._stats(spec.max_schools)
+
+    def _stats(self, capacity):
+        cp, spec, F = self.cp, self.spec, len(self.spec.channels)
+        dev = cp.out.device
+        self.capacity = K = int(capacity)
+        i32 = torch.empty(5 * K, dtype=torch.int32, device=dev)
+        i64 = torch.empty((3 + F) * K, dtype=torch.int64, device=dev)
+        self.anchor, self.bbox = i32[:K], i32[K:].view(K, 4)
+        self.pixels, self.row_sum, self.ping_sum, self.sv_pixels = i64[:K], i64[K:2 * K], i64[2 * K:3 * K], i64[3 * K:].view(F, K)
+        self.sv_sum = torch.empty((F, K), dtype=torch.float64, device=dev)
+        n = self.n_range * self.n_pings
+        scratch = cp.engine._buf("schools.scratch", ((hip.DEFINES["CRIMAC_SCHOOLS_SCRATCH_PIXEL_BYTES"] * n + 16 + 7) // 8,),
+                                 torch.float64)
+        channels = (ctypes.c_int * F)(*spec.channels)          # a host array: it lives until the call returns
+        with torch.cuda.device(dev):
+            call("crimac_schools_stats", ptr(self.labels), self.n_range, self.n_pings, ptr(cp.data[0]), int(cp.data.stride(0)),
+                 int(cp.data.shape[0]), channels, F, int(cp.data.shape[1]), cp.start_ping - cp.data_ping0, spec.min_pixels,
+                 int(self.keep[0]), int(self.keep[1]), K, ptr(self.anchor), ptr(self.pixels), ptr(self.bbox), ptr(self.row_sum),
+                 ptr(self.ping_sum), ptr(self.sv_sum), ptr(self.sv_pixels), ptr(self.found), ptr(self.edges), ptr(scratch),
+                 scratch.numel() * 8)
+
+    def numpy(self):
+        """Download the table (this waits for the stream): a chunk-local dict for ``merge_school_chunks`` -- the
+        ``SCHOOL_FIELDS`` cut to the schools found, ``"edges"``, ``"start_ping"``, ``"n_pings"``, ``"n_range"``, ``"class"``,
+        ``"frequencies"``.  A chunk with more schools than the table's rows is reduced once more with the count it
+        reported -- the one case that launches again; the chunk must still be resident, so download before the next
+        ``load_chunk``."""
+        found = int(self.found.item())
+        if int(self.status.item()) != 0:
+            raise hip.HipLibraryError("crimac_schools_label: a union-find loop exceeded its iteration bound (status 1): the "
+                                      "labels of this chunk are invalid")
+        if found > self.capacity:
+            self._stats(found)
+            found = int(self.found.item())
+        res = {name: getattr(self, name)[..., :found].cpu().numpy() if name in ("sv_sum", "sv_pixels")
+               else getattr(self, name)[:found].cpu().numpy() for name in SCHOOL_FIELDS}
+        res.update(edges=self.edges.cpu().numpy(), start_ping=self.start_ping, n_pings=self.n_pings, n_range=self.n_range)
+        res["class"] = SCHOOL_CLASSES[self.klass]
+        res["frequencies"] = self.spec.frequencies
+        return res
+
+
+def merge_school_chunks(chunks, connectivity, min_pixels):
+    """The schools of a survey from the chunk-local tables of ONE class (``SchoolTable.numpy()``; numpy only), ``chunks``
+    in ascending ping order, each starting where the one before ends.  Schools of neighbouring chunks are one school when
+    a foreground pixel of the last column of chunk i and one of the first column of chunk i + 1 lie in rows that differ by
+    0 (``connectivity`` 4) or by at most 1 (8) -- read from the ``"edges"`` columns.  Merging adds ``pixels``, ``row_sum``,
+    ``ping_sum``, ``sv_pixels`` and (in ascending chunk order) ``sv_sum``, unites the boxes and takes the smallest (row,
+    global ping) anchor; ``min_pixels`` is applied after the merge.  Returns a dict of arrays sorted by (anchor row, anchor
+    ping), pings global: ``"anchor"`` int64 [K, 2], ``"pixels"``, ``"bbox"`` [K, 4] (r0, r1, p0, p1 half-open), ``"row_sum"``,
+    ``"ping_sum"``, ``"sv_sum"`` float64 [F, K], ``"sv_pixels"`` int64 [F, K], ``"frequencies"``, ``"class"``."""
+    if connectivity not in (4, 8):
+        raise ValueError(f"merge_school_chunks: connectivity={connectivity!r}: 4 or 8")
+    if not chunks:
+        raise ValueError("merge_school_chunks: no chunks")
+    for a, b in zip(chunks, chunks[1:]):
+        if a["start_ping"] + a["n_pings"] != b["start_ping"] or a["n_range"] != b["n_range"]:
+            raise ValueError("merge_school_chunks: the chunks must follow each other in ping order with one range axis")
+    first = np.cumsum([0] + [len(c["anchor"]) for c in chunks])        # the global id of a chunk's school 0
+    parent = np.arange(first[-1])
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+    for i, (a, b) in enumerate(zip(chunks, chunks[1:])):
+        right, left = np.asarray(a["edges"][1], dtype=np.int64), np.asarray(b["edges"][0], dtype=np.int64)
+        n = len(right)
+        for d in ((0,) if connectivity == 4 else (-1, 0, 1)):            # row of the right chunk = row of the left + d
+            ra, rb = right[max(0, -d):n - max(0, d)], left[max(0, d):n - max(0, -d)]
+            both = (ra >= 0) & (rb >= 0)
+            for x, y in np.unique(np.stack([ra[both] + first[i], rb[both] + first[i + 1]], axis=1), axis=0):
+                x, y = find(x), find(y)
+                if x != y:
+                    parent[max(x, y)] = min(x, y)
+    total = int(first[-1])
+    root = np.array([find(x) for x in range(total)], dtype=np.int64)
+    roots, group = np.unique(root, return_inverse=True)
+    G, F = len(roots), chunks[0]["sv_sum"].shape[0]
+    out = {"pixels": np.zeros(G, np.int64), "row_sum": np.zeros(G, np.int64), "ping_sum": np.zeros(G, np.int64),
+           "sv_sum": np.zeros((F, G), np.float64), "sv_pixels": np.zeros((F, G), np.int64)}
+    big = np.iinfo(np.int64).max
+    box = np.tile(np.array([big, 0, big, 0], np.int64), (G, 1))
+    key = np.full(G, big, np.int64)                                       # the anchor as row * (survey end) + global ping
+    end = int(chunks[-1]["start_ping"] + chunks[-1]["n_pings"])
+    for i, c in enumerate(chunks):
+        g = group[first[i]:first[i + 1]]
+        s, w = int(c["start_ping"]), int(c["n_pings"])
+        px = np.asarray(c["pixels"], np.int64)
+        np.add.at(out["pixels"], g, px)
+        np.add.at(out["row_sum"], g, c["row_sum"])
+        np.add.at(out["ping_sum"], g, np.asarray(c["ping_sum"], np.int64) + s * px)
+        for f in range(F):
+            np.add.at(out["sv_sum"][f], g, c["sv_sum"][f])
+            np.add.at(out["sv_pixels"][f], g, c["sv_pixels"][f])
+        b = np.asarray(c["bbox"], np.int64).reshape(-1, 4)
+        np.minimum.at(box[:, 0], g, b[:, 0])
+        np.maximum.at(box[:, 1], g, b[:, 1])
+        np.minimum.at(box[:, 2], g, b[:, 2] + s)
+        np.maximum.at(box[:, 3], g, b[:, 3] + s)
+        a = np.asarray(c["anchor"], np.int64)
+        np.minimum.at(key, g, (a // w) * end + (a % w) + s)
+    keep = out["pixels"] >= int(min_pixels)
+    order = np.flatnonzero(keep)[np.argsort(key[keep], kind="stable")]
+    res = {"anchor": np.stack([key[order] // end, key[order] % end], axis=1), "pixels": out["pixels"][order],
+           "bbox": box[order], "row_sum": out["row_sum"][order], "ping_sum": out["ping_sum"][order],
+           "sv_sum": out["sv_sum"][:, order], "sv_pixels": out["sv_pixels"][:, order],
+           "frequencies": chunks[0]["frequencies"], "class": chunks[0]["class"]}
+    return res
+
+
+def detect_schools_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, spec, start_ping=0,
+                          labels_available=True, predict_fn=None, stats=None):
+    """The predicted schools of one zarr survey: ``integrate_survey``'s chunk loop (the same feed, staging and upload
+    overlap), but each chunk's float16 predictions are labelled and reduced to a table of schools on the GPU
+    (``ChunkPredictor.detect_schools``); per chunk the table and the first and last ping column (as school indices) come
+    back, and ``merge_school_chunks`` joins the schools that a chunk seam cut.  Returns ``{class k: result}`` for the
+    classes of ``spec`` (a ``SchoolSpec``), each the dict of ``merge_school_chunks`` with global pings.  Single rank only:
+    under an initialised process group of more than one rank it raises NotImplementedError before it reads anything."""
+    if parallel.rank_world()[1] > 1:
+        raise NotImplementedError("detect_schools_survey: one rank only (a school can span the chunks of several ranks); "
+                                  "run it on one rank of the process group")
+    flow = _SurveyChunks("detect_schools_survey", reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings,
+                         start_ping, labels_available, True, stats, predict_fn, share_patches=False)
+    spec = spec.bind(segpipe.frequencies)
+    if not flow.chunks:
+        raise ValueError(f"detect_schools_survey: no pings from start_ping={start_ping} on")
+    tables = {k: [] for k in spec.classes}
+    first, last = flow.chunks[0][0], flow.chunks[-1][1]
+
+    def detect(cp):                              # (downloads before the chunk's device slot is handed back)
+        for t in cp.detect_schools(spec, keep_left=cp.start_ping > first, keep_right=cp.end_ping < last):
+            tables[t.klass].append(t.numpy())
+    flow.check_model()
+    with flow.feed(("schools",)) as feed:
+        for _ in flow.predicted(feed, then=detect):
+            flow.note("enqueue_s", feed.t_taken)
+    return {k: merge_school_chunks(tables[k], spec.connectivity, spec.min_pixels) for k in spec.classes}
+
+
+def detect_schools_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, spec, predict_fn=None,
+                                 meta_channels=None, seabed=None):
+    """``detect_schools_survey`` for ONE memmap echogram: ``predict_echogram_memm``'s prediction (same arguments, the
+    float16 values it would return) labelled and reduced on the GPU.  The whole echogram is one chunk: no seams.  Returns
+    ``{class k: result}`` as ``detect_schools_survey``."""
+    cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
+                                     out_f16=True, wide=False, seabed=seabed)
+    spec = spec.bind(segpipe.frequencies)
+    grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
+    cp.predict(grid, predict_fn=predict_fn)
+    return {t.klass: merge_school_chunks([t.numpy()], spec.connectivity, spec.min_pixels) for t in cp.detect_schools(spec)}
+
+
+def school_centroids(result):
+    """The centroid (row, global ping) of every school of a result, float64 [K, 2]: ``row_sum`` / ``ping_sum`` over ``pixels``."""
+    px = np.asarray(result["pixels"], dtype=np.float64)
+    return np.stack([np.asarray(result["row_sum"], np.float64) / px, np.asarray(result["ping_sum"], np.float64) / px], axis=1)
+
+
+def school_nasc(result, range_step_m):
+    """The scaling of ``nasc`` per school and frequency: ``4 pi 1852^2 * range_step_m * sv_sum``, float64 [F, K] (summed over
+    the school's pings; a uniform range grid is assumed)."""
+    return 4.0 * np.pi * 1852.0 ** 2 * float(range_step_m) * np.asarray(result["sv_sum"], dtype=np.float64)
+
+
+def school_frequency_response(result, reference=None):
+    """r(f) = sv_sum[f] / sv_sum[reference] per school, float64 [F, K], NaN where the reference sum is 0.  ``reference``: one
+    of ``result["frequencies"]``; None takes 38 or, failing that, 38000 (as ``frequency_response``)."""
+    freqs = [float(f) for f in result["frequencies"]]
+    wanted = (38, 38000) if reference is None else (reference,)
+    at = next((freqs.index(float(f)) for f in wanted if float(f) in freqs), None)
+    if at is None:
+        raise ValueError(f"school_frequency_response: reference {' / '.join(str(f) for f in wanted)} is not among the result's "
+                         f"frequencies {list(result['frequencies'])}")
+    sums = np.asarray(result["sv_sum"], dtype=np.float64)
+    ref = np.broadcast_to(sums[at], sums.shape)
+    return np.divide(sums, ref, out=np.full(sums.shape, np.nan), where=ref > 0)
+
+
+def schools_to_boxes(result, extend_size=0):
+    """The schools' boxes as int32 [K, 4] = (y0, y1, x0, x1), the format of ``eval_boxes`` /
+    ``get_object_bounding_boxes`` (rows, then pings, half-open), grown by ``extend_size`` on every side as ``eval_boxes``
+    grows a 'region' box (not clipped), so that predicted and annotated schools are comparable."""
+    b = np.asarray(result["bbox"], dtype=np.int64).reshape(-1, 4)
+    e = int(extend_size)
+    return np.stack([b[:, 0] - e, b[:, 1] + e, b[:, 2] - e, b[:, 3] + e], axis=1).astype(np.int32)
 
 
 # ---- a memm survey: many small echograms in one prediction feed ----------------------------------------------------------

@@ -994,6 +994,59 @@ int crimac_integrate_confusion_multi(const float* logits, int ncls, const float*
                                      int range_bin, float thr_sandeel, float thr_other, int mode, double* acc,
                                      long long* cnt, void* scratch, long scratch_bytes, void* stream);
 
+/* ---- schools from the predictions (csrc/schools.hip) ---------------------------------------------------------------
+ * A SCHOOL is a connected region of one predicted class.  The reference has them on the annotation side only
+ * (Echogram.get_object_bounding_boxes); for predictions it has no counterpart.  Two launches sequences on a finished
+ * prediction chunk: label the class plane, then reduce the labels to a table of schools.  Neither synchronises.
+ *
+ * crimac_schools_label: connected-component labelling of ONE class plane.
+ *   pred [n_range][n_pings], ping fastest: one plane of what crimac_scatter_patches_ex wrote, float16 (pred_f16 = 1) or
+ *     float32 (0).  A pixel is FOREGROUND when the stored value, widened exactly to fp32, is >= threshold (equality counts;
+ *     NaN is background).  threshold must be > 0, so that a pixel the scatter never wrote is background.
+ *   connectivity 4 (edge neighbours) or 8 (edge and corner neighbours).
+ *   labels int32 [n_range][n_pings] (caller allocates; every element is written): -1 for background, otherwise the linear
+ *     index r * n_pings + p of the FIRST pixel of the component in raster order, the component's ANCHOR.  The labelling is
+ *     canonical: it does not depend on the launch and equals any other labelling relabelled to anchors.
+ *   n_range * n_pings must be below 2^31 (CRIMAC_ERR_INVALID otherwise).
+ *   status int32 [1] (device): zeroed by the call, set to 1 when a union-find loop exceeded its iteration bound (a chain
+ *     cannot be longer than the number of pixels; the loop then gives up, it never spins) -- the labels are then invalid.
+ *     The entry does not wait for the kernels: the caller reads the word with the results.
+ *   Three launches and one 4-byte memset, whatever the content: tiles of CCL_TILE_H x CCL_TILE_W pixels labelled in LDS, the
+ *   tile borders merged by atomicMin unions on global memory, one flatten pass. */
+int crimac_schools_label(const void* pred, int pred_f16, int n_range, long n_pings, float threshold, int connectivity,
+                         int* labels, int* status, void* stream);
+
+/* crimac_schools_stats: the table of schools of a labelled plane, in ASCENDING ANCHOR ORDER.
+ *   labels: what crimac_schools_label wrote.  The linear sv planes are addressed as crimac_integrate_freqs addresses them:
+ *     sv = plane 0 of n_planes planes [data_pings][n_range] (range fastest), plane_stride elements apart; channels int32
+ *     [n_freqs] on the HOST (read during the call only), 1 <= n_freqs <= CRIMAC_SCHOOLS_MAX_FREQS; column sv_ping_off of sv
+ *     belongs to column 0 of labels.
+ *   A school is KEPT when it has >= min_pixels pixels (min_pixels >= 1), or when keep_left (keep_right) is set and it has a
+ *     pixel in ping column 0 (n_pings - 1): a school cut by a chunk seam survives until the chunks are merged.
+ *   capacity K >= 1: the rows of the output arrays.  Kept school k (k-th smallest anchor, k < K) gets
+ *     anchor int32 [K]; pixels int64 [K]; bbox int32 [K][4] = r0, r1, p0, p1 half-open; row_sum, ping_sum int64 [K] = the sum
+ *     of r and of p over its pixels (centroid = sums / pixels, exactly);
+ *     sv_sum fp64 [n_freqs][K] / sv_pixels int64 [n_freqs][K]: per frequency the sum and the number of its pixels whose sv
+ *     is finite and > 0 -- the pixel rule of crimac_integrate_classes; the other pixels count in `pixels` only.
+ *   found int64 [1]: the TRUE number of kept schools, also when it exceeds K; then only the first K are written (call again
+ *     with capacity >= found).  Rows from min(found, K) on are not written.
+ *   edges int32 [2][n_range] or NULL: ping column 0 and ping column n_pings - 1 of labels translated to school indices k
+ *     (-1: background or a school that is not kept; an index >= K when the table overflowed).
+ *   Integer fields come from 32 / 64-bit integer atomics and are exact.  The fp64 sums use NO floating-point atomics: one
+ *     workgroup per school walks the school's bounding box in a fixed order and reduces by a fixed tree, so two calls give
+ *     the same bits, and frequency i of a call has the bits a single-frequency call on channels[i] gives.  That pass reads
+ *     the labels of every box once: its cost is the SUM OF THE BOX AREAS (many nested diagonal schools, each box covering
+ *     most of the plane, cost schools x plane).
+ *   scratch: scratch_bytes >= CRIMAC_SCHOOLS_SCRATCH_PIXEL_BYTES * n_range * n_pings + 16 of device memory, 8-byte aligned
+ *     (a 64-bit word per pixel and a count per 256 pixels); contents undefined before and after.  Six launches and one memset, whatever the content. */
+#define CRIMAC_SCHOOLS_MAX_FREQS CRIMAC_INTEGRATE_MAX_FREQS
+#define CRIMAC_SCHOOLS_SCRATCH_PIXEL_BYTES 9
+int crimac_schools_stats(const int* labels, int n_range, long n_pings, const float* sv, long plane_stride, int n_planes,
+                         const int* channels, int n_freqs, long data_pings, long sv_ping_off, long long min_pixels,
+                         int keep_left, int keep_right, long capacity, int* anchor, long long* pixels, int* bbox,
+                         long long* row_sum, long long* ping_sum, double* sv_sum, long long* sv_pixels, long long* found,
+                         int* edges, void* scratch, long scratch_bytes, void* stream);
+
 /* ---- measurement support (bench.py only, not on the product path) --------------------------- */
 
 /* MFMA-only calibration launch: `blocks` workgroups of 4 waves each issue iters x 8 v_mfma_f32_16x16x32_bf16 on
