@@ -13,6 +13,11 @@
 //                        workgroup depends on a cache line another one has written during the launch);
 //   flatten_kernel       labels[i] = the root of i.
 //   Roots are the smallest index of their tree, so the final label is the component's first pixel in raster order.
+//   label_tiles_kernel is ONE body; what a foreground pixel is, is its template parameter (PredFg: a probability plane,
+//   crimac_schools_label; IdsFg: the raw annotation ids, crimac_schools_label_ids; BothFg: foreground in two label planes,
+//   crimac_schools_label_both).  The overlap of two sets of schools labelled with one connectivity needs nothing else: a
+//   component of the plane `A >= 0 && B >= 0` lies in exactly one school of A and one of B, so crimac_schools_stats of that
+//   plane is a table of pair overlaps and crimac_schools_pair_anchors names the pair of every row.
 //
 // crimac_schools_stats -- the per-school table, in ascending anchor order:
 //   count_kernel         key[anchor] += pixels (64-bit integer atomics, one add per run of equal labels of a wave), bit 62 set
@@ -57,21 +62,68 @@ struct GlobalMem {
   __device__ __forceinline__ void fail() { *err = 1; }
 };
 
-// foreground: the stored value, widened exactly, >= threshold (NaN compares false)
+// ---- the foreground rules of label_tiles_kernel ----------------------------------------------------------------------------
+// fill_tile(fg, lab, ...) writes lab[i] = i for a foreground pixel i of the tile and -1 for every other one (outside the plane
+// included).  The rules that read a plane laid out as the labels ([n_range][n_pings], ping fastest) give `at(linear index)`.
+// PredFg: the stored value, widened exactly, >= threshold (NaN compares false)
 template <typename TP>
-__global__ void __launch_bounds__(kThreads)
-label_tiles_kernel(const TP* __restrict__ pred, int n_range, int n_pings, float thr, int connectivity, int tiles_p,
-                   int* __restrict__ labels, int* err) {
-  __shared__ int lab[kTilePixels];
-  const int t = threadIdx.x;
-  const int r0 = (int)(blockIdx.x / tiles_p) * CCL_TILE_H, p0 = (int)(blockIdx.x % tiles_p) * CCL_TILE_W;
+struct PredFg {
+  const TP* __restrict__ pred;
+  float thr;
+  __device__ __forceinline__ bool at(long i) const { return (float)pred[i] >= thr; }
+};
+
+// BothFg: foreground in two label planes at once (the overlap of two sets of schools)
+struct BothFg {
+  const int* __restrict__ a;
+  const int* __restrict__ b;
+  __device__ __forceinline__ bool at(long i) const { return a[i] >= 0 && b[i] >= 0; }
+};
+
+template <class Fg>
+__device__ __forceinline__ void fill_tile(const Fg& fg, int* lab, int t, int r0, int p0, int n_range, int n_pings) {
 #pragma unroll
   for (int k = 0; k < kTilePixels / kThreads; ++k) {
     const int i = t + kThreads * k, r = r0 + i / CCL_TILE_W, p = p0 + i % CCL_TILE_W;
-    bool fg = false;
-    if (r < n_range && p < n_pings) fg = (float)pred[(long)r * n_pings + p] >= thr;
-    lab[i] = fg ? i : -1;
+    bool fg_px = false;
+    if (r < n_range && p < n_pings) fg_px = fg.at((long)r * n_pings + p);
+    lab[i] = fg_px ? i : -1;
   }
+}
+
+// IdsFg: raw annotation ids [ids_pings][n_range], RANGE fastest -- the tile read is a transposition.  The lanes run along
+// range (16 consecutive int16 of one ping, 4 pings per wave and step) and write the tile's LDS transposed, so that the rest of
+// the kernel sees the tile as the other rules leave it.  A wave reads 4 runs of 32 bytes per step and its LDS stores collide
+// on the banks (stride CCL_TILE_W words); the rate of this read has NOT been measured.
+struct IdsFg {
+  const short* __restrict__ ids;
+  long ping_off;                                   // column ping_off of ids is column 0 of the labels
+  int select;
+  __device__ __forceinline__ bool is_fg(int id) const {
+    return select >= 0 ? id == select : (id != 0 && id != 27 && id != 1);          // (the ids labels.hip does not map to a class)
+  }
+};
+
+__device__ __forceinline__ void fill_tile(const IdsFg& fg, int* lab, int t, int r0, int p0, int n_range, int n_pings) {
+  static_assert(kThreads % CCL_TILE_H == 0 && CCL_TILE_W % (kThreads / CCL_TILE_H) == 0, "the transposed read covers the tile");
+  const int lr = t % CCL_TILE_H, r = r0 + lr;
+#pragma unroll
+  for (int k = 0; k < kTilePixels / kThreads; ++k) {
+    const int lp = t / CCL_TILE_H + (kThreads / CCL_TILE_H) * k, p = p0 + lp;
+    bool fg_px = false;
+    if (r < n_range && p < n_pings) fg_px = fg.is_fg(fg.ids[(fg.ping_off + p) * n_range + r]);
+    const int i = lr * CCL_TILE_W + lp;
+    lab[i] = fg_px ? i : -1;
+  }
+}
+
+template <class Fg>
+__global__ void __launch_bounds__(kThreads)
+label_tiles_kernel(const Fg fg, int n_range, int n_pings, int connectivity, int tiles_p, int* __restrict__ labels, int* err) {
+  __shared__ int lab[kTilePixels];
+  const int t = threadIdx.x;
+  const int r0 = (int)(blockIdx.x / tiles_p) * CCL_TILE_H, p0 = (int)(blockIdx.x % tiles_p) * CCL_TILE_W;
+  fill_tile(fg, lab, t, r0, p0, n_range, n_pings);
   __syncthreads();
   int dummy = 0;
   LdsMem m{lab, &dummy};
@@ -324,36 +376,83 @@ sv_kernel(const int* __restrict__ labels, const float* __restrict__ sv, Planes f
 
 inline long blocks_of(long n) { return (n + kThreads - 1) / kThreads; }
 
-}  // namespace
+// what every labelling entry refuses about its plane and connectivity, before anything is launched
+#define SCHOOLS_PLANE_REQUIRE(name)                                                                                          \
+  CRIMAC_REQUIRE(n_range > 0 && n_pings > 0, name ": empty plane (%d x %ld)", n_range, n_pings);                              \
+  CRIMAC_REQUIRE(n_pings <= 2147483647L / n_range, name ": %d x %ld pixels: the labels are 32-bit indices, "                 \
+                 "n_range * n_pings must be below 2^31", n_range, n_pings);                                                  \
+  CRIMAC_REQUIRE(connectivity == 4 || connectivity == 8, name ": connectivity=%d (4 or 8)", connectivity)
 
-extern "C" int crimac_schools_label(const void* pred, int pred_f16, int n_range, long n_pings, float threshold,
-                                    int connectivity, int* labels, int* status, void* stream) {
-  CRIMAC_REQUIRE(pred && labels && status, "schools_label: null pointer");
-  CRIMAC_REQUIRE(pred_f16 == 0 || pred_f16 == 1, "schools_label: pred_f16 is 0 or 1");
-  CRIMAC_REQUIRE(n_range > 0 && n_pings > 0, "schools_label: empty prediction plane (%d x %ld)", n_range, n_pings);
-  CRIMAC_REQUIRE(n_pings <= 2147483647L / n_range, "schools_label: %d x %ld pixels: the labels are 32-bit indices, "
-                 "n_range * n_pings must be below 2^31", n_range, n_pings);
-  CRIMAC_REQUIRE(threshold > 0.f, "schools_label: threshold=%g must be > 0 (pixels the scatter left at 0 are background)",
-                 (double)threshold);
-  CRIMAC_REQUIRE(connectivity == 4 || connectivity == 8, "schools_label: connectivity=%d (4 or 8)", connectivity);
-  const hipStream_t st = (hipStream_t)stream;
+// the launches of every labelling entry: one 4-byte memset, tiles by the rule `fg`, borders, flatten
+template <class Fg>
+int label_plane(const Fg& fg, int n_range, long n_pings, int connectivity, int* labels, int* status, hipStream_t st) {
   if (hipMemsetAsync(status, 0, sizeof(int), st) != hipSuccess) {
     crimac_set_error("schools_label: hipMemsetAsync failed");
     return CRIMAC_ERR_LAUNCH;
   }
   const int np = (int)n_pings, tiles_p = (np + CCL_TILE_W - 1) / CCL_TILE_W;
   const long tiles = (long)tiles_p * ((n_range + CCL_TILE_H - 1) / CCL_TILE_H), n = (long)n_range * n_pings;
-  if (pred_f16)
-    hipLaunchKernelGGL(label_tiles_kernel<half_t>, dim3((unsigned)tiles), dim3(kThreads), 0, st, (const half_t*)pred, n_range,
-                       np, threshold, connectivity, tiles_p, labels, status);
-  else
-    hipLaunchKernelGGL(label_tiles_kernel<float>, dim3((unsigned)tiles), dim3(kThreads), 0, st, (const float*)pred, n_range, np,
-                       threshold, connectivity, tiles_p, labels, status);
+  hipLaunchKernelGGL(label_tiles_kernel<Fg>, dim3((unsigned)tiles), dim3(kThreads), 0, st, fg, n_range, np, connectivity,
+                     tiles_p, labels, status);
   CRIMAC_LAUNCH_CHECK();
   hipLaunchKernelGGL(merge_borders_kernel, dim3((unsigned)tiles), dim3(CCL_TILE_W + CCL_TILE_H), 0, st, labels, n_range, np,
                      connectivity, tiles_p, status);
   CRIMAC_LAUNCH_CHECK();
   hipLaunchKernelGGL(flatten_kernel, dim3((unsigned)blocks_of(n)), dim3(kThreads), 0, st, labels, n, status);
+  CRIMAC_LAUNCH_CHECK();
+  return CRIMAC_OK;
+}
+
+// row k of an overlap table lies in the schools a[anchor[k]] and b[anchor[k]]
+__global__ void __launch_bounds__(kThreads)
+pair_anchors_kernel(const int* __restrict__ anchor, const long long* __restrict__ found, long capacity,
+                    const int* __restrict__ a, const int* __restrict__ b, int* __restrict__ pair) {
+  const long k = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (k >= capacity || k >= found[0]) return;
+  const int at = anchor[k];
+  pair[2 * k] = a[at];
+  pair[2 * k + 1] = b[at];
+}
+
+}  // namespace
+
+extern "C" int crimac_schools_label(const void* pred, int pred_f16, int n_range, long n_pings, float threshold,
+                                    int connectivity, int* labels, int* status, void* stream) {
+  CRIMAC_REQUIRE(pred && labels && status, "schools_label: null pointer");
+  CRIMAC_REQUIRE(pred_f16 == 0 || pred_f16 == 1, "schools_label: pred_f16 is 0 or 1");
+  SCHOOLS_PLANE_REQUIRE("schools_label");
+  CRIMAC_REQUIRE(threshold > 0.f, "schools_label: threshold=%g must be > 0 (pixels the scatter left at 0 are background)",
+                 (double)threshold);
+  const hipStream_t st = (hipStream_t)stream;
+  if (pred_f16) return label_plane(PredFg<half_t>{(const half_t*)pred, threshold}, n_range, n_pings, connectivity, labels, status, st);
+  return label_plane(PredFg<float>{(const float*)pred, threshold}, n_range, n_pings, connectivity, labels, status, st);
+}
+
+extern "C" int crimac_schools_label_ids(const short* ids, long ids_pings, long ids_ping_off, int n_range, long n_pings,
+                                        int select, int connectivity, int* labels, int* status, void* stream) {
+  CRIMAC_REQUIRE(ids && labels && status, "schools_label_ids: null pointer");
+  SCHOOLS_PLANE_REQUIRE("schools_label_ids");
+  CRIMAC_REQUIRE(ids_ping_off >= 0 && ids_ping_off <= ids_pings && n_pings <= ids_pings - ids_ping_off,
+                 "schools_label_ids: id columns [%ld, %ld) outside the id extent of %ld pings", ids_ping_off,
+                 ids_ping_off + n_pings, ids_pings);
+  CRIMAC_REQUIRE(select >= 0 || select == CRIMAC_SCHOOLS_IDS_IGNORED, "schools_label_ids: select=%d (an id >= 0, or "
+                 "CRIMAC_SCHOOLS_IDS_IGNORED = %d)", select, CRIMAC_SCHOOLS_IDS_IGNORED);
+  return label_plane(IdsFg{ids, ids_ping_off, select}, n_range, n_pings, connectivity, labels, status, (hipStream_t)stream);
+}
+
+extern "C" int crimac_schools_label_both(const int* a, const int* b, int n_range, long n_pings, int connectivity, int* labels,
+                                         int* status, void* stream) {
+  CRIMAC_REQUIRE(a && b && labels && status, "schools_label_both: null pointer");
+  SCHOOLS_PLANE_REQUIRE("schools_label_both");
+  return label_plane(BothFg{a, b}, n_range, n_pings, connectivity, labels, status, (hipStream_t)stream);
+}
+
+extern "C" int crimac_schools_pair_anchors(const int* anchor, const long long* found, long capacity, const int* a, const int* b,
+                                           int* pair, void* stream) {
+  CRIMAC_REQUIRE(anchor && found && a && b && pair, "schools_pair_anchors: null pointer");
+  CRIMAC_REQUIRE(capacity >= 1 && capacity <= 2147483647L, "schools_pair_anchors: capacity=%ld (1 .. 2^31 - 1)", capacity);
+  hipLaunchKernelGGL(pair_anchors_kernel, dim3((unsigned)blocks_of(capacity)), dim3(kThreads), 0, (hipStream_t)stream, anchor,
+                     found, capacity, a, b, pair);
   CRIMAC_LAUNCH_CHECK();
   return CRIMAC_OK;
 }

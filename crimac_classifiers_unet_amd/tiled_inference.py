@@ -274,16 +274,43 @@ class ChunkPredictor:
         planes, on the current stream.  Returns a list of ``SchoolTable`` (device tensors, nothing has been waited for);
         ``SchoolTable.numpy()`` downloads one.  ``keep_left`` / ``keep_right``: keep every school that touches the first /
         last ping column whatever its size (the chunk has a neighbour there: ``merge_school_chunks``)."""
+        self._check_schools("detect_schools", spec)
+        return [SchoolTable(self, spec, k, bool(keep_left), bool(keep_right)) for k in spec.classes]
+
+    def _check_schools(self, name, spec):
         if self.wide or self.out is None:
-            raise ValueError("ChunkPredictor.detect_schools: the chunk was loaded for evaluate() (wide=True) and has no predictions")
+            raise ValueError(f"ChunkPredictor.{name}: the chunk was loaded for evaluate() (wide=True) and has no predictions")
         if spec.channels is None:
-            raise ValueError("ChunkPredictor.detect_schools: bind the spec to the model's frequencies first (SchoolSpec.bind)")
+            raise ValueError(f"ChunkPredictor.{name}: bind the spec to the model's frequencies first (SchoolSpec.bind)")
         for ch in spec.channels:
             if not 0 <= ch < self.data.shape[0]:
-                raise ValueError(f"ChunkPredictor.detect_schools: channel {ch} of {self.data.shape[0]} data planes")
+                raise ValueError(f"ChunkPredictor.{name}: channel {ch} of {self.data.shape[0]} data planes")
         if not self.data.is_contiguous():
-            raise ValueError("ChunkPredictor.detect_schools: the chunk's data must be contiguous [C, pings, range]")
-        return [SchoolTable(self, spec, k, bool(keep_left), bool(keep_right)) for k in spec.classes]
+            raise ValueError(f"ChunkPredictor.{name}: the chunk's data must be contiguous [C, pings, range]")
+
+    def score_schools(self, spec, keep_left=False, keep_right=False, ignored=True):
+        """``detect_schools`` plus, per class, the ANNOTATED schools of the chunk -- the connected regions of the class's raw
+        annotation id (27 / 1) in ``self.labels``, with the same connectivity, ``min_pixels`` and keep flags -- and the
+        overlap of every (predicted, annotated) pair: pixels and per-frequency sv sums, from the table of the components of
+        the intersection plane (``SchoolOverlaps``).  ``ignored``: also the pixels every predicted school shares with ids the
+        label transform ignores (any id but 0, 27, 1).  All on the current stream; returns a list of ``SchoolScore`` (device
+        tensors, nothing has been waited for).  Refuses what ``detect_schools`` refuses, and a chunk loaded without labels."""
+        self._check_schools("score_schools", spec)
+        n = self.end_ping - self.start_ping
+        if self.labels is None:
+            raise ValueError("ChunkPredictor.score_schools: the chunk was loaded without labels: there are no annotated schools "
+                             "to score against")
+        if self.labels.dtype != torch.int16 or tuple(self.labels.shape) != (n, self.n_range) or not self.labels.is_contiguous():
+            raise ValueError(f"ChunkPredictor.score_schools: the chunk's labels must be contiguous int16 [{n}, {self.n_range}] "
+                             f"(pings, range); got {self.labels.dtype} {tuple(self.labels.shape)}")
+        plane = None
+        if ignored:                                  # one plane for all classes: the ids no class maps to
+            plane = types.SimpleNamespace(labels=self.engine._buf("schools.ignored", (self.n_range, n), torch.int32),
+                                          status=torch.empty(1, dtype=torch.int32, device=self.out.device))
+            with torch.cuda.device(self.out.device):
+                call("crimac_schools_label_ids", ptr(self.labels), n, 0, self.n_range, n, SCHOOLS_IDS_IGNORED,
+                     spec.connectivity, ptr(plane.labels), ptr(plane.status))
+        return [SchoolScore(self, spec, k, bool(keep_left), bool(keep_right), plane) for k in spec.classes]
 
     def _limit_line(self):
         """The seabed line of a seabed-aware integration, as ``(pointer, index of ping start_ping, length)``: the chunk's
@@ -1936,21 +1963,32 @@ class SchoolTable:
     anchor), the table ``anchor`` / ``pixels`` / ``bbox`` / ``row_sum`` / ``ping_sum`` ``[capacity]``, ``sv_sum`` /
     ``sv_pixels`` ``[F, capacity]`` in ascending anchor order, ``found`` int64 [1] (the true count), ``edges`` int32
     ``[2, n_range]`` (the first and last ping column as school indices) and ``status`` int32 [1].  Everything is enqueued
-    on the stream that was current; nothing has been waited for."""
+    on the stream that was current; nothing has been waited for.
+    ``plane``: the name of the label plane's engine buffer (``schools.<plane>.<class>``).  ``select``: None labels the
+    predictions of the class; an annotation id (or ``SCHOOLS_IDS_IGNORED``) labels the chunk's raw ids instead
+    (``crimac_schools_label_ids``): the annotated schools, same table."""
 
-    def __init__(self, cp, spec, klass, keep_left, keep_right):
+    def __init__(self, cp, spec, klass, keep_left, keep_right, plane="labels", select=None):
         self.cp, self.spec, self.klass, self.keep = cp, spec, klass, (keep_left, keep_right)
         self.n_range, self.n_pings, self.start_ping = cp.n_range, cp.end_ping - cp.start_ping, cp.start_ping
+        self.min_pixels = spec.min_pixels
         dev = cp.out.device
-        eng = cp.engine
-        self.labels = eng._buf(f"schools.labels.{klass}", (self.n_range, self.n_pings), torch.int32)
+        self.labels = cp.engine._buf(f"schools.{plane}.{klass}", (self.n_range, self.n_pings), torch.int32)
         self.status = torch.empty(1, dtype=torch.int32, device=dev)
         self.found = torch.empty(1, dtype=torch.int64, device=dev)
         self.edges = torch.empty((2, self.n_range), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            call("crimac_schools_label", ptr(cp.out[klass - 1]), 1 if cp.out_f16 else 0, self.n_range, self.n_pings,
-                 spec.thresholds[klass - 1], spec.connectivity, ptr(self.labels), ptr(self.status))
+            self._label(select)
         self._stats(spec.max_schools)
+
+    def _label(self, select):
+        cp, spec = self.cp, self.spec
+        if select is None:
+            call("crimac_schools_label", ptr(cp.out[self.klass - 1]), 1 if cp.out_f16 else 0, self.n_range, self.n_pings,
+                 spec.thresholds[self.klass - 1], spec.connectivity, ptr(self.labels), ptr(self.status))
+        else:
+            call("crimac_schools_label_ids", ptr(cp.labels), int(cp.labels.shape[0]), 0, self.n_range, self.n_pings, select,
+                 spec.connectivity, ptr(self.labels), ptr(self.status))
 
     def _stats(self, capacity):
         cp, spec, F = self.cp, self.spec, len(self.spec.channels)
@@ -1967,7 +2005,7 @@ class SchoolTable:
         channels = (ctypes.c_int * F)(*spec.channels)          # a host array: it lives until the call returns
         with torch.cuda.device(dev):
             call("crimac_schools_stats", ptr(self.labels), self.n_range, self.n_pings, ptr(cp.data[0]), int(cp.data.stride(0)),
-                 int(cp.data.shape[0]), channels, F, int(cp.data.shape[1]), cp.start_ping - cp.data_ping0, spec.min_pixels,
+                 int(cp.data.shape[0]), channels, F, int(cp.data.shape[1]), cp.start_ping - cp.data_ping0, self.min_pixels,
                  int(self.keep[0]), int(self.keep[1]), K, ptr(self.anchor), ptr(self.pixels), ptr(self.bbox), ptr(self.row_sum),
                  ptr(self.ping_sum), ptr(self.sv_sum), ptr(self.sv_pixels), ptr(self.found), ptr(self.edges), ptr(scratch),
                  scratch.numel() * 8)
@@ -1987,13 +2025,95 @@ class SchoolTable:
             found = int(self.found.item())
         res = {name: getattr(self, name)[..., :found].cpu().numpy() if name in ("sv_sum", "sv_pixels")
                else getattr(self, name)[:found].cpu().numpy() for name in SCHOOL_FIELDS}
-        res.update(edges=self.edges.cpu().numpy(), start_ping=self.start_ping, n_pings=self.n_pings, n_range=self.n_range)
+        if self.edges is not None:
+            res["edges"] = self.edges.cpu().numpy()
+        res.update(start_ping=self.start_ping, n_pings=self.n_pings, n_range=self.n_range)
         res["class"] = SCHOOL_CLASSES[self.klass]
         res["frequencies"] = self.spec.frequencies
         return res
 
 
-def merge_school_chunks(chunks, connectivity, min_pixels):
+# ---- schools scored against the annotations: the overlap of two label planes is a third labelling ----------------------------
+SCHOOL_IDS = {1: 27, 2: 1}                           # the raw annotation id of class k (the mapping of csrc/labels.hip)
+SCHOOLS_IDS_IGNORED = hip.DEFINES["CRIMAC_SCHOOLS_IDS_IGNORED"]      # `select` of the ids the label transform ignores
+
+
+class SchoolOverlaps(SchoolTable):
+    """The overlap of the schools of two label planes of one chunk (``a`` a ``SchoolTable``; ``b`` one, or any object with
+    ``labels`` and ``status``): ``crimac_schools_label_both``, ``crimac_schools_stats`` with ``min_pixels`` 1, no kept edges
+    and no edge columns, and ``crimac_schools_pair_anchors``.  Every row is one connected component of ``a >= 0 && b >= 0``
+    and lies in exactly one (school of a, school of b) pair: ``pair`` int32 ``[capacity, 2]`` holds the two anchors."""
+
+    def __init__(self, a, b, plane):
+        self.a, self.b = a, b
+        super().__init__(a.cp, a.spec, a.klass, False, False, plane=plane)
+
+    def _label(self, select):
+        self.min_pixels, self.edges = 1, None
+        call("crimac_schools_label_both", ptr(self.a.labels), ptr(self.b.labels), self.n_range, self.n_pings,
+             self.spec.connectivity, ptr(self.labels), ptr(self.status))
+
+    def _stats(self, capacity):
+        super()._stats(capacity)
+        self.pair = torch.empty((self.capacity, 2), dtype=torch.int32, device=self.anchor.device)
+        with torch.cuda.device(self.anchor.device):
+            call("crimac_schools_pair_anchors", ptr(self.anchor), ptr(self.found), self.capacity, ptr(self.a.labels),
+                 ptr(self.b.labels), ptr(self.pair))
+
+    def numpy(self, a_anchor, b_anchor=None):
+        """The rows as a dict: ``"anchor"``, ``"pixels"``, ``"sv_sum"`` / ``"sv_pixels"`` ``[F, n]`` in ascending anchor order,
+        and ``"pred"`` (``"ann"``): the row of the component's school in the DOWNLOADED table of ``a`` (``b``), whose anchor
+        column is given -- so after that table's own second pass, if it had one --, -1 for a school its table dropped.
+        ``b_anchor`` None: no ``"ann"``."""
+        if int(self.b.status.item()) != 0:
+            raise hip.HipLibraryError("crimac_schools_label_ids: a union-find loop exceeded its iteration bound (status 1): the "
+                                      "labels of this chunk are invalid")
+        t = super().numpy()                          # (a table that overflowed: _stats again, the pairs with it)
+        pair = self.pair[:len(t["anchor"])].cpu().numpy()
+        res = {name: t[name] for name in ("anchor", "pixels", "sv_sum", "sv_pixels")}
+        for name, col, anchors in (("pred", 0, a_anchor), ("ann", 1, b_anchor)):
+            if anchors is not None:
+                res[name] = _rows_of_anchors(anchors, pair[:, col])
+        return res
+
+
+def _rows_of_anchors(anchors, wanted):
+    """The index of every ``wanted`` anchor in the ascending ``anchors``, int64; -1 for one that is not there."""
+    anchors, wanted = np.asarray(anchors, dtype=np.int64), np.asarray(wanted, dtype=np.int64)
+    if not len(anchors):
+        return np.full(len(wanted), -1, dtype=np.int64)
+    at = np.minimum(np.searchsorted(anchors, wanted), len(anchors) - 1)
+    return np.where(anchors[at] == wanted, at, -1).astype(np.int64)
+
+
+class SchoolScore:
+    """The predicted schools of one class of one resident chunk against the annotated ones, on the GPU
+    (``ChunkPredictor.score_schools``): ``predicted`` and ``annotated`` (``SchoolTable``), ``overlaps`` and -- with
+    ``ignored`` -- ``ignored`` (``SchoolOverlaps`` of the predicted plane with the annotated plane / the plane of the ids
+    the label transform ignores).  Nothing has been waited for."""
+
+    def __init__(self, cp, spec, klass, keep_left, keep_right, ignored_plane):
+        self.klass = klass
+        self.predicted = SchoolTable(cp, spec, klass, keep_left, keep_right)
+        self.annotated = SchoolTable(cp, spec, klass, keep_left, keep_right, plane="annotated", select=SCHOOL_IDS[klass])
+        self.overlaps = SchoolOverlaps(self.predicted, self.annotated, "overlaps")
+        self.ignored = None if ignored_plane is None else SchoolOverlaps(self.predicted, ignored_plane, "overlaps_ignored")
+
+    def numpy(self):
+        """Download (this waits for the stream; before the next ``load_chunk``, as ``SchoolTable.numpy``): ``"predicted"`` and
+        ``"annotated"`` chunk-local tables, ``"overlaps"`` (``SchoolOverlaps.numpy``: rows of the two tables as downloaded)
+        and ``"ignored_pixels"`` int64 per predicted row (zeros without ``ignored``)."""
+        pred, ann = self.predicted.numpy(), self.annotated.numpy()
+        res = {"predicted": pred, "annotated": ann, "overlaps": self.overlaps.numpy(pred["anchor"], ann["anchor"]),
+               "ignored_pixels": np.zeros(len(pred["anchor"]), dtype=np.int64)}
+        if self.ignored is not None:
+            ign = self.ignored.numpy(pred["anchor"])
+            hit = ign["pred"] >= 0
+            np.add.at(res["ignored_pixels"], ign["pred"][hit], ign["pixels"][hit])
+        return res
+
+
+def merge_school_chunks(chunks, connectivity, min_pixels, index=False):
     """The schools of a survey from the chunk-local tables of ONE class (``SchoolTable.numpy()``; numpy only), ``chunks``
     in ascending ping order, each starting where the one before ends.  Schools of neighbouring chunks are one school when
     a foreground pixel of the last column of chunk i and one of the first column of chunk i + 1 lie in rows that differ by
@@ -2060,7 +2180,60 @@ def merge_school_chunks(chunks, connectivity, min_pixels):
            "bbox": box[order], "row_sum": out["row_sum"][order], "ping_sum": out["ping_sum"][order],
            "sv_sum": out["sv_sum"][:, order], "sv_pixels": out["sv_pixels"][:, order],
            "frequencies": chunks[0]["frequencies"], "class": chunks[0]["class"]}
+    if index:
+        row = np.full(G, -1, dtype=np.int64)
+        row[order] = np.arange(len(order))
+        res["index"] = [row[group[first[i]:first[i + 1]]] for i in range(len(chunks))]
     return res
+
+
+def merge_school_overlaps(overlap_chunks, pred_index, ann_index):
+    """The pair overlaps of a survey from the chunk-local overlap rows (``SchoolScore.numpy()["overlaps"]``; numpy only), one
+    per chunk in ascending ping order.  ``pred_index`` / ``ann_index``: the ``"index"`` of ``merge_school_chunks(..., index=True)``
+    over the predicted / annotated tables of the same chunks; a row whose school was dropped on either side (-1 in the row
+    itself or in the index) is dropped.  The rows of equal (pred, ann) pairs are added up: ``pixels`` and ``sv_pixels``
+    exactly, ``sv_sum`` in ascending chunk order and, inside a chunk, in ascending component-anchor order.  Returns
+    ``"pred"``, ``"ann"``, ``"pixels"`` int64 [M], ``"sv_sum"`` float64 / ``"sv_pixels"`` int64 [F, M], sorted by (pred, ann)."""
+    if not overlap_chunks or not len(overlap_chunks) == len(pred_index) == len(ann_index):
+        raise ValueError("merge_school_overlaps: one overlap table and one index of each side per chunk, at least one chunk")
+    F = np.asarray(overlap_chunks[0]["sv_sum"]).shape[0]
+    rows = {"pred": [], "ann": [], "pixels": [], "sv_sum": [], "sv_pixels": []}
+    for c, pi, ai in zip(overlap_chunks, pred_index, ann_index):
+        def merged(local, index):
+            local, index = np.asarray(local, dtype=np.int64), np.asarray(index, dtype=np.int64)
+            out = np.full(len(local), -1, dtype=np.int64)
+            out[local >= 0] = index[local[local >= 0]]
+            return out
+        p, a = merged(c["pred"], pi), merged(c["ann"], ai)
+        keep = (p >= 0) & (a >= 0)
+        rows["pred"].append(p[keep])
+        rows["ann"].append(a[keep])
+        rows["pixels"].append(np.asarray(c["pixels"], dtype=np.int64)[keep])
+        rows["sv_sum"].append(np.asarray(c["sv_sum"], dtype=np.float64).reshape(F, -1)[:, keep])
+        rows["sv_pixels"].append(np.asarray(c["sv_pixels"], dtype=np.int64).reshape(F, -1)[:, keep])
+    rows = {k: np.concatenate(v, axis=-1) for k, v in rows.items()}
+    pairs, of = np.unique(np.stack([rows["pred"], rows["ann"]], axis=1), axis=0, return_inverse=True)
+    of = of.reshape(-1)
+    M = len(pairs)
+    out = {"pred": pairs[:, 0], "ann": pairs[:, 1], "pixels": np.zeros(M, np.int64), "sv_sum": np.zeros((F, M), np.float64),
+           "sv_pixels": np.zeros((F, M), np.int64)}
+    np.add.at(out["pixels"], of, rows["pixels"])
+    for f in range(F):                               # (np.add.at adds in the order of the rows: chunk, then anchor)
+        np.add.at(out["sv_sum"][f], of, rows["sv_sum"][f])
+        np.add.at(out["sv_pixels"][f], of, rows["sv_pixels"][f])
+    return out
+
+
+def _merge_school_scores(chunks, spec):
+    """``{"predicted", "annotated", "overlaps", "ignored_pixels"}`` of ONE class from its ``SchoolScore.numpy()`` per chunk."""
+    pred = merge_school_chunks([c["predicted"] for c in chunks], spec.connectivity, spec.min_pixels, index=True)
+    ann = merge_school_chunks([c["annotated"] for c in chunks], spec.connectivity, spec.min_pixels, index=True)
+    p_index, a_index = pred.pop("index"), ann.pop("index")
+    ignored = np.zeros(len(pred["pixels"]), dtype=np.int64)
+    for c, index in zip(chunks, p_index):
+        np.add.at(ignored, index[index >= 0], c["ignored_pixels"][index >= 0])
+    return {"predicted": pred, "annotated": ann, "ignored_pixels": ignored,
+            "overlaps": merge_school_overlaps([c["overlaps"] for c in chunks], p_index, a_index)}
 
 
 def detect_schools_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, spec, start_ping=0,
@@ -2103,6 +2276,105 @@ def detect_schools_echogram_memm(echogram, segpipe, patch_size, patch_overlap, b
     grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
     cp.predict(grid, predict_fn=predict_fn)
     return {t.klass: merge_school_chunks([t.numpy()], spec.connectivity, spec.min_pixels) for t in cp.detect_schools(spec)}
+
+
+def score_schools_survey(reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings, spec, start_ping=0,
+                         labels_available=True, predict_fn=None, stats=None, ignored=True):
+    """``detect_schools_survey`` scored against the annotations in the same chunk pass (``ChunkPredictor.score_schools``):
+    per chunk the predicted table, the table of the annotated schools (regions of the raw annotation id of the class, as
+    stored) and the overlap rows come back; ``merge_school_chunks`` joins both kinds of schools across the seams and
+    ``merge_school_overlaps`` adds the overlaps up per pair.  Returns ``{class k: {"predicted": result, "annotated": result,
+    "overlaps": ..., "ignored_pixels": int64 [K predicted]}}``; ``"predicted"`` is what ``detect_schools_survey`` returns,
+    ``"overlaps"`` refers to the rows of the two results.  ``school_iou`` / ``match_schools`` / ``school_detection_scores``
+    take one class of it.  Single rank only, as ``detect_schools_survey``; a survey without labels is refused."""
+    if parallel.rank_world()[1] > 1:
+        raise NotImplementedError("score_schools_survey: one rank only (a school can span the chunks of several ranks); "
+                                  "run it on one rank of the process group")
+    flow = _SurveyChunks("score_schools_survey", reader, segpipe, patch_size, patch_overlap, batch_size, preload_n_pings,
+                         start_ping, labels_available, True, stats, predict_fn, share_patches=False)
+    spec = spec.bind(segpipe.frequencies)
+    if not flow.chunks:
+        raise ValueError(f"score_schools_survey: no pings from start_ping={start_ping} on")
+    scores = {k: [] for k in spec.classes}
+    first, last = flow.chunks[0][0], flow.chunks[-1][1]
+
+    def score(cp):                               # (downloads before the chunk's device slot is handed back)
+        for t in cp.score_schools(spec, keep_left=cp.start_ping > first, keep_right=cp.end_ping < last, ignored=ignored):
+            scores[t.klass].append(t.numpy())
+    flow.check_model()
+    with flow.feed(("schools",)) as feed:
+        for _ in flow.predicted(feed, then=score):
+            flow.note("enqueue_s", feed.t_taken)
+    return {k: _merge_school_scores(scores[k], spec) for k in spec.classes}
+
+
+def score_schools_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, spec, predict_fn=None,
+                                meta_channels=None, seabed=None, ignored=True):
+    """``score_schools_survey`` for ONE memmap echogram (``detect_schools_echogram_memm``'s prediction; one chunk, no seams)."""
+    cp, seabed = _load_echogram_memm(echogram, segpipe, patch_size, patch_overlap, batch_size, meta_channels,
+                                     out_f16=True, wide=False, seabed=seabed)
+    spec = spec.bind(segpipe.frequencies)
+    grid = plan_eval_grid(cp.n_range, seabed, cp.end_ping, patch_size, patch_overlap, memm=True)
+    cp.predict(grid, predict_fn=predict_fn)
+    return {t.klass: _merge_school_scores([t.numpy()], spec) for t in cp.score_schools(spec, ignored=ignored)}
+
+
+def school_iou(score):
+    """Per overlap row of one class of a score: ``pixels / (predicted pixels + annotated pixels - pixels)``, float64 [M] --
+    the mask IoU of COCO "segm" of the (predicted, annotated) pair."""
+    ov = score["overlaps"]
+    both = np.asarray(ov["pixels"], dtype=np.float64)
+    union = (np.asarray(score["predicted"]["pixels"], np.int64)[ov["pred"]]
+             + np.asarray(score["annotated"]["pixels"], np.int64)[ov["ann"]] - np.asarray(ov["pixels"], np.int64))
+    return both / union.astype(np.float64)
+
+
+def match_schools(score, min_iou=0.5):
+    """One-to-one matches of predicted and annotated schools: the pairs with IoU >= ``min_iou`` are taken in descending
+    IoU, ties in ascending (pred, ann), and a pair is a match when neither school has been used.  Above 0.5 a school has
+    at most one such partner, so the match is unique.  Returns ``"pred"``, ``"ann"`` int64 and ``"iou"`` float64 [m], in the
+    order taken."""
+    ov, iou = score["overlaps"], school_iou(score)
+    cand = np.flatnonzero(iou >= float(min_iou))
+    cand = cand[np.lexsort((ov["ann"][cand], ov["pred"][cand], -iou[cand]))]
+    used_p, used_a, taken = set(), set(), []
+    for i in cand:
+        p, a = int(ov["pred"][i]), int(ov["ann"][i])
+        if p not in used_p and a not in used_a:
+            used_p.add(p), used_a.add(a), taken.append(i)
+    taken = np.asarray(taken, dtype=np.int64)
+    return {"pred": np.asarray(ov["pred"], np.int64)[taken], "ann": np.asarray(ov["ann"], np.int64)[taken], "iou": iou[taken]}
+
+
+def school_detection_scores(score, min_iou=0.5, max_ignored=0.5):
+    """Object-level scores of one class of a score.  A match (``match_schools``) is a true positive; an annotated school
+    without one a false negative; a predicted school without one a false positive -- unless more than ``max_ignored`` of
+    its pixels lie on ids the label transform ignores: then it counts neither way (``"excluded"``).  Returns the counts
+    ``"true_positives"``, ``"false_positives"``, ``"false_negatives"``, ``"excluded"``, ``"predicted"``, ``"annotated"``;
+    ``"recall"``, ``"precision"``, ``"f1"``; ``"sv_recall"`` float64 [F]: the overlap ``sv_sum`` over the annotated ``sv_sum``,
+    all schools; ``"school_sv_recall"`` [F, K annotated]: the same per annotated school; and ``"matches"``.  A division by
+    zero gives NaN, as ``frequency_response``."""
+    m = match_schools(score, min_iou)
+    pred_px = np.asarray(score["predicted"]["pixels"], dtype=np.float64)
+    n_pred, n_ann, tp = len(pred_px), len(score["annotated"]["pixels"]), len(m["pred"])
+    unmatched = np.ones(n_pred, dtype=bool)
+    unmatched[m["pred"]] = False
+    excluded = int(np.count_nonzero(unmatched & (np.asarray(score["ignored_pixels"], np.float64) > float(max_ignored) * pred_px)))
+    fp, fn = n_pred - tp - excluded, n_ann - tp
+
+    def ratio(num, den):
+        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+        return np.divide(num, den, out=np.full(np.broadcast(num, den).shape, np.nan), where=den > 0)
+    recall, precision = float(ratio(tp, tp + fn)), float(ratio(tp, tp + fp))
+    ov, ann_sv = score["overlaps"], np.asarray(score["annotated"]["sv_sum"], dtype=np.float64)
+    per_school = np.zeros_like(ann_sv)
+    for f in range(ann_sv.shape[0]):
+        np.add.at(per_school[f], ov["ann"], ov["sv_sum"][f])
+    return {"true_positives": tp, "false_positives": fp, "false_negatives": fn, "excluded": excluded, "predicted": n_pred,
+            "annotated": n_ann, "recall": recall, "precision": precision,
+            "f1": float(ratio(2.0 * precision * recall, precision + recall)),
+            "sv_recall": ratio(np.asarray(ov["sv_sum"], np.float64).sum(axis=1), ann_sv.sum(axis=1)),
+            "school_sv_recall": ratio(per_school, ann_sv), "matches": m}
 
 
 def school_centroids(result):

@@ -1047,6 +1047,42 @@ int crimac_schools_stats(const int* labels, int n_range, long n_pings, const flo
                          long long* row_sum, long long* ping_sum, double* sv_sum, long long* sv_pixels, long long* found,
                          int* edges, void* scratch, long scratch_bytes, void* stream);
 
+/* ---- schools scored against the annotations (csrc/schools.hip) -------------------------------------------------------
+ * The ANNOTATED schools of a class are the connected regions of one raw annotation id, and the overlap of predicted and
+ * annotated schools is a third labelling: with A and B two label planes of the same connectivity, two adjacent pixels of
+ * the plane `A >= 0 && B >= 0` are adjacent foreground pixels of A and of B, so every component of that plane lies in
+ * exactly ONE (school of A, school of B) pair.  crimac_schools_stats of that plane is the table of pair overlaps (several
+ * rows per pair at most; the host adds them up): the same exact integers and ordered fp64 sums, no new atomics.
+ *
+ * crimac_schools_label_ids: crimac_schools_label with the raw annotation ids as the plane.
+ *   ids int16 [ids_pings][n_range], RANGE fastest (the chunk layout of the labels); column ids_ping_off of ids belongs to
+ *     column 0 of labels, and [ids_ping_off, ids_ping_off + n_pings) must lie inside [0, ids_pings).
+ *   select >= 0: a pixel is foreground when its id == select (27 = sandeel for class 1, 1 = other for class 2: the mapping
+ *     of csrc/labels.hip).  select == CRIMAC_SCHOOLS_IDS_IGNORED: foreground is an id the label transform ignores, i.e. any
+ *     id but 0, 27 and 1.  Any other negative select is refused.
+ *   labels, status, connectivity, the 2^31 limit and the launches (three and one 4-byte memset): as crimac_schools_label.
+ *   The tile read is a transposition (16 rows x 64 pings from a range-contiguous source), staged through the tile's LDS with
+ *   the lanes along range; its rate has not been measured. */
+#define CRIMAC_SCHOOLS_IDS_IGNORED (-2)
+int crimac_schools_label_ids(const short* ids, long ids_pings, long ids_ping_off, int n_range, long n_pings, int select,
+                             int connectivity, int* labels, int* status, void* stream);
+
+/* crimac_schools_label_both: crimac_schools_label with foreground = `a[i] >= 0 && b[i] >= 0`.
+ *   a, b int32 [n_range][n_pings]: two label planes (only their sign is read; neither is written).  labels must be a third
+ *   array.  labels, status, connectivity, the 2^31 limit and the launches: as crimac_schools_label. */
+int crimac_schools_label_both(const int* a, const int* b, int n_range, long n_pings, int connectivity, int* labels,
+                              int* status, void* stream);
+
+/* crimac_schools_pair_anchors: the pair of every row of an overlap table.
+ *   anchor int32 [capacity], found int64 [1]: what crimac_schools_stats wrote for the plane of crimac_schools_label_both
+ *     (device; found is read by the kernel, nothing is waited for); a, b: the two label planes that call was given.
+ *   pair int32 [capacity][2]: for each row k < min(found, capacity), pair[k] = (a[anchor[k]], b[anchor[k]]) -- the ANCHORS of
+ *     the school of a and of the school of b the component lies in.  The other rows are not written.
+ *   The host translates anchors to table rows by a search in the (ascending) anchor column of either table; an anchor that
+ *   is absent there is a school its table dropped (min_pixels).  One launch. */
+int crimac_schools_pair_anchors(const int* anchor, const long long* found, long capacity, const int* a, const int* b,
+                                int* pair, void* stream);
+
 /* ---- measurement support (bench.py only, not on the product path) --------------------------- */
 
 /* MFMA-only calibration launch: `blocks` workgroups of 4 waves each issue iters x 8 v_mfma_f32_16x16x32_bf16 on
